@@ -423,6 +423,35 @@ def dry_launch(rank, world, json_fd):
     dist.destroy_process_group()
 
 
+DUMP_SAMPLE = 1 << 20          # entries of x written by --dump-outputs: 8 MB of float64
+
+
+def dump_outputs(out_dir, ws, n, r0, r1, rank, dist):
+    """--dump-outputs DIR: what the timed cg! handed back to its caller after the last timed step, as float64 .npy files --
+    x.npy (the solution; above DUMP_SAMPLE rows a fixed, seeded sample of it, in global row order), x_index.npy (the global
+    rows of that sample), residuals.npy (the residual history of the last solve) and niter.npy.  The inputs (the operator,
+    b = ones, x0 = 0) do not change from run to run, so two builds can be compared output for output."""
+    import numpy as np
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    lo, hi = np.searchsorted(idx, [r0, r1])
+    x = ws.x.to_host()[idx[lo:hi] - r0]           # this rank's rows of the sample
+    if dist is not None:                          # ranks hold consecutive row blocks: rank order is row order
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, x)
+        x = np.concatenate(parts)
+    if rank != 0:
+        return
+    st = ws.stats
+    assert x.size == idx.size, (x.size, idx.size)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("x", x), ("x_index", idx), ("residuals", st.residuals), ("niter", [st.niter])):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+    log(f"bench.py: outputs of the last timed step written to {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -445,7 +474,11 @@ def main():
                     help="exercise only the N-rank launch + rendezvous (gloo), no GPU work: tests/test_bench_launch.py")
     ap.add_argument("--also-variant1", action="store_true",
                     help="also time single-reduction CG and report it as the nested entry single_reduction_cg (always done with --gpus > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed cg! returned (x, residual history, niter) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         sys.exit(launch_ranks(args, sys.argv[1:]))      # no launcher around us: be the launcher (one rank per GPU)
@@ -589,6 +622,8 @@ def main():
     launches = prof_main["spmv"][0] + prof_main["spmv_boundary"][0]        # interior + boundary launches of a row-partitioned product
     spmv_ms = prof_main["spmv"][1] + prof_main["spmv_boundary"][1]
     ctx.set_option("profile_spmv", 0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ws, n, r0, r1, rank, dist if world > 1 else None)
     # N > 1: every rank's phase times to rank 0; then the same K iterations with the halo overlap off and with the communication
     # stream at default priority (an A/B inside ONE launch: the one scaling run the driver may get should explain itself)
     phases, ab = None, None

@@ -39,6 +39,11 @@ if [ -f "$KH/krylov.h" ]; then
   g++ -O2 -fPIC -shared -std=c++17 -I"$KH" -I"$HERE/../include" -o "$HERE/libkrylov_hip_capi.so" "$SRC/capi_compat.cpp" \
       -L"$HERE" -lkrylov_hip -Wl,-rpath,'$ORIGIN'
   echo "built $HERE/libkrylov_hip_capi.so"
+elif [ -f "$HERE/../oracle/_ref/libkrylov_hip_capi.so" ]; then
+  # no header here: the copy that `make -C oracle refhip` kept beside the reference clients, built from the same
+  # capi_compat.cpp where the header was; it loads the libkrylov_hip.so just built above (rpath $ORIGIN)
+  cp -f "$HERE/../oracle/_ref/libkrylov_hip_capi.so" "$HERE/libkrylov_hip_capi.so"
+  echo "krylov.h not found (KRYLOV_H_DIR): installed oracle/_ref/libkrylov_hip_capi.so as $HERE/libkrylov_hip_capi.so"
 else
   echo "krylov.h not found (KRYLOV_H_DIR): libkrylov_hip_capi.so not rebuilt"
 fi
