@@ -467,6 +467,45 @@ int khip_cg_last_path(khip_cg_workspace *ws);
 double           *khip_cg_vector(khip_cg_workspace *ws, const char *name);
 size_t            khip_cg_workspace_bytes(khip_cg_workspace *ws);                  /* storage test, test/test_allocations.jl:41-57 */
 
+/* ---- minres! (src/minres.jl:164-484), real Float64.  MinresWorkspace (src/krylov_workspaces.jl:77-114): window = length of the
+ * forward-error window err_vec (the reference's workspace keyword, default 5).  The MINRES-only scalars travel in their own struct;
+ * khip_options / khip_stats keep their layout.  NaN in etol / conlim -> the reference's defaults sqrt(eps) / 1 / sqrt(eps). */
+typedef struct khip_minres_workspace khip_minres_workspace;
+typedef struct {
+  double lambda;              /* λ: solve (A + λ I) x = b                     (src/minres.jl:141, 283-285) */
+  double etol;                /* forward-error tolerance over the window      (:146, :443) */
+  double conlim;              /* condition-number limit                       (:147, :437) */
+} khip_minres_params;
+khip_minres_params khip_minres_default_params(void);   /* lambda = 0, etol = conlim = NaN */
+int khip_minres_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, int window, khip_minres_workspace **out);
+/* MinresWorkspace on the caller's x, r1, r2, w1, w2, y (distinct device vectors of n doubles); adopt_vector names: "dx" (Δx: hand
+ * it over, then khip_minres_warm_start(ws, dx) only sets the flag), "v" (the preconditioned vector, needed with M), "npc_dir" */
+int khip_minres_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, int window, double *x, double *r1, double *r2, double *w1,
+                                double *w2, double *y, khip_minres_workspace **out);
+int khip_minres_workspace_adopt_vector(khip_minres_workspace *ws, const char *name, double *ptr);
+int khip_minres_workspace_destroy(khip_minres_workspace *ws);
+int khip_minres_warm_start(khip_minres_workspace *ws, const double *x0);
+/* minres!(ws, A, b; M, λ, atol, rtol, etol, conlim, itmax, timemax, verbose, history, callback).  M == NULL means M = I, otherwise
+ * v <- M r (M must be symmetric positive definite).  options.linesearch != 0 (nonpositive-curvature detection) returns
+ * KHIP_ERR_UNSUPPORTED; options.radius / restart / reorthogonalization / variant are ignored.  params == NULL: the defaults.
+ * Loops (khip_minres_last_path): 2 = device-resident (CSR operator, M = I, no callback, verbose = 0, window <= 64), 1 = host-driven
+ * on the fused kernels (same bits as 2), 0 = one launch per primitive (options.fused = 0). */
+int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const khip_operator *M, const double *b,
+                      const khip_options *opts, const khip_minres_params *params);
+double           *khip_minres_solution(khip_minres_workspace *ws);
+const khip_stats *khip_minres_stats(khip_minres_workspace *ws);      /* residuals = the reference's stats.residuals */
+/* stats.Aresiduals and stats.Acond of the last solve (history = true), owned by the workspace until its next solve */
+int khip_minres_histories(khip_minres_workspace *ws, const double **aresiduals, int *naresiduals, const double **acond,
+                          int *nacond);
+int khip_minres_last_path(khip_minres_workspace *ws);
+/* 1 when the last solve's Lanczos step (y = ((A v + λ v) / β) - (β / oldβ) r1 and v.y) ran inside the CSR handle's product -- the
+ * sliced SpMV kernel (khip_spmv_kernel_info 4 on a coded or int32 sliced copy) carries it as an epilogue; 0 when the product and the
+ * step were separate passes (other kernels, user operators, options.fused = 0); -1 without a workspace */
+int khip_minres_fused_product(khip_minres_workspace *ws);
+/* named work vectors: "x", "r1", "r2", "w1", "w2", "y", "v", "dx", "npc_dir" */
+double           *khip_minres_vector(khip_minres_workspace *ws, const char *name);
+size_t            khip_minres_workspace_bytes(khip_minres_workspace *ws);   /* 6n doubles without M and without warm start */
+
 int khip_gmres_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, int memory, khip_gmres_workspace **out);
 /* GmresWorkspace on the caller's x, w and basis V_host[0 .. memory) (device pointers in a HOST array; `V::Vector{S}`,
  * src/krylov_workspaces.jl:2857-2873).  adopt_vector names: "x", "w", "p", "q", "dx".  adopt_basis replaces the whole list

@@ -404,6 +404,65 @@ function Krylov.bicgstab!(ws::BicgstabWs, A::HIPCsr, b::HIPVector; c::HIPVector 
   return ws
 end
 
+# ------------------------------------------------------------------------------------------------ minres!  (src/minres.jl:164-484)
+struct MinresParams                 # khip_minres_params: λ, etol, conlim
+  lambda::Cdouble; etol::Cdouble; conlim::Cdouble
+end
+const MinresWs = MinresWorkspace{Float64,Float64,HIPVector}
+function minres_handle(ws::MinresWs)
+  get!(HANDLES, ws) do
+    r = Ref{Ptr{Cvoid}}()
+    ck(ccall((:khip_minres_workspace_adopt, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                                                        Ptr{Cdouble}, Ptr{Cdouble}, Ref{Ptr{Cvoid}}),
+             CTX[].h, ws.m, ws.n, length(ws.err_vec), ws.x.ptr, ws.r1.ptr, ws.r2.ptr, ws.w1.ptr, ws.w2.ptr, ws.y.ptr, r))
+    h = r[]
+    finalizer(_ -> ccall((:khip_minres_workspace_destroy, lib), Cint, (Ptr{Cvoid},), h), ws)
+    h
+  end
+end
+minres_adopt(h, name, v::HIPVector) = ck(ccall((:khip_minres_workspace_adopt_vector, lib), Cint, (Ptr{Cvoid}, Cstring, Ptr{Cdouble}), h, name, dptr(v)))
+
+function Krylov.minres!(ws::MinresWs, A::HIPCsr, b::HIPVector; M = I, ldiv::Bool = false, linesearch::Bool = false, λ::Float64 = 0.0,
+                        atol::Float64 = √eps(Float64), rtol::Float64 = √eps(Float64), etol::Float64 = √eps(Float64),
+                        conlim::Float64 = 1/√eps(Float64), itmax::Int = 0, timemax::Float64 = Inf, verbose::Int = 0,
+                        history::Bool = false, callback = nothing, iostream::IO = Krylov.kstdout, fused::Int = 2)
+  if ldiv || linesearch || !native_precond(M) || !native_log(verbose, iostream)     # linesearch: nonpositive curvature is generic-only
+    GENERIC_SOLVES[] += 1
+    return invoke(Krylov.minres!, Tuple{MinresWs,Any,AbstractVector{Float64}}, ws, A, b; M, ldiv, linesearch, λ, atol, rtol, etol, conlim,
+                  itmax, timemax, verbose, history, callback = callback === nothing ? (w -> false) : callback, iostream)
+  end
+  m, n = size(A)                                                                            # the reference's own argument checks, :172-179
+  (m == ws.m && n == ws.n) || error("(workspace.m, workspace.n) = ($(ws.m), $(ws.n)) is inconsistent with size(A) = ($m, $n)")
+  m == n || error("System must be square")
+  length(b) == n || error("Inconsistent problem size")
+  Krylov.allocate_if(M !== I, ws, :v, HIPVector, ws.x)                                        # :192
+  h = minres_handle(ws)
+  for (name, v) in (("v", ws.v), ("npc_dir", ws.npc_dir), ("dx", ws.Δx))
+    minres_adopt(h, name, v)
+  end
+  ws.warm_start && ck(ccall((:khip_minres_warm_start, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h, ws.Δx.ptr))
+  sp = ccall((:khip_minres_stats, lib), Ptr{Stats}, (Ptr{Cvoid},), h)
+  cbf, cbd, box = callback_args(user_callback(callback), ws, sp, history)
+  opts = Ref(Options(; atol, rtol, itmax, timemax, history, fused, verbose, log_fd = logfd(iostream), callback = cbf, callback_data = cbd))
+  prm = Ref(MinresParams(λ, etol, conlim))
+  opA = Ref(Operator(A))
+  rc = GC.@preserve ws A b M opts prm opA box ccall((:khip_minres_solve, lib), Cint,
+                                                     (Ptr{Cvoid}, Ref{Operator}, Ptr{Operator}, Ptr{Cdouble}, Ref{Options}, Ptr{Cvoid}),
+                                                     h, opA, opref(M), b.ptr, opts, prm)
+  st = fill_stats!(ws.stats, sp, history)
+  if history                                                                                # stats.Aresiduals, stats.Acond
+    ar, nar, ac, nac = Ref{Ptr{Cvoid}}(), Ref{Cint}(0), Ref{Ptr{Cvoid}}(), Ref{Cint}(0)
+    ck(ccall((:khip_minres_histories, lib), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Cint}, Ref{Ptr{Cvoid}}, Ref{Cint}), h, ar, nar, ac, nac))
+    nar[] > 0 && append!(ws.stats.Aresiduals, unsafe_wrap(Array, Ptr{Float64}(ar[]), Int(nar[])))
+    nac[] > 0 && append!(ws.stats.Acond, unsafe_wrap(Array, Ptr{Float64}(ac[]), Int(nac[])))
+  end
+  NATIVE_SOLVES[] += 1;  LAST_PATH[] = ccall((:khip_minres_last_path, lib), Cint, (Ptr{Cvoid},), h)
+  ws.warm_start = false
+  finish_callback(box)
+  rc == 0 || failed(st)
+  return ws
+end
+
 # ------------------------------------------------------------------------------------------------ device matrix (block solvers)
 # Tall blocks are libkrylov_hip panels (ROW-major, rows padded to 16, padding rows zero), small blocks host matrices -- exactly
 # where the library keeps them (csrc/block.cpp) and where the reference's own small LAPACK calls run.  INTEGRATION.md has the

@@ -185,6 +185,20 @@ end
     @test ws.stats.residuals ≈ ws2.stats.residuals rtol = 1e-6
   end
 
+  @testset "MINRES -- $FC" begin                                      # symmetric; also indefinite through the shift λ
+    b = S(b_cpu)
+    x, stats = native(2) do; minres(A_gpu, b); end
+    @test stats.solved
+    ws = MinresWorkspace(nA, nA, S); ws2 = MinresWorkspace(nA, nA, S)
+    native(2) do; krylov_solve!(ws, A_gpu, b; history = true); end
+    generic(minres!, ws2, A_gpu, b; history = true)
+    @test ws.stats.niter == ws2.stats.niter
+    @test ws.stats.residuals ≈ ws2.stats.residuals rtol = 1e-8
+    @test length(ws.stats.Aresiduals) == length(ws.stats.Acond) == ws.stats.niter + 1
+    native(1) do; minres!(ws, A_gpu, b; M = KrylovHIP.jacobi(A_gpu)); end
+    @test ws.stats.solved
+  end
+
   @testset "block-GMRES -- $FC" begin
     p = 4
     B_cpu = hcat((U_cpu * (collect(1.0:nA) .^ (j / 4)) for j in 1:p)...)

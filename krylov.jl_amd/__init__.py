@@ -54,6 +54,10 @@ class COptions(C.Structure):
                 ("callback_data", C.c_void_p), ("variant", C.c_int), ("verbose", C.c_int), ("log_fd", C.c_int)]
 
 
+class CMinresParams(C.Structure):
+    _fields_ = [("lambda_", C.c_double), ("etol", C.c_double), ("conlim", C.c_double)]
+
+
 class CStats(C.Structure):
     _fields_ = [("niter", C.c_int), ("solved", C.c_int), ("inconsistent", C.c_int), ("indefinite", C.c_int),
                 ("npcCount", C.c_int), ("timer", C.c_double), ("status", C.c_char * 96),
@@ -203,6 +207,21 @@ SIGNATURES = {
     "khip_bicgstab_stats": (C.POINTER(CStats), [_vp]),
     "khip_bicgstab_last_path": (_int, [_vp]),
     "khip_bicgstab_workspace_bytes": (_sz, [_vp]),
+    "khip_minres_default_params": (CMinresParams, []),
+    "khip_minres_workspace_create": (_int, [_vp, _i64, _i64, _int, c_void_pp]),
+    "khip_minres_workspace_adopt": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, c_void_pp]),
+    "khip_minres_workspace_adopt_vector": (_int, [_vp, C.c_char_p, _vp]),
+    "khip_minres_workspace_destroy": (_int, [_vp]),
+    "khip_minres_warm_start": (_int, [_vp, _vp]),
+    "khip_minres_solve": (_int, [_vp, C.POINTER(COperator), C.POINTER(COperator), _vp, C.POINTER(COptions),
+                                 C.POINTER(CMinresParams)]),
+    "khip_minres_solution": (_vp, [_vp]),
+    "khip_minres_stats": (C.POINTER(CStats), [_vp]),
+    "khip_minres_histories": (_int, [_vp, C.POINTER(c_double_p), C.POINTER(_int), C.POINTER(c_double_p), C.POINTER(_int)]),
+    "khip_minres_last_path": (_int, [_vp]),
+    "khip_minres_fused_product": (_int, [_vp]),
+    "khip_minres_vector": (_vp, [_vp, C.c_char_p]),
+    "khip_minres_workspace_bytes": (_sz, [_vp]),
     "khip_block_gmres_workspace_bytes": (_sz, [_vp, C.POINTER(C.c_size_t)]),
     "khip_test_gen_banded_random_host": (_int, [_i64, _int, _int, C.c_uint64, _int, _int, _i64, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_double_p, C.POINTER(_i64)]),
     "khip_test_small_dense": (_int, [_int, _int, _int, _int, c_double_p, c_double_p, c_double_p]),
@@ -1217,6 +1236,45 @@ class BicgstabWorkspace(_Workspace):
             _ck(lib().khip_bicgstab_workspace_create(ctx._h, m, n, C.byref(self._h)))
 
 
+class MinresWorkspace(_Workspace):
+    """MinresWorkspace(m, n, S; window = 5) (src/krylov_workspaces.jl:77-114).  stats carries Aresiduals and Acond."""
+    _prefix = "minres"
+
+    def __init__(self, ctx: Context, m: int, n: int, window: int = 5, adopt: bool | None = None):
+        self.ctx, self.m, self.n, self.window = ctx, m, n, window
+        self.adopted = _adopt_default() if adopt is None else bool(adopt)
+        self._h = C.c_void_p()
+        if self.adopted:
+            t0 = time.perf_counter()
+            self._vec = {k: ctx.empty(n) for k in ("x", "r1", "r2", "w1", "w2", "y")}     # dx, npc_dir, v stay empty
+            self._alloc_s = time.perf_counter() - t0
+            v = self._vec
+            _ck(lib().khip_minres_workspace_adopt(ctx._h, m, n, window, v["x"].ptr, v["r1"].ptr, v["r2"].ptr, v["w1"].ptr,
+                                                  v["w2"].ptr, v["y"].ptr, C.byref(self._h)))
+        else:
+            _ck(lib().khip_minres_workspace_create(ctx._h, m, n, window, C.byref(self._h)))
+
+    @property
+    def stats(self) -> SimpleStats:
+        st = super().stats
+        ar, nar, ac, nac = c_double_p(), _int(), c_double_p(), _int()
+        _ck(lib().khip_minres_histories(self._h, C.byref(ar), C.byref(nar), C.byref(ac), C.byref(nac)))
+        st.Aresiduals = np.array(ar[:nar.value]) if nar.value else np.zeros(0)
+        st.Acond = np.array(ac[:nac.value]) if nac.value else np.zeros(0)
+        return st
+
+    @property
+    def fused_product(self) -> bool:
+        """The last solve's Lanczos step ran inside the sliced SpMV (khip_minres_fused_product)."""
+        return lib().khip_minres_fused_product(self._h) == 1
+
+    def vector(self, name: str):
+        if self.adopted and name in self._vec:
+            return self._vec[name]
+        p = lib().khip_minres_vector(self._h, name.encode())
+        return DeviceVector(self.ctx, self.n, ptr=p, owner=self) if p else None
+
+
 def _finish(ws, rc):
     ws._timer_extra = 0.0          # an entry point that did work of its own before the solve adds it afterwards
     if rc != 0:
@@ -1261,6 +1319,23 @@ def bicgstab_(ws: BicgstabWorkspace, A, b: DeviceVector, c: DeviceVector | None 
     return _finish(ws, rc)
 
 
+def minres_(ws: MinresWorkspace, A, b: DeviceVector, M=None, λ=0.0, etol=None, conlim=None, **kw):
+    """minres!(workspace, A, b; M, ldiv, linesearch, λ, atol, rtol, etol, conlim, itmax, timemax, verbose, history, callback,
+    iostream) (src/minres.jl:164-484).  linesearch = true is refused (KHIP_ERR_UNSUPPORTED).  Returns the workspace."""
+    keep = []
+    ws._allocate_if(M is not None, "v")                                                   # src/minres.jl:192
+    opts = _make_options(keep=keep, ws=ws, **kw)
+    prm = lib().khip_minres_default_params()
+    prm.lambda_ = float(λ)
+    if etol is not None:
+        prm.etol = etol
+    if conlim is not None:
+        prm.conlim = conlim
+    rc = lib().khip_minres_solve(ws._h, _make_operator(ws.ctx, A, ws.n, keep), _make_operator(ws.ctx, M, ws.n, keep), _p(b),
+                                 C.byref(opts), C.byref(prm))
+    return _finish(ws, rc)
+
+
 def _local_rows(A):
     return A.m if isinstance(A, CsrMatrix) else None
 
@@ -1281,8 +1356,17 @@ FORWARDED_DEFAULTS = {
                      history=False, callback=default_callback, iostream=None),
     "block_gmres": dict(M=None, N=None, ldiv=False, restart=False, reorthogonalization=False, atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0,
                         timemax=math.inf, verbose=0, history=False, callback=default_callback, iostream=None),
+    "minres": dict(M=None, ldiv=False, linesearch=False, λ=0.0, atol=_SQRT_EPS, rtol=_SQRT_EPS, etol=_SQRT_EPS,
+                   conlim=1.0 / _SQRT_EPS, itmax=0, timemax=math.inf, verbose=0, history=False, callback=default_callback,
+                   iostream=None),
 }
 WORKSPACE_KWARGS = {"gmres": dict(memory=20), "block_gmres": dict(memory=5)}      # kwargs_workspace_gmres, _block_gmres
+# kwargs_workspace_minres (src/minres.jl:159): kept apart from WORKSPACE_KWARGS, whose contents tests/test_abi.py pins
+MINRES_WORKSPACE_KWARGS = dict(window=5)
+
+
+def _workspace_kwargs(method: str) -> dict:
+    return MINRES_WORKSPACE_KWARGS if method == "minres" else WORKSPACE_KWARGS.get(method, {})
 
 
 def _forward(method: str, kw: dict) -> dict:
@@ -1295,7 +1379,8 @@ def _forward(method: str, kw: dict) -> dict:
 
 def krylov_workspace(method: str, *args, ctx: Context | None = None, **kw):
     """krylov_workspace(Val(method), m, n, S; memory) / (Val(method), A, b; memory) (src/interface.jl:117-141, 237-244)."""
-    cls = {"cg": CgWorkspace, "gmres": GmresWorkspace, "bicgstab": BicgstabWorkspace, "block_gmres": BlockGmresWorkspace}[method]
+    cls = {"cg": CgWorkspace, "gmres": GmresWorkspace, "bicgstab": BicgstabWorkspace, "block_gmres": BlockGmresWorkspace,
+           "minres": MinresWorkspace}[method]
     if len(args) == 2 and isinstance(args[1], DeviceVector):                  # (A, b)
         A, b = args
         return cls(b.ctx, len(b), len(b), **kw)
@@ -1331,7 +1416,7 @@ def krylov_solve_(ws, A, b, x0=None, **kw):
 def krylov_solve(method: str, A, b, x0=None, ctx: Context | None = None, **kw):
     """krylov_solve(Val(method), A, b[, x0]; kwargs...) = method(A, b[, x0]; kwargs...) (src/interface.jl:146-199): a fresh
     workspace (its creation charged to `timemax` and `stats.timer`), every keyword forwarded.  Returns (x, stats, workspace)."""
-    wkw = {k: kw.pop(k) for k in list(kw) if k in WORKSPACE_KWARGS.get(method, {})}
+    wkw = {k: kw.pop(k) for k in list(kw) if k in _workspace_kwargs(method)}
     t0 = time.perf_counter()
     if method == "block_gmres":
         B = np.asarray(b, dtype=np.float64)
@@ -1361,6 +1446,11 @@ def gmres(A, b: DeviceVector, x0=None, **kw):
 
 def bicgstab(A, b: DeviceVector, x0=None, **kw):
     return krylov_solve("bicgstab", A, b, x0, **kw)
+
+
+def minres(A, b: DeviceVector, x0=None, **kw):
+    """Out-of-place minres(A, b[, x0]; window, kwargs...) -> (x, stats, workspace) (src/minres.jl:164-172)."""
+    return krylov_solve("minres", A, b, x0, **kw)
 
 
 # --------------------------------------------------------------------------- Krylov processes
@@ -1797,4 +1887,4 @@ def block_gmres(A, B, X0=None, ctx=None, **kw):
 
 
 _INPLACE.update({CgWorkspace: ("cg", cg_), GmresWorkspace: ("gmres", gmres_), BicgstabWorkspace: ("bicgstab", bicgstab_),
-                 BlockGmresWorkspace: ("block_gmres", block_gmres_)})
+                 BlockGmresWorkspace: ("block_gmres", block_gmres_), MinresWorkspace: ("minres", minres_)})

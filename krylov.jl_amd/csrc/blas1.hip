@@ -12,7 +12,6 @@
 
 namespace khip {
 
-typedef double dbl2 __attribute__((ext_vector_type(2)));
 
 enum MapOp {
   OP_COPY = 0,      // y = x
@@ -27,24 +26,6 @@ enum MapOp {
   OP_VMUL = 9,      // w = x * y   (diagonal operator)
   OP_VDIV = 10,     // w = x / y   (Jacobi: z = r ./ diag(A))
 };
-
-template <int VEC> struct VecT;
-template <> struct VecT<1> { using type = double; };
-template <> struct VecT<2> { using type = dbl2; };
-
-__device__ __forceinline__ double vget(const double &v, int) { return v; }
-__device__ __forceinline__ double vget(const dbl2 &v, int i) { return i == 0 ? v.x : v.y; }
-__device__ __forceinline__ void vset(double &v, int, double s) { v = s; }
-__device__ __forceinline__ void vset(dbl2 &v, int i, double s) { if (i == 0) v.x = s; else v.y = s; }
-
-template <bool NT, typename T> __device__ __forceinline__ T ldg(const T *p) {
-  if (NT) return __builtin_nontemporal_load(p);
-  return *p;
-}
-template <bool NT, typename T> __device__ __forceinline__ void stg(T v, T *p) {
-  if (NT) __builtin_nontemporal_store(v, p);
-  else *p = v;
-}
 
 template <int OP> __host__ __device__ constexpr bool reads_x() {
   return OP == OP_COPY || OP == OP_SCALCOPY || OP == OP_DIVCOPY || OP == OP_AXPY || OP == OP_AXPBY ||

@@ -32,7 +32,6 @@ extern "C" int khip_panel_rows(int64_t n, int64_t *n_pad);
 namespace {
 
 constexpr double kEps = std::numeric_limits<double>::epsilon();
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // ---- small dense helpers, column-major (LAPACK DGEQR2 / DORG2R / DORM2R semantics) ----------
 double nrm2_h(int n, const double *x) {

@@ -26,6 +26,26 @@
 
 namespace khip {
 
+// element access of the streaming kernels (blas1.hip, minres.cpp): VEC = 2 moves 16 bytes per lane; NT = non-temporal
+typedef double dbl2 __attribute__((ext_vector_type(2)));
+template <int VEC> struct VecT;
+template <> struct VecT<1> { using type = double; };
+template <> struct VecT<2> { using type = dbl2; };
+
+__device__ __forceinline__ double vget(const double &v, int) { return v; }
+__device__ __forceinline__ double vget(const dbl2 &v, int i) { return i == 0 ? v.x : v.y; }
+__device__ __forceinline__ void vset(double &v, int, double s) { v = s; }
+__device__ __forceinline__ void vset(dbl2 &v, int i, double s) { if (i == 0) v.x = s; else v.y = s; }
+
+template <bool NT, typename T> __device__ __forceinline__ T ldg(const T *p) {
+  if (NT) return __builtin_nontemporal_load(p);
+  return *p;
+}
+template <bool NT, typename T> __device__ __forceinline__ void stg(T v, T *p) {
+  if (NT) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+
 constexpr int kBlock = 256;            // 4 waves of 64
 constexpr int kWavesPerBlock = kBlock / 64;
 constexpr int kFinishMaxBlocks = 256;

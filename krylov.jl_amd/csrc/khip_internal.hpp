@@ -5,6 +5,7 @@
 
 #include <unistd.h>
 
+#include <chrono>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -153,6 +154,13 @@ struct SeqCtl {
   void *epi_state = nullptr;
 };
 
+// Lanczos epilogue of minres! carried by the next fused SpMV (spmv_common.hpp SpmvArgs::lz*); empty outside minres!'s loops
+struct LanczosEpi {
+  const double *coef = nullptr;          // device (lambda, 1 / beta, -beta / oldbeta)
+  const double *r1 = nullptr;
+  int sub_r1 = 0;
+};
+
 }  // namespace khip
 
 struct khip_ctx {
@@ -183,6 +191,7 @@ struct khip_ctx {
   int next_slot = 0;
   khip::Tuning tune;
   khip::SeqCtl ctl;                    // empty except inside a device-resident solver loop
+  khip::LanczosEpi lz;                 // empty except for minres!'s fused product (spmv_takes_lanczos)
   khip::Comm *comm = nullptr;
   void *panel_scratch = nullptr;       // panel.hip: V^T Q partial tiles + Psi staging ring
   // SpMV launch profiling (events recorded on `stream`, resolved lazily)
@@ -347,6 +356,9 @@ int launch_spmv(khip_ctx *ctx, const khip_csr *A, const double *x, double *y, in
                 const double *dotw = nullptr, int dot_sq = 0,      // dot_sq: 0 none, 1 second output y.y, 2 second output dotw.dotw
                 int64_t hole_lo = 0, int64_t hole_hi = 0);         // hole_hi > hole_lo: rows [hole_lo, hole_hi) are left out (two ranges, one launch where the kernel can)
 int spmv_kernel_choice(const khip_ctx *ctx, const khip_csr *A);
+// true when a full-range fused product on this handle runs the sliced kernel, which carries minres!'s Lanczos epilogue (ctx->lz);
+// performs the lazy builds launch_spmv would perform first, so the answer holds for the next launch
+bool spmv_takes_lanczos(khip_ctx *ctx, const khip_csr *A);
 int launch_spmm(khip_ctx *ctx, const khip_csr *A, const double *X, double *Y, int p);
 int csr_finalize(khip_ctx *ctx, khip_csr *A);   // row statistics after arrays are resident
 int csr_transpose(khip_ctx *ctx, const khip_csr *A, khip_csr *T);   // T = A' (fresh handle, deterministic entry order)
@@ -421,6 +433,14 @@ inline bool time_limit_reached(khip_ctx *ctx, double elapsed_s, double timemax) 
   if (comm_nranks(ctx) > 1 && comm_allreduce_sum_host(ctx, &over, 1) != KHIP_OK) return true;   // a broken communicator ends the solve
   return over > 0.0;
 }
+
+// wall clock of the solvers' timers (stats.timer, timemax)
+inline double now_s() {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+// y <- op x: the user's apply callback, else the CSR handle's product (solvers.cpp)
+int apply_op(khip_ctx *ctx, const khip_operator *op, const double *x, double *y);
+constexpr long long kHistWindowMax = 1 << 14;   // device history window of the device-resident loops (entries); ctx option "hist_window" shrinks it (tests)
 
 // rows of the GLOBAL operator (= n on one GPU): a distributed handle knows it, otherwise the local counts are summed
 inline int64_t global_rows(khip_ctx *ctx, const khip_operator *A, int64_t n_local) {

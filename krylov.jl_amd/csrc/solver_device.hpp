@@ -14,7 +14,8 @@
 
 namespace khip {
 
-enum Epilogue { EPI_NONE = 0, EPI_CG_STEP1 = 1, EPI_CG_STEP2 = 2, EPI_BICG_A = 3, EPI_BICG_B = 4, EPI_BICG_C = 5, EPI_CGCG = 6 };
+enum Epilogue { EPI_NONE = 0, EPI_CG_STEP1 = 1, EPI_CG_STEP2 = 2, EPI_BICG_A = 3, EPI_BICG_B = 4, EPI_BICG_C = 5, EPI_CGCG = 6,
+               EPI_MINRES_A = 7, EPI_MINRES_B = 8, EPI_MINRES_C = 9 };
 
 struct CgDevState {
   double gamma;        // r.z of the current iterate              (src/cg.jl:162, 257)
@@ -59,6 +60,125 @@ struct BicgDevState {
 };
 
 constexpr long long kSeqNever = 0x7fffffffffffffffLL;
+
+// minres! (src/minres.jl:164-484) with linesearch = false: the scalars of the Lanczos recurrence and of the Givens QR, the
+// norm estimates and the stopping tests.  The same three steps run on the host (host-driven loop, fused = 1) and as the
+// epilogues of the three reductions of an iteration (device-resident loop, fused = 2): one source, the same IEEE operations in
+// the reference's order, so both loops produce the same bits.  Field names follow the reference.
+constexpr int kMinresWindowMax = 64;     // err_vec entries the device state carries; larger windows run the host-driven loop
+
+struct MinresDevState {
+  // the Lanczos product's coefficients, contiguous: the sliced SpMV reads them as SpmvArgs::lz_coef[0..2]
+  double lambda;       // λ                                            (:173)
+  double inv_beta;     // one(T) / β: kdiv!(y, β) (:284) and the v / β term of w (:299)
+  double c_r1;         // -β / oldβ                                    (:285)
+  // constants of the solve
+  double beta1;        // β₁                                           (:231)
+  double eps_tol;      // ε = atol + rtol β₁                           (:274)
+  double etol, ctol;   // etol, 1 / conlim                             (:202)
+  long long itmax;
+  int window, MisI;
+  // recurrences (values of the current iteration)
+  double beta, oldbeta, alpha, delta, dbar, epsln;   // β, oldβ, α, δ, δbar, ϵ
+  double cs, sn, phibar, phi, gamma, gbar, root;     // cs, sn, ϕbar, ϕ, γ, γbar, root
+  double gmin, gmax, ANorm2, xENorm2, rhs1, rhs2, err_lbnd;
+  double rNorm, ArNorm, Acond, ANorm, xNorm, test1, test2;
+  // coefficients the vector kernels read
+  double c_r2;         // -α / β                                       (:288)
+  double inv_gamma;    // one(T) / γ: kdiv!(w, γ)                      (:325)
+  long long stop_seq, iter, hist_base, hist_cap;
+  double *hist_r, *hist_ar, *hist_acond;   // device history windows (null: no history)
+  int solved, zero_resid, ill_cond_mach, ill_cond_lim, fwd_err, lsq_exit, not_pd;
+  double err_vec[kMinresWindowMax];
+};
+
+// Julia's max / min on Float64 (NaN wins)
+__host__ __device__ inline double jl_max(double a, double b) { return (a != a || b != b) ? a + b : (a > b ? a : b); }
+__host__ __device__ inline double jl_min(double a, double b) { return (a != a || b != b) ? a + b : (a < b ? a : b); }
+
+// after the dot v.y of the Lanczos product (:287-288, :291)
+__host__ __device__ inline void minres_step_a(MinresDevState &s, double vy) {
+  s.alpha = vy / s.beta;
+  s.c_r2 = -s.alpha / s.beta;
+  s.delta = s.cs * s.dbar + s.sn * s.alpha;
+}
+
+// after beta^2 = r2.v of the next Lanczos vector (:305-336, :348-351); false when beta^2 < 0 (M not positive definite)
+__host__ __device__ inline bool minres_step_b(MinresDevState &s, double beta2, long long k) {
+  s.oldbeta = s.beta;
+  if (beta2 < 0) { s.not_pd = 1; return false; }
+  s.beta = sqrt(beta2);
+  s.ANorm2 = s.ANorm2 + s.alpha * s.alpha + s.oldbeta * s.oldbeta + s.beta * s.beta;
+  s.gbar = s.sn * s.dbar - s.cs * s.alpha;
+  s.epsln = s.sn * s.beta;
+  s.dbar = -s.cs * s.beta;
+  s.root = sqrt(s.gbar * s.gbar + s.dbar * s.dbar);
+  s.ArNorm = s.phibar * s.root;
+  double g = sqrt(s.gbar * s.gbar + s.beta * s.beta);
+  s.gamma = jl_max(g, 2.220446049250313e-16);
+  s.inv_gamma = 1.0 / s.gamma;
+  s.cs = s.gbar / s.gamma;
+  s.sn = s.beta / s.gamma;
+  s.phi = s.cs * s.phibar;
+  s.phibar = s.sn * s.phibar;
+  s.inv_beta = 1.0 / s.beta;       // for the next iteration's product and w update
+  s.c_r1 = -s.beta / s.oldbeta;
+  if (s.hist_ar) {
+    const long long idx = k - 1 - s.hist_base;
+    if (idx >= 0 && idx < s.hist_cap) s.hist_ar[idx] = s.ArNorm;
+  }
+  return true;
+}
+
+// after xNorm = knorm(n, x) of the updated iterate (:378, :385-451); k = iter.  err_vec: window entries.  True when the loop stops.
+__host__ __device__ inline bool minres_step_c(MinresDevState &s, double xNorm, long long k, double *err_vec) {
+  const double epsM = 2.220446049250313e-16;
+  s.xENorm2 = s.xENorm2 + s.phi * s.phi;
+  const int window = s.window;
+  err_vec[k % window] = s.phi;
+  if (k >= window) {                          // knorm(window, err_vec)
+    double acc = 0.0;
+    for (int i = 0; i < window; ++i) acc = acc + err_vec[i] * err_vec[i];
+    s.err_lbnd = sqrt(acc);
+  }
+  s.gmax = jl_max(s.gmax, s.gamma);
+  s.gmin = jl_min(s.gmin, s.gamma);
+  const double zeta = s.rhs1 / s.gamma;
+  s.rhs1 = s.rhs2 - s.delta * zeta;
+  s.rhs2 = -s.epsln * zeta;
+  s.ANorm = sqrt(s.ANorm2);
+  s.xNorm = xNorm;
+  s.rNorm = s.phibar;
+  s.test1 = s.rNorm / (s.ANorm * s.xNorm);
+  s.test2 = s.root / s.ANorm;
+  s.Acond = s.gmax / s.gmin;
+  if (s.hist_r) {
+    const long long idx = k - 1 - s.hist_base;
+    if (idx >= 0 && idx < s.hist_cap) { s.hist_r[idx] = s.rNorm; s.hist_acond[idx] = s.Acond; }
+  }
+  s.iter = k;
+  if (k == 1 && s.beta / s.beta1 <= 10 * epsM) {   // A b = 0: x = 0 is a minimum least-squares solution (:410-419)
+    s.lsq_exit = 1;
+    s.solved = 1;
+    return true;
+  }
+  const double inv_acond = 1.0 / s.Acond;
+  s.ill_cond_mach = (1.0 + inv_acond <= 1.0);
+  const bool solved_mach = (1.0 + s.test2 <= 1.0);
+  const bool zero_resid_mach = (1.0 + s.test1 <= 1.0);
+  const bool resid_decrease_mach = (s.rNorm + 1.0 <= 1.0);
+  const bool tired = k >= s.itmax;
+  s.ill_cond_lim = (inv_acond <= s.ctol);
+  const bool solved_lim = (s.test2 <= s.eps_tol);
+  const bool zero_resid_lim = s.MisI && (s.test1 <= epsM);
+  const bool resid_decrease_lim = (s.rNorm <= s.eps_tol);
+  if (k >= window) s.fwd_err = (s.err_lbnd <= s.etol * sqrt(s.xENorm2));
+  s.zero_resid = zero_resid_mach || zero_resid_lim;
+  const bool resid_decrease = resid_decrease_mach || resid_decrease_lim;
+  const bool ill_cond = s.ill_cond_mach || s.ill_cond_lim;
+  s.solved = solved_mach || solved_lim || s.zero_resid || s.fwd_err || resid_decrease;
+  return s.solved || tired || ill_cond;
+}
 
 __device__ __forceinline__ bool seq_skip(const long long *stop_seq, long long seq) {
   return stop_seq != nullptr && seq >= *stop_seq;
@@ -125,6 +245,14 @@ __device__ inline void solver_epilogue(int epi, void *state, const double *v, lo
     st->beta = beta;
     st->alpha = gamma_next / denom;
     st->gamma = gamma_next;
+  } else if (epi == EPI_MINRES_A) {               // v[0] = v.y                 src/minres.jl:287-291
+    minres_step_a(*static_cast<MinresDevState *>(state), v[0]);
+  } else if (epi == EPI_MINRES_B) {                // v[0] = y.y = beta^2        :305-336
+    MinresDevState *st = static_cast<MinresDevState *>(state);
+    if (!minres_step_b(*st, v[0], st->iter + 1)) st->stop_seq = seq + 1;
+  } else if (epi == EPI_MINRES_C) {                // v[0] = x.x                 :348-451
+    MinresDevState *st = static_cast<MinresDevState *>(state);
+    if (minres_step_c(*st, sqrt(v[0]), st->iter + 1, st->err_vec)) st->stop_seq = seq + 1;
   } else if (epi == EPI_BICG_A) {                  // v[0] = c.v                 src/bicgstab.jl:223
     BicgDevState *st = static_cast<BicgDevState *>(state);
     st->alpha = st->rho / v[0];

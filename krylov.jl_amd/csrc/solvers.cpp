@@ -25,9 +25,6 @@ namespace {
 
 constexpr double kEps = std::numeric_limits<double>::epsilon();
 
-double now_s() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 double tol_or_default(double t) { return std::isnan(t) ? std::sqrt(kEps) : t; }
 double timemax_of(const khip_options &o) {
   return (std::isnan(o.timemax) || o.timemax <= 0) ? std::numeric_limits<double>::infinity() : o.timemax;
@@ -66,16 +63,6 @@ struct StatsBox {
     return rc;
   }
 };
-
-int apply_op(khip_ctx *ctx, const khip_operator *op, const double *x, double *y) {
-  if (op->apply) {
-    int rc = op->apply(op->self, x, y);
-    if (rc != 0) { set_error("user operator returned %d", rc); return KHIP_ERR_INVALID; }
-    return KHIP_OK;
-  }
-  if (!op->csr) { set_error("operator has neither a CSR handle nor an apply callback"); return KHIP_ERR_INVALID; }
-  return khip_spmv(ctx, op->csr, x, y);
-}
 
 int64_t padded(int64_t n) { return (n + 31) & ~(int64_t)31; }   // 256-byte multiples keep every slice 16-B aligned
 
@@ -139,6 +126,16 @@ inline bool kdisplay(int64_t iter, int verbose) { return verbose > 0 && iter % v
 
 }  // namespace
 
+int khip::apply_op(khip_ctx *ctx, const khip_operator *op, const double *x, double *y) {
+  if (op->apply) {
+    int rc = op->apply(op->self, x, y);
+    if (rc != 0) { set_error("user operator returned %d", rc); return KHIP_ERR_INVALID; }
+    return KHIP_OK;
+  }
+  if (!op->csr) { set_error("operator has neither a CSR handle nor an apply callback"); return KHIP_ERR_INVALID; }
+  return khip_spmv(ctx, op->csr, x, y);
+}
+
 // ================================================================== CG ==========
 struct khip_cg_workspace {
   khip_ctx *ctx;
@@ -159,7 +156,6 @@ struct khip_cg_workspace {
 namespace {
 
 constexpr int kDevChunk = 4;             // iterations enqueued between two snapshots of the device state
-constexpr long long kHistWindowMax = 1 << 14;   // device history window (entries); ctx option "hist_window" shrinks it (tests)
 
 // The loop of src/cg.jl:195-268 with scalars and stopping tests on the device.  Preconditions (checked by
 // the caller): CSR operator, M = I, radius = 0, no linesearch, no callback.  On return the vectors are in

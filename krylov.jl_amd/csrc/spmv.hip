@@ -614,6 +614,7 @@ __global__ __launch_bounds__(kBlock) void spmv_sell_kernel(SpmvArgs a, RedArgs r
           }
         }
       }
+      if (DOT && a.lz) acc = lanczos_row(a, rowl, acc, wv);   // minres!: y = ((A v + lambda v) / beta) - (beta / oldbeta) r1, wv = v[row]
       store_y(a, rowl, acc);
       if (DOT) {
         acc_prod<COMP>(dacc[0], wv, acc);
@@ -1393,6 +1394,31 @@ int spmv_kernel_choice(const khip_ctx *ctx, const khip_csr *A) {
   return kernel;
 }
 
+// The decisions of launch_spmv's kernel-4 branch that lead to spmv_sell_kernel, with the same lazy builds (the coded stream at the
+// top of launch_spmv, then the sliced copies): the fused product carries the Lanczos epilogue exactly when this holds.
+bool spmv_takes_lanczos(khip_ctx *ctx, const khip_csr *A) {
+  if (ctx->tune.spmv_kernel == 0 && A->code_state == 0 && A->mean_row_nnz > 12.0 && A->mean_row_nnz <= 64.0 && A->max_row_nnz <= 64 &&
+      ctx->tune.spmv_codes && (ctx->tune.spmv_codes != 1 || A->nnz >= ((int64_t)1 << 22)) && ctx->tune.spmv_nt == 0 && !ctx->tune.spmv_fake_gather &&
+      !(A->tmpl_id && ctx->tune.spmv_template))
+    optional_build(csr_build_codes(ctx, const_cast<khip_csr *>(A)));
+  if (spmv_kernel_choice(ctx, A) != 4) return false;
+  khip_csr *Am = const_cast<khip_csr *>(A);
+  const bool nt = ctx->tune.spmv_nt != 0, fake = ctx->tune.spmv_fake_gather != 0;
+  const bool try_codes = ctx->tune.spmv_codes && (ctx->tune.spmv_codes != 1 || A->nnz >= ((int64_t)1 << 22)) && !nt && !fake;
+  if (try_codes && Am->code_state == 0) optional_build(csr_build_codes(ctx, Am));
+  const bool coded = try_codes && Am->code_state == 1;
+  if (coded && ctx->tune.spmv_sell && Am->code_bits == 8 && Am->sell_state == 0 && ctx->tune.spmv_pipe <= 0) optional_build(csr_build_sell(ctx, Am));
+  const bool sliced = coded && ctx->tune.spmv_sell && Am->sell_state == 1 && ctx->tune.spmv_pipe <= 0;
+  if (coded) return sliced;
+  int rows = ctx->tune.spmv_rows;
+  if (rows != 256 && rows != 128 && rows != 64 && rows != 32) rows = 256;
+  while (rows > 32 && rows * A->mean_row_nnz > 2048.0) rows >>= 1;
+  const bool try32 = ctx->tune.spmv_sell && !nt && !fake && ctx->tune.spmv_pipe <= 0 && rows == 256 &&
+                     (ctx->tune.spmv_codes == 2 || ctx->tune.spmv_sell >= 3 || A->nnz >= ((int64_t)1 << 22));
+  if (try32 && Am->sell32_state == 0) optional_build(csr_build_sell32(ctx, Am));
+  return try32 && Am->sell32_state == 1;
+}
+
 int launch_spmv(khip_ctx *ctx, const khip_csr *A, const double *x, double *y, int dot_slot, int64_t row_lo,
                 int64_t row_hi, int64_t *wave_cursor, bool finish, const double *dotw, int dot_sq, int64_t hole_lo, int64_t hole_hi) {
   int64_t local_cursor = 0;
@@ -1405,6 +1431,11 @@ int launch_spmv(khip_ctx *ctx, const khip_csr *A, const double *x, double *y, in
       ctx->tune.spmv_codes && (ctx->tune.spmv_codes != 1 || A->nnz >= ((int64_t)1 << 22)) && ctx->tune.spmv_nt == 0 && !ctx->tune.spmv_fake_gather &&
       !(A->tmpl_id && ctx->tune.spmv_template))
     optional_build(csr_build_codes(ctx, const_cast<khip_csr *>(A)));
+  // minres!'s Lanczos epilogue rides only on the sliced kernel's fused dot (the caller asked spmv_takes_lanczos): anything else is a defect
+  if (ctx->lz.coef && (dot_slot < 0 || dot_sq || !spmv_takes_lanczos(ctx, A))) {
+    set_error("spmv: the Lanczos epilogue reached a product that does not run the sliced kernel with a fused dot");
+    return KHIP_ERR_INVALID;
+  }
   // Two ranges [row_lo, hole_lo) and [hole_hi, row_hi) in one launch (the boundary rows of a row-partitioned product, api.cpp
   // spmv_any): taken by the staged / coded kernels when the first range is whole row blocks; anything else runs them as two launches.
   bool hole = hole_hi > hole_lo && hole_lo >= row_lo && hole_hi <= row_hi;
@@ -1462,6 +1493,7 @@ int launch_spmv(khip_ctx *ctx, const khip_csr *A, const double *x, double *y, in
   a.stream_nt = ctx->tune.spmv_stream_nt;
   a.dcode = nullptr; a.dbase = nullptr; a.desc_ptr = nullptr; a.desc_pos = nullptr; a.desc_col = nullptr;
   a.blockptr = (ctx->tune.spmv_blockptr && A->blockptr && (row_lo & 255) == 0) ? A->blockptr : nullptr;
+  a.lz = ctx->lz.coef != nullptr; a.lz_sub_r1 = ctx->lz.sub_r1; a.lz_coef = ctx->lz.coef; a.lz_r1 = ctx->lz.r1;
   const bool dot = dot_slot >= 0, comp = ctx->tune.compensated != 0, dist = A->dist;
   const bool persist = ctx->tune.spmv_persist != 0;
   const bool nt = ctx->tune.spmv_nt != 0;

@@ -63,7 +63,23 @@ struct SpmvArgs {
   const int32_t *desc_col;   // escape: column
   int stage_rows;            // coded / pipelined / delta kernels: rows per block (256, 128, 64 or 32)
   int max_row;               // pipelined kernel: longest row of the operator (uniform trip count of the row walk)
+  // Lanczos epilogue of minres! (sliced kernel only, with the fused dot and dotw = x = v; read only when lz != 0):
+  //   y = ((A v + lz_coef[0] v) * lz_coef[1]) + lz_coef[2] r1   (the r1 term when lz_sub_r1), results[slot] = v . y
+  // with lz_coef = (lambda, 1 / beta, -beta / oldbeta) in device memory (MinresDevState)
+  int lz, lz_sub_r1;
+  const double *lz_coef;
+  const double *lz_r1;
 };
+
+// the Lanczos epilogue of one row: the expressions of kaxpy! (fma), kdiv! (kscal! by 1 / beta) and kaxpy! (src/minres.jl:283-285)
+__device__ __forceinline__ double lanczos_row(const SpmvArgs &a, int64_t row, double av, double v) {
+  const double lam = a.lz_coef[0], ib = a.lz_coef[1], c1 = a.lz_coef[2];
+  double t = av;
+  if (lam != 0.0) t = fma(lam, v, t);
+  t = ib * t;
+  if (a.lz_sub_r1) t = fma(c1, a.lz_r1[row], t);
+  return t;
+}
 
 template <bool NT, typename T>
 __device__ __forceinline__ T ld(const T *p) {
