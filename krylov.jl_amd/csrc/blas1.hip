@@ -546,7 +546,7 @@ __global__ void combine_kernel(const dd *gathered, int nranks, int count, RedArg
       hi = s;
       lo += v.lo + e;
     }
-    ra.results[ra.slot + i] = hi + lo;
+    ra.results[ra.slot + i] = dd_value(hi, lo);
   }
   __syncthreads();
   if (threadIdx.x == 0 && ra.epi) solver_epilogue(ra.epi, ra.epi_state, ra.results + ra.slot, ra.seq);

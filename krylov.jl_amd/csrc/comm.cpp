@@ -673,7 +673,7 @@ int comm_allreduce_dd(khip_ctx *ctx, dd *vals_dev, int count, double *out_host) 
       hi = s;
       lo += v.lo + e;
     }
-    out_host[i] = hi + lo;
+    out_host[i] = dd_value(hi, lo);
   }
   return KHIP_OK;
 }

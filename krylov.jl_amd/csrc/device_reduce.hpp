@@ -235,7 +235,7 @@ __global__ __launch_bounds__(kBlock) void reduce_finish_kernel(RedArgs ra, int64
     if (threadIdx.x == 0) {
 #pragma unroll
       for (int o = 0; o < NOUT; ++o) {
-        ra.results[ra.slot + o] = acc[o].hi + acc[o].lo;
+        ra.results[ra.slot + o] = dd_value(acc[o].hi, acc[o].lo);
         ra.results_dd[ra.slot + o] = acc[o];
       }
       if (ra.epi) solver_epilogue(ra.epi, ra.epi_state, ra.results + ra.slot, ra.seq);
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(kBlock) void reduce_finish_kernel(RedArgs ra, int64
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int o = 0; o < NOUT; ++o) {
-      ra.results[ra.slot + o] = fin[o].hi + fin[o].lo;
+      ra.results[ra.slot + o] = dd_value(fin[o].hi, fin[o].lo);
       ra.results_dd[ra.slot + o] = fin[o];
     }
     __hip_atomic_store(ra.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -70,6 +70,11 @@ struct dd {
   double hi, lo;
 };
 
+// The double a (hi, lo) partial stands for.  Once hi is not finite (one overflowing product, a +-Inf input), TwoSum has
+// left lo = NaN (Inf - Inf inside it); hi alone then carries the plain sum's result: +-Inf, or NaN for Inf - Inf or a NaN
+// input.  Finite partials give hi + lo, bit for bit as before.
+__host__ __device__ inline double dd_value(double hi, double lo) { return __builtin_isfinite(hi) ? hi + lo : hi; }
+
 constexpr int kMaxNout = 4;           // outputs one reduction launch may produce (dot2 = 2)
 constexpr int kMaxRedOut = 64;        // scalars one all-reduce call may carry (multi-GPU)
 constexpr int kResultSlots = 256;     // device-resident scalar ring (chained MGS coefficients)

@@ -515,7 +515,7 @@ static double ko_dot2(int64_t n, const double *x, const double *y) {
     h = s;
     l += e + lo[t];
   }
-  return h + l;
+  return isfinite(h) ? h + l : h;   /* h = +-Inf or NaN: l is NaN (Inf - Inf in TwoSum); h is the plain sum's result */
 }
 
 double ko_dot(int64_t n, const double *x, const double *y) {
