@@ -20,18 +20,14 @@
 // rank-deficient block, which the reference does not support either, docs/src/interfaces/reference.md:236,
 // comes out like LAPACK's: A = QR with a tiny diagonal entry).  Only p x p matrices are ever handled on the host.
 #include <chrono>
-#include <cmath>
-#include <limits>
 
-#include "khip_internal.hpp"
+#include "solver_host.hpp"
 
 using namespace khip;
 
 extern "C" int khip_panel_rows(int64_t n, int64_t *n_pad);
 
 namespace {
-
-constexpr double kEps = std::numeric_limits<double>::epsilon();
 
 // ---- small dense helpers, column-major (LAPACK DGEQR2 / DORG2R / DORM2R semantics) ----------
 double nrm2_h(int n, const double *x) {
@@ -202,17 +198,6 @@ void householder_signs(int p, int64_t n, double *Q1, double *S, double *tau) {
     }
   }
 }
-
-struct StatsBoxB {
-  khip_stats st;
-  std::vector<double> residuals;
-  int path = -1;       // khip_block_gmres_last_path: 1 once the library's loop (tile SpMM + fused panel sweeps) has run a solve
-  StatsBoxB() { memset(&st, 0, sizeof(st)); snprintf(st.status, sizeof(st.status), "unknown"); }
-  void reset() { residuals.clear(); st.residuals = nullptr; st.nres = 0; st.indefinite = 0; st.npcCount = 0; st.error[0] = 0; }
-  void publish() { st.residuals = residuals.empty() ? nullptr : residuals.data(); st.nres = (int)residuals.size(); }
-  int fail(int code, const char *msg) { snprintf(st.error, sizeof(st.error), "%s", msg); set_error("%s", msg); publish(); return code; }
-  int fail_rc(int rc) { snprintf(st.error, sizeof(st.error), "%s", khip_last_error()); publish(); return rc; }
-};
 
 }  // namespace
 
@@ -449,22 +434,13 @@ struct khip_block_gmres_workspace {
   std::vector<double> sweep, Yall, tmp;                        // staging of the fused sweeps: mem p x p each (grown with the basis), p x p
   std::vector<const double *> Vp;
   bool warm_start = false;
-  std::vector<const double *> borrowed;                        // panels of a caller's BlockGmresWorkspace (khip_block_gmres_workspace_adopt)
+  Borrowed borrowed;                                           // panels of a caller's BlockGmresWorkspace (khip_block_gmres_workspace_adopt)
   khip_grow_fn grow = nullptr;                                 // the caller's push!(V, SM(undef, n, p)) (src/block_gmres.jl:300-305)
   void *grow_data = nullptr;
-  StatsBoxB box;
-  bool is_borrowed(const double *q) const { for (const double *b : borrowed) if (b == q) return true; return false; }
-  void borrow(const double *q) { if (q && !is_borrowed(q)) borrowed.push_back(q); }
-  void unborrow(const double *q) { for (size_t i = 0; i < borrowed.size(); ++i) if (borrowed[i] == q) { borrowed.erase(borrowed.begin() + (long)i); return; } }
+  StatsBox box;                                                // path: 1 once the library's loop (tile SpMM + fused panel sweeps) has run a solve
 };
 
-#define KB(expr)                                        \
-  do {                                                  \
-    int rc_k = (expr);                                  \
-    if (rc_k != KHIP_OK) return ws->box.fail_rc(rc_k);  \
-  } while (0)
-
-static thread_local double g_alloc_seconds = 0.0;              // stats.allocation_timer (allocate_if, src/krylov_utils.jl:290-297)
+// a zeroed panel, its allocation timed for stats.allocation_timer (allocate_if, src/krylov_utils.jl:290-297)
 static int alloc_panel(khip_ctx *ctx, int64_t np, int p, double **out) {
   const double t_alloc = now_s();
   const int rc_alloc = khip_malloc(ctx, sizeof(double) * (size_t)np * p, reinterpret_cast<void **>(out));
@@ -510,7 +486,7 @@ int khip_block_gmres_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, int p
   }
   if (rc) { khip_block_gmres_workspace_destroy(ws); return rc; }
   block_host_arrays(ws, memory);
-  g_alloc_seconds = 0.0;
+  (void)take_alloc_seconds();
   ws->box.st.allocation_timer = now_s() - t_create;                // workspace.stats.allocation_timer, :161
   *out = ws;
   return KHIP_OK;
@@ -529,10 +505,10 @@ int khip_block_gmres_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, int p,
   ws->ctx = ctx; ws->m = m; ws->n = n; ws->p = p; ws->mem = memory;
   khip_panel_rows(n, &ws->np);
   ws->X = X; ws->W = W;
-  ws->borrow(X); ws->borrow(W);
-  for (int i = 0; i < memory; ++i) { ws->V.push_back(V_host[i]); ws->borrow(V_host[i]); }
+  ws->borrowed.add(X); ws->borrowed.add(W);
+  for (int i = 0; i < memory; ++i) { ws->V.push_back(V_host[i]); ws->borrowed.add(V_host[i]); }
   block_host_arrays(ws, memory);
-  g_alloc_seconds = 0.0;
+  (void)take_alloc_seconds();
   ws->box.st.allocation_timer = 0.0;
   *out = ws;
   return KHIP_OK;
@@ -540,28 +516,15 @@ int khip_block_gmres_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, int p,
 
 int khip_block_gmres_workspace_adopt_panel(khip_block_gmres_workspace *ws, const char *name, double *ptr) {
   KHIP_REQUIRE(ws && name, "block_gmres_workspace_adopt_panel: null argument");
-  struct { const char *k; double **slot; bool required; } tab[] = {
-      {"X", &ws->X, true}, {"W", &ws->W, true}, {"P", &ws->Pn, false}, {"Q", &ws->Qm, false}, {"dX", &ws->dX, false}};
-  for (auto &e : tab)
-    if (strcmp(e.k, name) == 0) {
-      KHIP_REQUIRE(ptr || !e.required, "block_gmres_workspace_adopt_panel: X and W cannot be emptied");
-      if (*e.slot == ptr) return KHIP_OK;                       // nothing changes, in particular not who owns the panel
-      if (ptr) {                                                // one panel, one slot (`borrowed` is a set of pointers)
-        for (auto &o : tab) KHIP_REQUIRE(o.slot == e.slot || *o.slot != ptr, "block_gmres_workspace_adopt_panel: the pointer already is another panel of the workspace");
-        for (const double *v : ws->V) KHIP_REQUIRE(v != ptr, "block_gmres_workspace_adopt_panel: the pointer already is a basis panel of the workspace");
-      }
-      if (*e.slot) { if (ws->is_borrowed(*e.slot)) ws->unborrow(*e.slot); else khip_free(ws->ctx, *e.slot); }
-      *e.slot = ptr;
-      ws->borrow(ptr);
-      return KHIP_OK;
-    }
-  set_error("block_gmres_workspace_adopt_panel: unknown panel '%s' (X, W, P, Q, dX)", name);
-  return KHIP_ERR_INVALID;
+  using S = NamedSlot;
+  return adopt_named(ws->ctx, ws->borrowed, {{"X", &ws->X, S::Required}, {"W", &ws->W, S::Required}, {"P", &ws->Pn, S::Optional},
+                     {"Q", &ws->Qm, S::Optional}, {"dX", &ws->dX, S::Optional}}, "block_gmres_workspace_adopt_panel", "panel", name,
+                     ptr, &ws->V);
 }
 
 int khip_block_gmres_workspace_adopt_basis(khip_block_gmres_workspace *ws, int k, double *const *V_host) {
   KHIP_REQUIRE(ws && k >= 1 && V_host, "block_gmres_workspace_adopt_basis: bad argument");
-  for (double *v : ws->V) KHIP_REQUIRE(ws->is_borrowed(v), "block_gmres_workspace_adopt_basis: this workspace owns its basis");
+  for (double *v : ws->V) KHIP_REQUIRE(ws->borrowed.has(v), "block_gmres_workspace_adopt_basis: this workspace owns its basis");
   KHIP_REQUIRE(k >= ws->mem, "block_gmres_workspace_adopt_basis: fewer panels than the workspace's memory");
   for (int i = 0; i < k; ++i) {
     KHIP_REQUIRE(V_host[i] != nullptr, "block_gmres_workspace_adopt_basis: null basis panel");
@@ -569,9 +532,9 @@ int khip_block_gmres_workspace_adopt_basis(khip_block_gmres_workspace *ws, int k
       KHIP_REQUIRE(V_host[i] != named, "block_gmres_workspace_adopt_basis: a basis panel is also one of X, W, P, Q, dX");
     for (int j = 0; j < i; ++j) KHIP_REQUIRE(V_host[i] != V_host[j], "block_gmres_workspace_adopt_basis: the same panel twice");
   }
-  for (double *v : ws->V) ws->unborrow(v);
+  for (double *v : ws->V) ws->borrowed.drop(v);
   ws->V.assign(V_host, V_host + k);
-  for (double *v : ws->V) ws->borrow(v);
+  for (double *v : ws->V) ws->borrowed.add(v);
   return KHIP_OK;
 }
 
@@ -583,8 +546,8 @@ int khip_block_gmres_workspace_set_grow(khip_block_gmres_workspace *ws, khip_gro
 
 int khip_block_gmres_workspace_destroy(khip_block_gmres_workspace *ws) {
   if (!ws) return KHIP_OK;
-  for (double *v : {ws->dX, ws->X, ws->W, ws->Bp, ws->Pn, ws->Qm}) if (v && !ws->is_borrowed(v)) khip_free(ws->ctx, v);
-  for (double *v : ws->V) if (v && !ws->is_borrowed(v)) khip_free(ws->ctx, v);
+  for (double *v : {ws->dX, ws->X, ws->W, ws->Bp, ws->Pn, ws->Qm}) free_unless_borrowed(ws->ctx, ws->borrowed, v);
+  for (double *v : ws->V) free_unless_borrowed(ws->ctx, ws->borrowed, v);
   delete ws;
   return KHIP_OK;
 }
@@ -652,22 +615,22 @@ static int block_gmres_solve_impl(khip_block_gmres_workspace *ws, const khip_ope
   KHIP_REQUIRE(ws && A && B_in, "block_gmres_solve: null argument");
   khip_ctx *ctx = ws->ctx;
   khip_options o = opts_in ? *opts_in : khip_default_options();
-  g_alloc_seconds = 0.0;
+  (void)take_alloc_seconds();
   const double t0 = now_s();
-  const double timemax = (std::isnan(o.timemax) || o.timemax <= 0) ? std::numeric_limits<double>::infinity() : o.timemax;
+  const double timemax = timemax_of(o);
   const int64_t n = ws->n, np = ws->np;
   const int p = ws->p;
   const int64_t len = np * p;                       // panel length in doubles (padding rows stay zero)
   const size_t pp = (size_t)p * p;
   khip_stats *st = &ws->box.st;
-  const double atol = std::isnan(o.atol) ? std::sqrt(kEps) : o.atol, rtol = std::isnan(o.rtol) ? std::sqrt(kEps) : o.rtol;
+  const double atol = tol_or_default(o.atol), rtol = tol_or_default(o.rtol);
   const bool restart = o.restart != 0, reorth = o.reorthogonalization != 0;
   if (ws->m != ws->n) return ws->box.fail(KHIP_ERR_INVALID, "System must be square");
   if (o.verbose > 0) klogf(o.log_fd, "BLOCK-GMRES: system of size %lld with %d right-hand sides\n", (long long)ws->n, ws->p);   // src/block_gmres.jl:120
   if (o.variant != 0) return ws->box.fail(KHIP_ERR_INVALID, "block_gmres: options.variant must be 0 (there is no other recurrence)");
 
-  if (restart && !ws->dX) KB(alloc_panel(ctx, np, p, &ws->dX));
-  if (!B_is_panel && !ws->Bp) KB(alloc_panel(ctx, np, p, &ws->Bp));                // adopted workspaces have no panel copy of B until a column-major B arrives
+  if (restart && !ws->dX) K(alloc_panel(ctx, np, p, &ws->dX));
+  if (!B_is_panel && !ws->Bp) K(alloc_panel(ctx, np, p, &ws->Bp));                // adopted workspaces have no panel copy of B until a column-major B arrives
   double *dX = ws->dX, *X = ws->X, *W = ws->W;
   const double *Bp = B_is_panel ? B_in : ws->Bp;
   std::vector<double *> &V = ws->V;
@@ -678,24 +641,24 @@ static int block_gmres_solve_impl(khip_block_gmres_workspace *ws, const khip_ope
   ws->box.reset();
   ws->box.path = 1;
   const bool MisI = (M == nullptr), NisI = (N == nullptr);
-  if (!MisI && !ws->Qm) KB(alloc_panel(ctx, np, p, &ws->Qm));                      // :146
-  if (!NisI && !ws->Pn) KB(alloc_panel(ctx, np, p, &ws->Pn));                      // :147
+  if (!MisI && !ws->Qm) K(alloc_panel(ctx, np, p, &ws->Qm));                      // :146
+  if (!NisI && !ws->Pn) K(alloc_panel(ctx, np, p, &ws->Pn));                      // :147
   double *Q = MisI ? W : ws->Qm, *R0 = MisI ? W : ws->Qm;
   double *Xr = restart ? dX : X;
   bool xr_zeroed = true;            // Xr holds what the update of :324-326 accumulates into (X itself without restart)
 
-  if (!B_is_panel) KB(khip_panel_from_colmajor(ctx, n, p, B_in, ws->Bp));
-  KB(khip_fill(ctx, len, X, 0.0));                                                 // src/block_gmres.jl:155
+  if (!B_is_panel) K(khip_panel_from_colmajor(ctx, n, p, B_in, ws->Bp));
+  K(khip_fill(ctx, len, X, 0.0));                                                 // src/block_gmres.jl:155
   if (warm_start) {
-    KB(apply_block_op(ctx, A, dX, W, p));
-    KB(khip_axpby(ctx, len, 1.0, Bp, -1.0, W));                                    // W .= B .- W
-    if (restart) KB(khip_axpy(ctx, len, 1.0, dX, X));
+    K(apply_block_op(ctx, A, dX, W, p));
+    K(khip_axpby(ctx, len, 1.0, Bp, -1.0, W));                                    // W .= B .- W
+    if (restart) K(khip_axpy(ctx, len, 1.0, dX, X));
   } else {
-    KB(khip_copy(ctx, len, W, Bp));
+    K(khip_copy(ctx, len, W, Bp));
   }
-  if (!MisI) KB(apply_block_op(ctx, M, W, R0, p));                                 // R0 = M (B - A X0)  :165
+  if (!MisI) K(apply_block_op(ctx, M, W, R0, p));                                 // R0 = M (B - A X0)  :165
   double RNorm;
-  KB(khip_panel_norm(ctx, n, p, R0, &RNorm));                                      // :166
+  K(khip_panel_norm(ctx, n, p, R0, &RNorm));                                      // :166
   if (o.history) ws->box.residuals.push_back(RNorm);
   const double eps_tol = atol + rtol * RNorm;
 
@@ -728,18 +691,18 @@ static int block_gmres_solve_impl(khip_block_gmres_workspace *ws, const khip_ope
       // from beta = 0 instead (the panel kernels do not read X then: same bits as 1 * 0 + sum) and the fill + one panel read
       // per cycle go away -- unless a callback could look at the workspace's dX during the cycle.
       xr_zeroed = o.callback != nullptr;
-      if (xr_zeroed) KB(khip_fill(ctx, len, Xr, 0.0));
+      if (xr_zeroed) K(khip_fill(ctx, len, Xr, 0.0));
       if (npass >= 1) {
         // the residual block of a restart goes straight into V[1] (the copy of :211 is the only reader of R0)
         double *Wr = MisI ? V[0] : W;
-        KB(apply_block_op(ctx, A, X, Wr, p));
-        KB(khip_axpby(ctx, len, 1.0, Bp, -1.0, Wr));
-        if (!MisI) KB(apply_block_op(ctx, M, W, V[0], p));
+        K(apply_block_op(ctx, A, X, Wr, p));
+        K(khip_axpby(ctx, len, 1.0, Bp, -1.0, Wr));
+        if (!MisI) K(apply_block_op(ctx, M, W, V[0], p));
       }
     }
 
-    if (!(restart && npass >= 1)) KB(khip_copy(ctx, len, V[0], R0));               // :211
-    KB(khip_panel_qr(ctx, n, p, V[0], Z[0].data()));                               // :212 householder!(V[1], Z[1], ..)
+    if (!(restart && npass >= 1)) K(khip_copy(ctx, len, V[0], R0));               // :211
+    K(khip_panel_qr(ctx, n, p, V[0], Z[0].data()));                               // :212 householder!(V[1], Z[1], ..)
 
     npass = npass + 1;
     inner_iter = 0;
@@ -755,13 +718,13 @@ static int block_gmres_solve_impl(khip_block_gmres_workspace *ws, const khip_ope
       }
 
       double *Pk = NisI ? V[inner_iter - 1] : ws->Pn;
-      if (!NisI) KB(apply_block_op(ctx, N, V[inner_iter - 1], Pk, p));             // :241  P <- N V_k
+      if (!NisI) K(apply_block_op(ctx, N, V[inner_iter - 1], Pk, p));             // :241  P <- N V_k
       // Q of this iteration lives in the next basis panel when that exists: the copy of :307 disappears
       double *const Qsave = Q;
       if ((int)V.size() > inner_iter) Q = V[inner_iter];
       double *Wk = MisI ? Q : W;
-      KB(apply_block_op(ctx, A, Pk, Wk, p));                                       // :242  W <- A N V_k
-      if (!MisI) KB(apply_block_op(ctx, M, W, Q, p));                              // :243  Q <- M A N V_k
+      K(apply_block_op(ctx, A, Pk, Wk, p));                                       // :242  W <- A N V_k
+      if (!MisI) K(apply_block_op(ctx, M, W, Q, p));                              // :243  Q <- M A N V_k
       // :244-247 (Psi_i = V_i^T Q ; Q -= V_i Psi_i for i = 1..k) and the reorthogonalisation pass :250-256, each as
       // one sweep whose blocks stay on the device between the steps
       {
@@ -773,16 +736,16 @@ static int block_gmres_solve_impl(khip_block_gmres_workspace *ws, const khip_ope
         // the LAST sweep also returns the Gram matrix of the swept panel (same pass as its last update): the QR's first round
         const bool gram_wanted = ctx->tune.panel_qr_tsqr == 0;
         if (gram.size() < pp) gram.resize(pp);
-        KB(khip::panel_mgs_gram(ctx, n, p, inner_iter, Vp.data(), Q, sweep.data(), 0, (gram_wanted && !reorth) ? gram.data() : nullptr, &have_gram));
+        K(khip::panel_mgs_gram(ctx, n, p, inner_iter, Vp.data(), Q, sweep.data(), 0, (gram_wanted && !reorth) ? gram.data() : nullptr, &have_gram));
         for (int i = 0; i < inner_iter; ++i) std::copy(sweep.begin() + (size_t)i * pp, sweep.begin() + (size_t)(i + 1) * pp, R[nr + i].begin());
         if (reorth) {
-          KB(khip::panel_mgs_gram(ctx, n, p, inner_iter, Vp.data(), Q, sweep.data(), 0, gram_wanted ? gram.data() : nullptr, &have_gram));
+          K(khip::panel_mgs_gram(ctx, n, p, inner_iter, Vp.data(), Q, sweep.data(), 0, gram_wanted ? gram.data() : nullptr, &have_gram));
           for (int i = 0; i < inner_iter; ++i)
             for (size_t l = 0; l < pp; ++l) R[nr + i][l] += sweep[(size_t)i * pp + l];
         }
       }
 
-      KB(panel_qr_tau_impl(ctx, n, p, Q, C.data(), nullptr, have_gram ? gram.data() : nullptr));   // :259 householder!(Q, C, ..)
+      K(panel_qr_tau_impl(ctx, n, p, Q, C.data(), nullptr, have_gram ? gram.data() : nullptr));   // :259 householder!(Q, C, ..)
 
       for (int i = 0; i < inner_iter - 1; ++i) {                                   // :263-269
         for (int j = 0; j < p; ++j)
@@ -848,15 +811,15 @@ static int block_gmres_solve_impl(khip_block_gmres_workspace *ws, const khip_ope
               v = ws->grow(ws->grow_data);
               g_alloc_seconds += now_s() - t_grow;
               if (!v) return ws->box.fail(KHIP_ERR_INVALID, "block_gmres: the workspace's grow callback returned no panel");
-              ws->borrow(v);
+              ws->borrowed.add(v);
             } else {
-              KB(alloc_panel(ctx, np, p, &v));
+              K(alloc_panel(ctx, np, p, &v));
             }
             V.push_back(v);
           }
           while ((int)Z.size() <= inner_iter) Z.emplace_back(pp, 0.0);
         }
-        if (Q != V[inner_iter]) KB(khip_copy(ctx, len, V[inner_iter], Q));         // :307
+        if (Q != V[inner_iter]) K(khip_copy(ctx, len, V[inner_iter], Q));         // :307
         for (int j = 0; j < p; ++j)
           for (int l = 0; l < p; ++l) Z[inner_iter][(size_t)j * p + l] = D[(size_t)j * 2 * p + p + l];
       }
@@ -899,13 +862,13 @@ static int block_gmres_solve_impl(khip_block_gmres_workspace *ws, const khip_ope
         Vp[i] = V[i];
         std::copy(Y[i].begin(), Y[i].begin() + pp, Yall.begin() + (size_t)i * pp);
       }
-      KB(panel_multi_nn(ctx, n, p, inner_iter, Vp.data(), Yall.data(), xr_zeroed ? 1.0 : 0.0, Xr));
+      K(panel_multi_nn(ctx, n, p, inner_iter, Vp.data(), Yall.data(), xr_zeroed ? 1.0 : 0.0, Xr));
     }
     if (!NisI) {                                                                   // :327-330
-      KB(khip_copy(ctx, len, ws->Pn, Xr));
-      KB(apply_block_op(ctx, N, ws->Pn, Xr, p));
+      K(khip_copy(ctx, len, ws->Pn, Xr));
+      K(apply_block_op(ctx, N, ws->Pn, Xr, p));
     }
-    if (restart) KB(khip_axpy(ctx, len, 1.0, Xr, X));
+    if (restart) K(khip_axpy(ctx, len, 1.0, Xr, X));
 
     inner_itmax = inner_itmax - inner_iter;
     iter = iter + inner_iter;
@@ -919,15 +882,14 @@ static int block_gmres_solve_impl(khip_block_gmres_workspace *ws, const khip_ope
   if (overtimed) status = "time limit exceeded";
   if (user_requested_exit) status = "user-requested exit";
 
-  if (warm_start && !restart) KB(khip_axpy(ctx, len, 1.0, dX, X));
+  if (warm_start && !restart) K(khip_axpy(ctx, len, 1.0, dX, X));
   ws->warm_start = false;
-  KB(khip_ctx_sync(ctx));
+  K(khip_ctx_sync(ctx));
 
   st->niter = (int)iter;
   st->solved = solved;
   st->timer = now_s() - t0;
-  st->allocation_timer += g_alloc_seconds;                      // lazy allocations of this solve
-  g_alloc_seconds = 0.0;
+  st->allocation_timer += take_alloc_seconds();                 // lazy allocations of this solve
   snprintf(st->status, sizeof(st->status), "%s", status);
   ws->box.publish();
   return KHIP_OK;

@@ -16,18 +16,14 @@
 // the fused loops agree with the primitive sequence bit for bit on elementwise values and to the reductions' one ulp otherwise;
 // loops 1 and 2 run the same kernels and the same scalar code and produce the same bits.
 #include <chrono>
-#include <cmath>
-#include <limits>
 #include <utility>
 
 #include "device_reduce.hpp"
+#include "solver_host.hpp"
 
 using namespace khip;
 
 namespace {
-
-constexpr double kEps = std::numeric_limits<double>::epsilon();
-constexpr int kDevChunk = 4;                    // iterations enqueued between two snapshots of the device state
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -245,11 +241,6 @@ int lanczos_product(khip_ctx *ctx, const khip_operator *A, bool fuse, int64_t n,
   return launch_p1(ctx, n, st, v, r1, y, sub_r1, slot);
 }
 
-// ------------------------------------------------------------------------------------------------------- host helpers ---
-int64_t padded(int64_t n) { return (n + 31) & ~(int64_t)31; }   // 256-byte multiples, as the other workspaces allocate
-inline bool kdisplay_row(int64_t iter, int verbose) { return verbose > 0 && iter % verbose == 0; }   // kdisplay
-
-
 }  // namespace
 
 struct khip_minres_workspace {
@@ -258,52 +249,14 @@ struct khip_minres_workspace {
   int window;
   double *dx = nullptr, *x = nullptr, *r1 = nullptr, *r2 = nullptr, *npc_dir = nullptr, *w1 = nullptr, *w2 = nullptr,
          *y = nullptr, *v = nullptr;
-  std::vector<const double *> borrowed;     // the caller's vectors (khip_minres_workspace_adopt*): never freed here
+  Borrowed borrowed;                        // the caller's vectors (khip_minres_workspace_adopt*): never freed here
   std::vector<double> err_vec;
   bool warm_start = false;
-  khip_stats st;
-  std::vector<double> residuals, aresiduals, aconds;
-  int path = -1;
+  StatsBox box;
+  std::vector<double> aresiduals, aconds;   // the Aresiduals / Acond histories next to box.residuals
   bool fused_product = false;               // the last solve's Lanczos epilogue ran inside the sliced SpMV
-  double alloc_s = 0.0;
-  // fused loops: device copy of the scalar state (+ pinned host mirror / snapshots), device history windows
-  MinresDevState *dev = nullptr, *pinned = nullptr;
-  double *hist_dev = nullptr;
-  hipEvent_t snap_ev[2] = {nullptr, nullptr};
-
-  bool is_borrowed(const double *p) const {
-    for (const double *q : borrowed) if (q == p) return true;
-    return false;
-  }
-  int alloc(double **slot) {
-    const double t = now_s();
-    const int rc = khip_malloc(ctx, sizeof(double) * (size_t)padded(n > 0 ? n : 1), reinterpret_cast<void **>(slot));
-    alloc_s += now_s() - t;
-    return rc;
-  }
-  void release(double *p) { if (p && !is_borrowed(p)) khip_free(ctx, p); }
-  int fail(int code, const char *msg) {
-    snprintf(st.error, sizeof(st.error), "%s", msg);
-    set_error("%s", msg);
-    publish();
-    return code;
-  }
-  int fail_rc(int rc) {
-    snprintf(st.error, sizeof(st.error), "%s", khip_last_error());
-    publish();
-    return rc;
-  }
-  void publish() {
-    st.residuals = residuals.empty() ? nullptr : residuals.data();
-    st.nres = (int)residuals.size();
-  }
+  DeviceLoop<MinresDevState, 3> loop;       // fused loops: device copy of the scalar state, pinned snapshots + staging, histories
 };
-
-#define K(expr)                                         \
-  do {                                                  \
-    int rc_k = (expr);                                  \
-    if (rc_k != KHIP_OK) return ws->fail_rc(rc_k);      \
-  } while (0)
 
 namespace {
 
@@ -311,18 +264,9 @@ struct Bufs {
   double *x, *r1, *r2, *y, *v, *w1, *w2;   // v == r2 when M = I
 };
 
-// allocation of the device-side state of the fused loops (first fused solve of the workspace)
-int ensure_fused_state(khip_minres_workspace *ws) {
-  if (!ws->dev) KHIP_CHECK_HIP(hipMalloc(&ws->dev, sizeof(MinresDevState)));
-  if (!ws->pinned)
-    KHIP_CHECK_HIP(hipHostMalloc(reinterpret_cast<void **>(&ws->pinned), 3 * sizeof(MinresDevState), hipHostMallocDefault));
-  for (auto &e : ws->snap_ev) if (!e) KHIP_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  return KHIP_OK;
-}
-
 int upload(khip_minres_workspace *ws, const MinresDevState &s) {   // pinned[2] is the staging copy of the host-driven loop
-  ws->pinned[2] = s;
-  KHIP_CHECK_HIP(hipMemcpyAsync(ws->dev, &ws->pinned[2], sizeof(MinresDevState), hipMemcpyHostToDevice, ws->ctx->stream));
+  ws->loop.pinned[2] = s;
+  KHIP_CHECK_HIP(hipMemcpyAsync(ws->loop.dev, &ws->loop.pinned[2], sizeof(MinresDevState), hipMemcpyHostToDevice, ws->ctx->stream));
   return KHIP_OK;
 }
 
@@ -354,15 +298,13 @@ int khip_minres_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, int window
   khip_minres_workspace *ws = new khip_minres_workspace();
   ws->ctx = ctx; ws->m = m; ws->n = n; ws->window = window;
   ws->err_vec.assign((size_t)window, 0.0);
-  memset(&ws->st, 0, sizeof(ws->st));
-  snprintf(ws->st.status, sizeof(ws->st.status), "unknown");
+  (void)take_alloc_seconds();
   // x, r1, r2, w1, w2, y allocated; dx, npc_dir, v stay empty until needed (src/krylov_workspaces.jl:94-112)
   int rc = KHIP_OK;
   for (double **slot : {&ws->x, &ws->r1, &ws->r2, &ws->w1, &ws->w2, &ws->y})
-    if (!rc) rc = ws->alloc(slot);
+    if (!rc) rc = alloc_vec(ctx, n, slot);
   if (rc) { khip_minres_workspace_destroy(ws); return rc; }
-  ws->st.allocation_timer = ws->alloc_s;
-  ws->alloc_s = 0.0;
+  ws->box.st.allocation_timer = take_alloc_seconds();
   *out = ws;
   return KHIP_OK;
 }
@@ -379,68 +321,40 @@ int khip_minres_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, int window,
   khip_minres_workspace *ws = new khip_minres_workspace();
   ws->ctx = ctx; ws->m = m; ws->n = n; ws->window = window;
   ws->err_vec.assign((size_t)window, 0.0);
-  memset(&ws->st, 0, sizeof(ws->st));
-  snprintf(ws->st.status, sizeof(ws->st.status), "unknown");
   ws->x = x; ws->r1 = r1; ws->r2 = r2; ws->w1 = w1; ws->w2 = w2; ws->y = y;
-  for (const double *p : all) if (p) ws->borrowed.push_back(p);
+  for (const double *p : all) ws->borrowed.add(p);
   *out = ws;
   return KHIP_OK;
 }
 
 int khip_minres_workspace_adopt_vector(khip_minres_workspace *ws, const char *name, double *ptr) {
   KHIP_REQUIRE(ws && name, "minres_workspace_adopt_vector: null argument");
-  struct { const char *k; double **slot; } tab[] = {{"dx", &ws->dx}, {"v", &ws->v}, {"npc_dir", &ws->npc_dir}};
-  double *fixed[] = {ws->x, ws->r1, ws->r2, ws->w1, ws->w2, ws->y};
-  for (auto &e : tab)
-    if (strcmp(e.k, name) == 0) {
-      if (ptr) {
-        bool clash = false;
-        for (double *p : fixed) clash = clash || p == ptr;
-        for (auto &o : tab) clash = clash || (o.slot != e.slot && *o.slot == ptr);
-        if (clash) {
-          set_error("minres_workspace_adopt_vector: the pointer for '%s' already is another vector of the workspace", name);
-          return KHIP_ERR_INVALID;
-        }
-      }
-      if (*e.slot == ptr) return KHIP_OK;
-      if (*e.slot) {
-        if (ws->is_borrowed(*e.slot)) {
-          for (size_t i = 0; i < ws->borrowed.size(); ++i)
-            if (ws->borrowed[i] == *e.slot) { ws->borrowed.erase(ws->borrowed.begin() + (long)i); break; }
-        } else {
-          khip_free(ws->ctx, *e.slot);
-        }
-      }
-      *e.slot = ptr;
-      if (ptr) ws->borrowed.push_back(ptr);
-      return KHIP_OK;
-    }
-  set_error("minres_workspace_adopt_vector: unknown vector '%s' (dx, v, npc_dir)", name);
-  return KHIP_ERR_INVALID;
+  using S = NamedSlot;
+  return adopt_named(ws->ctx, ws->borrowed, {{"x", &ws->x, S::Fixed}, {"r1", &ws->r1, S::Fixed}, {"r2", &ws->r2, S::Fixed},
+                     {"w1", &ws->w1, S::Fixed}, {"w2", &ws->w2, S::Fixed}, {"y", &ws->y, S::Fixed}, {"dx", &ws->dx, S::Optional},
+                     {"v", &ws->v, S::Optional}, {"npc_dir", &ws->npc_dir, S::Optional}},
+                     "minres_workspace_adopt_vector", "vector", name, ptr);
 }
 
 int khip_minres_workspace_destroy(khip_minres_workspace *ws) {
   if (!ws) return KHIP_OK;
-  for (double *p : {ws->dx, ws->x, ws->r1, ws->r2, ws->npc_dir, ws->w1, ws->w2, ws->y, ws->v}) ws->release(p);
-  if (ws->dev) (void)hipFree(ws->dev);
-  if (ws->pinned) (void)hipHostFree(ws->pinned);
-  if (ws->hist_dev) (void)hipFree(ws->hist_dev);
-  for (auto e : ws->snap_ev) if (e) (void)hipEventDestroy(e);
+  for (double *p : {ws->dx, ws->x, ws->r1, ws->r2, ws->npc_dir, ws->w1, ws->w2, ws->y, ws->v}) free_unless_borrowed(ws->ctx, ws->borrowed, p);
+  ws->loop.release();
   delete ws;
   return KHIP_OK;
 }
 
 int khip_minres_warm_start(khip_minres_workspace *ws, const double *x0) {
   KHIP_REQUIRE(ws && x0, "minres_warm_start: null argument");
-  if (!ws->dx) KHIP_TRY(ws->alloc(&ws->dx));
+  if (!ws->dx) KHIP_TRY(alloc_vec(ws->ctx, ws->n, &ws->dx));
   if (x0 != ws->dx) KHIP_TRY(khip_copy(ws->ctx, ws->n, ws->dx, x0));
   ws->warm_start = true;
   return KHIP_OK;
 }
 
 double *khip_minres_solution(khip_minres_workspace *ws) { return ws ? ws->x : nullptr; }
-const khip_stats *khip_minres_stats(khip_minres_workspace *ws) { return ws ? &ws->st : nullptr; }
-int khip_minres_last_path(khip_minres_workspace *ws) { return ws ? ws->path : -1; }
+const khip_stats *khip_minres_stats(khip_minres_workspace *ws) { return ws ? &ws->box.st : nullptr; }
+int khip_minres_last_path(khip_minres_workspace *ws) { return ws ? ws->box.path : -1; }
 int khip_minres_fused_product(khip_minres_workspace *ws) { return ws ? (ws->fused_product ? 1 : 0) : -1; }
 int khip_minres_histories(khip_minres_workspace *ws, const double **aresiduals, int *naresiduals, const double **acond,
                           int *nacond) {
@@ -472,41 +386,38 @@ int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const k
   const khip_options o = opts_in ? *opts_in : khip_default_options();
   const khip_minres_params prm = params_in ? *params_in : khip_minres_default_params();
   const double t0 = now_s();
-  const double timemax = (std::isnan(o.timemax) || o.timemax <= 0) ? std::numeric_limits<double>::infinity() : o.timemax;
+  const double timemax = timemax_of(o);
   const int64_t n = ws->n;
-  khip_stats *st = &ws->st;
-  const double sqeps = std::sqrt(kEps);
-  const double atol = std::isnan(o.atol) ? sqeps : o.atol, rtol = std::isnan(o.rtol) ? sqeps : o.rtol;
-  const double etol = std::isnan(prm.etol) ? sqeps : prm.etol;
-  const double conlim = std::isnan(prm.conlim) ? 1.0 / sqeps : prm.conlim;
+  khip_stats *st = &ws->box.st;
+  const double atol = tol_or_default(o.atol), rtol = tol_or_default(o.rtol), etol = tol_or_default(prm.etol);
+  const double conlim = std::isnan(prm.conlim) ? 1.0 / std::sqrt(kEps) : prm.conlim;
   const double lambda = prm.lambda;
   const int verbose = o.verbose;
-  ws->alloc_s = 0.0;
+  (void)take_alloc_seconds();
 
   if (A->csr && !A->apply) {
     int64_t am, an;
     khip_csr_shape(A->csr, &am, &an, nullptr);
-    if (am != ws->m) return ws->fail(KHIP_ERR_INVALID, "(workspace.m, workspace.n) is inconsistent with size(A)");
+    if (am != ws->m) return ws->box.fail(KHIP_ERR_INVALID, "(workspace.m, workspace.n) is inconsistent with size(A)");
   }
-  if (ws->m != ws->n) return ws->fail(KHIP_ERR_INVALID, "System must be square");
+  if (ws->m != ws->n) return ws->box.fail(KHIP_ERR_INVALID, "System must be square");
   if (verbose > 0) klogf(o.log_fd, "MINRES: system of size %lld\n", (long long)n);                       // src/minres.jl:180
   if (o.linesearch)
-    return ws->fail(KHIP_ERR_UNSUPPORTED, "minres: linesearch = true (nonpositive-curvature detection) is not supported");
+    return ws->box.fail(KHIP_ERR_UNSUPPORTED, "minres: linesearch = true (nonpositive-curvature detection) is not supported");
   const bool MisI = (M == nullptr);
-  if (!MisI && !ws->v) K(ws->alloc(&ws->v));                                                              // :192
+  if (!MisI && !ws->v) K(alloc_vec(ctx, n, &ws->v));                                                     // :192
   const bool warm_start = ws->warm_start;
   // reset!(stats)
-  ws->residuals.clear(); ws->aresiduals.clear(); ws->aconds.clear();
+  ws->box.reset(); ws->aresiduals.clear(); ws->aconds.clear();
   ws->fused_product = false;
-  st->residuals = nullptr; st->nres = 0; st->indefinite = 0; st->npcCount = 0; st->error[0] = 0;
   Bufs B{ws->x, ws->r1, ws->r2, ws->y, MisI ? ws->r2 : ws->v, ws->w1, ws->w2};
   const double ctol = conlim > 0 ? 1.0 / conlim : 0.0;
   const bool history = o.history != 0;
   auto finish_early = [&](void) {
     st->timer = now_s() - t0;
     ws->warm_start = false;
-    st->allocation_timer += ws->alloc_s;
-    ws->publish();
+    st->allocation_timer += take_alloc_seconds();
+    ws->box.publish();
   };
 
   // set-up, the same primitives on every path (:208-231)
@@ -522,13 +433,13 @@ int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const k
   if (!MisI) K(apply_op(ctx, M, B.r1, B.v));
   double beta1;
   K(khip_dot(ctx, n, B.r1, B.v, &beta1));
-  if (beta1 < 0) return ws->fail(KHIP_ERR_NUMERIC, "Preconditioner is not positive definite");
+  if (beta1 < 0) return ws->box.fail(KHIP_ERR_NUMERIC, "Preconditioner is not positive definite");
   if (beta1 == 0) {                                                                                       // :233-244
     st->niter = 1; st->solved = 1; st->inconsistent = 0;
     snprintf(st->status, sizeof(st->status), "x is a zero-residual solution");
-    if (history) { ws->residuals.push_back(beta1); ws->aresiduals.push_back(0.0); ws->aconds.push_back(0.0); }
+    if (history) { ws->box.residuals.push_back(beta1); ws->aresiduals.push_back(0.0); ws->aconds.push_back(0.0); }
     if (warm_start) K(khip_axpy(ctx, n, 1.0, ws->dx, B.x));
-    ws->path = o.fused ? 1 : 0;
+    ws->box.path = o.fused ? 1 : 0;
     finish_early();
     return KHIP_OK;
   }
@@ -543,7 +454,7 @@ int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const k
   s.window = ws->window; s.MisI = MisI ? 1 : 0;
   s.inv_beta = 1.0 / beta1;
   s.stop_seq = kSeqNever;
-  if (history) { ws->residuals.push_back(beta1); ws->aconds.push_back(0.0); ws->aresiduals.push_back(0.0); }
+  if (history) { ws->box.residuals.push_back(beta1); ws->aconds.push_back(0.0); ws->aresiduals.push_back(0.0); }
   K(khip_fill(ctx, n, B.w1, 0.0));
   K(khip_fill(ctx, n, B.w2, 0.0));
   std::fill(ws->err_vec.begin(), ws->err_vec.end(), 0.0);
@@ -561,13 +472,13 @@ int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const k
 
   const bool device_loop = o.fused >= 2 && A->csr && !A->apply && MisI && !o.callback && verbose <= 0 &&
                            ws->window <= kMinresWindowMax;
-  ws->path = device_loop ? 2 : (o.fused ? 1 : 0);
+  ws->box.path = device_loop ? 2 : (o.fused ? 1 : 0);
   // the Lanczos epilogue inside the product: fused loops on a CSR handle whose product runs the sliced kernel (both fused loops decide
   // alike, so they keep producing the same bits)
-  const bool fuse = ws->path >= 1 && A->csr && !A->apply && spmv_takes_lanczos(ctx, A->csr);
+  const bool fuse = ws->box.path >= 1 && A->csr && !A->apply && spmv_takes_lanczos(ctx, A->csr);
   ws->fused_product = fuse;
 
-  if (ws->path == 0) {
+  if (ws->box.path == 0) {
     // ---------------------------------------------------------------- the reference's primitive sequence (:283-451) ----
     double *w = nullptr;
     while (!stop) {
@@ -594,7 +505,7 @@ int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const k
       if (!MisI) K(apply_op(ctx, M, B.r2, B.v));
       double b2;
       K(khip_dot(ctx, n, B.r2, B.v, &b2));
-      if (!minres_step_b(s, b2, k)) return ws->fail(KHIP_ERR_NUMERIC, "Preconditioner is not positive definite");
+      if (!minres_step_b(s, b2, k)) return ws->box.fail(KHIP_ERR_NUMERIC, "Preconditioner is not positive definite");
       if (history) ws->aresiduals.push_back(s.ArNorm);
       K(khip_div(ctx, n, w, s.gamma));
       K(khip_axpy(ctx, n, s.phi, w, B.x));
@@ -602,32 +513,32 @@ int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const k
       double xNorm;
       K(khip_nrm2(ctx, n, B.x, &xNorm));
       stop = minres_step_c(s, xNorm, k, ws->err_vec.data());
-      if (history) { ws->residuals.push_back(s.rNorm); ws->aconds.push_back(s.Acond); }
-      if (kdisplay_row(k, verbose)) verbose_row(o, k, s, t0, false);
+      if (history) { ws->box.residuals.push_back(s.rNorm); ws->aconds.push_back(s.Acond); }
+      if (kdisplay(k, verbose)) verbose_row(o, k, s, t0, false);
       if (s.lsq_exit) break;
       tired = k >= itmax;
       if (o.callback) {
-        ws->publish();                              // the callback reads stats.residuals (as cg! / gmres! / bicgstab! publish them)
+        ws->box.publish();                          // the callback reads stats.residuals (as cg! / gmres! / bicgstab! publish them)
         user_exit = o.callback(ws, o.callback_data) != 0;
       }
       overtimed = time_limit_reached(ctx, now_s() - t0, timemax);
       stop = stop || user_exit || overtimed;
     }
-  } else if (ws->path == 1) {
+  } else if (ws->box.path == 1) {
     // ---------------------------------------------------------------- host-driven loop on the fused kernels ----------
-    K(ensure_fused_state(ws));
+    K(ws->loop.alloc());
     s.hist_r = s.hist_ar = s.hist_acond = nullptr;
     while (!stop) {
       const int64_t k = ++iter;
       K(upload(ws, s));
       int slot = take_slots(ctx, 1);
-      K(lanczos_product(ctx, A, fuse, n, ws->dev, B.v, B.r1, B.y, k >= 2, slot));
+      K(lanczos_product(ctx, A, fuse, n, ws->loop.dev, B.v, B.r1, B.y, k >= 2, slot));
       double vy;
       K(fetch_results(ctx, slot, 1, &vy));
       minres_step_a(s, vy);
       K(upload(ws, s));
       slot = take_slots(ctx, 1);
-      K(launch_p2(ctx, n, ws->dev, B.r2, B.v, B.y, B.w1, B.w2, (int)std::min<int64_t>(k, 3), MisI, slot));
+      K(launch_p2(ctx, n, ws->loop.dev, B.r2, B.v, B.y, B.w1, B.w2, (int)std::min<int64_t>(k, 3), MisI, slot));
       double *w = k == 1 ? B.w2 : B.w1;
       double *old_r1 = B.r1;                       // r1 <- r2 ; r2 <- y (:303-304) as a rotation of the roles
       B.r1 = B.r2; B.r2 = B.y; B.y = old_r1;
@@ -639,21 +550,21 @@ int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const k
         K(apply_op(ctx, M, B.r2, B.v));
         K(khip_dot(ctx, n, B.r2, B.v, &b2));
       }
-      if (!minres_step_b(s, b2, k)) return ws->fail(KHIP_ERR_NUMERIC, "Preconditioner is not positive definite");
+      if (!minres_step_b(s, b2, k)) return ws->box.fail(KHIP_ERR_NUMERIC, "Preconditioner is not positive definite");
       if (history) ws->aresiduals.push_back(s.ArNorm);
       K(upload(ws, s));
       slot = take_slots(ctx, 1);
-      K(launch_p3(ctx, n, ws->dev, w, B.x, slot));
+      K(launch_p3(ctx, n, ws->loop.dev, w, B.x, slot));
       double xx;
       K(fetch_results(ctx, slot, 1, &xx));
       if (k >= 2) std::swap(B.w1, B.w2);
       stop = minres_step_c(s, std::sqrt(xx), k, ws->err_vec.data());
-      if (history) { ws->residuals.push_back(s.rNorm); ws->aconds.push_back(s.Acond); }
-      if (kdisplay_row(k, verbose)) verbose_row(o, k, s, t0, false);
+      if (history) { ws->box.residuals.push_back(s.rNorm); ws->aconds.push_back(s.Acond); }
+      if (kdisplay(k, verbose)) verbose_row(o, k, s, t0, false);
       if (s.lsq_exit) break;
       tired = k >= itmax;
       if (o.callback) {
-        ws->publish();                              // the callback reads stats.residuals (as cg! / gmres! / bicgstab! publish them)
+        ws->box.publish();                          // the callback reads stats.residuals (as cg! / gmres! / bicgstab! publish them)
         user_exit = o.callback(ws, o.callback_data) != 0;
       }
       overtimed = time_limit_reached(ctx, now_s() - t0, timemax);
@@ -661,97 +572,36 @@ int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const k
     }
   } else if (!stop) {
     // ---------------------------------------------------------------- device-resident loop -----------------------------
-    K(ensure_fused_state(ws));
-    if (history && !ws->hist_dev) {
-      const int rc = khip_malloc(ctx, sizeof(double) * 3 * (size_t)kHistWindowMax, reinterpret_cast<void **>(&ws->hist_dev));
-      if (rc) return ws->fail_rc(rc);
-    }
-    long long window = ctx->tune.hist_window;
-    if (window < kDevChunk) window = kDevChunk;
-    if (window > kHistWindowMax) window = kHistWindowMax;
-    s.hist_cap = window;
-    s.hist_base = 0;
-    s.hist_r = history ? ws->hist_dev : nullptr;
-    s.hist_ar = history ? ws->hist_dev + kHistWindowMax : nullptr;
-    s.hist_acond = history ? ws->hist_dev + 2 * kHistWindowMax : nullptr;
     for (int i = 0; i < ws->window; ++i) s.err_vec[i] = 0.0;
-    MinresDevState *dev = ws->dev;
-    ws->pinned[2] = s;
-    KHIP_CHECK_HIP(hipMemcpyAsync(dev, &ws->pinned[2], sizeof(s), hipMemcpyHostToDevice, ctx->stream));
-    KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    long long hist_base = 0;
-    std::vector<double> win;
-    auto drain = [&](long long upto) -> int {                  // history entries of iterations (hist_base, upto]
-      const long long cnt = upto - hist_base;
-      if (!history || cnt <= 0) return KHIP_OK;
-      win.resize((size_t)cnt);
-      std::vector<double> *dst[3] = {&ws->residuals, &ws->aresiduals, &ws->aconds};
-      for (int h = 0; h < 3; ++h) {
-        KHIP_CHECK_HIP(hipMemcpy(win.data(), ws->hist_dev + (size_t)h * kHistWindowMax, sizeof(double) * (size_t)cnt,
-                                 hipMemcpyDeviceToHost));
-        dst[h]->insert(dst[h]->end(), win.begin(), win.end());
-      }
+    auto step = [&](MinresDevState *dev, long long j) {
+      const int64_t k = j + 1;
+      ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 1, EPI_MINRES_A, dev};
+      int slot = take_slots(ctx, 1);
+      int rc = lanczos_product(ctx, A, fuse, n, dev, B.v, B.r1, B.y, k >= 2, slot);          // y = A v + P1 ; v.y -> alpha, delta
+      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
+      if (rc != KHIP_OK) return rc;
+      ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 2, EPI_MINRES_B, dev};
+      slot = take_slots(ctx, 1);
+      rc = launch_p2(ctx, n, dev, B.r2, B.v, B.y, B.w1, B.w2, (int)std::min<int64_t>(k, 3), true, slot);   // P2 ; y.y -> rotation
+      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
+      if (rc != KHIP_OK) return rc;
+      double *w = k == 1 ? B.w2 : B.w1;
+      double *old_r1 = B.r1;
+      B.r1 = B.r2; B.r2 = B.y; B.y = old_r1; B.v = B.r2;
+      ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 3, EPI_MINRES_C, dev};
+      slot = take_slots(ctx, 1);
+      rc = launch_p3(ctx, n, dev, w, B.x, slot);                                         // P3 ; x.x -> tests
+      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
+      ctx->ctl = SeqCtl{};
+      if (rc != KHIP_OK) return rc;
+      if (k >= 2) std::swap(B.w1, B.w2);
       return KHIP_OK;
     };
-    const bool limited = timemax < 1e300;
-    int64_t enq = 0;
-    int rc = KHIP_OK;
-    bool stopped = false;
-    for (int chunk = 0; !stopped; ++chunk) {
-      // a finite timemax: the first chunk is ONE iteration, so that a limit already used up stops after iteration 1 as the
-      // host-driven loop does
-      const int64_t c = std::min<int64_t>((limited && chunk == 0) ? 1 : kDevChunk, itmax - enq);
-      if (history && enq + c - hist_base > window) {          // window full: empty it
-        KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        MinresDevState cur;
-        KHIP_CHECK_HIP(hipMemcpy(&cur, dev, sizeof(cur), hipMemcpyDeviceToHost));
-        if (cur.stop_seq != kSeqNever) break;
-        if ((rc = drain(cur.iter)) != KHIP_OK) break;
-        hist_base = cur.iter;
-        KHIP_CHECK_HIP(hipMemcpy(&dev->hist_base, &hist_base, sizeof(hist_base), hipMemcpyHostToDevice));
-      }
-      for (int64_t i = 0; i < c && rc == KHIP_OK; ++i) {
-        const long long j = (long long)(enq + i);
-        const int64_t k = j + 1;
-        ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 1, EPI_MINRES_A, dev};
-        int slot = take_slots(ctx, 1);
-        rc = lanczos_product(ctx, A, fuse, n, dev, B.v, B.r1, B.y, k >= 2, slot);          // y = A v + P1 ; v.y -> alpha, delta
-        if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-        if (rc != KHIP_OK) break;
-        ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 2, EPI_MINRES_B, dev};
-        slot = take_slots(ctx, 1);
-        rc = launch_p2(ctx, n, dev, B.r2, B.v, B.y, B.w1, B.w2, (int)std::min<int64_t>(k, 3), true, slot);   // P2 ; y.y -> rotation
-        if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-        if (rc != KHIP_OK) break;
-        double *w = k == 1 ? B.w2 : B.w1;
-        double *old_r1 = B.r1;
-        B.r1 = B.r2; B.r2 = B.y; B.y = old_r1; B.v = B.r2;
-        ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 3, EPI_MINRES_C, dev};
-        slot = take_slots(ctx, 1);
-        rc = launch_p3(ctx, n, dev, w, B.x, slot);                                         // P3 ; x.x -> tests
-        if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-        ctx->ctl = SeqCtl{};
-        if (rc != KHIP_OK) break;
-        if (k >= 2) std::swap(B.w1, B.w2);
-      }
-      ctx->ctl = SeqCtl{};
-      if (rc != KHIP_OK) break;
-      enq += c;
-      const int bsel = chunk & 1;
-      KHIP_CHECK_HIP(hipMemcpyAsync(&ws->pinned[bsel], dev, sizeof(MinresDevState), hipMemcpyDeviceToHost, ctx->stream));
-      KHIP_CHECK_HIP(hipEventRecord(ws->snap_ev[bsel], ctx->stream));
-      if (chunk >= 1) {                                      // look at the PREVIOUS chunk: the queue never runs dry
-        KHIP_CHECK_HIP(hipEventSynchronize(ws->snap_ev[bsel ^ 1]));
-        if (ws->pinned[bsel ^ 1].stop_seq != kSeqNever) stopped = true;
-      }
-      if (enq >= itmax) stopped = true;
-      if (!stopped && time_limit_reached(ctx, now_s() - t0, timemax)) { overtimed = true; stopped = true; }
-    }
-    ctx->ctl = SeqCtl{};
-    KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    if (rc != KHIP_OK) return ws->fail_rc(rc);
-    KHIP_CHECK_HIP(hipMemcpy(&s, dev, sizeof(MinresDevState), hipMemcpyDeviceToHost));
-    K(drain(s.iter));
+    // a finite timemax: the first chunk is ONE iteration, so that a limit already used up stops after iteration 1 as the
+    // host-driven loop does
+    const DeviceLoopArgs loop_args{itmax, t0, timemax, history, {&ws->box.residuals, &ws->aresiduals, &ws->aconds},
+                                   timemax < 1e300 ? 1 : kDevChunk};
+    K(ws->loop.run(ctx, s, loop_args, step, &s, &overtimed));
     iter = s.iter;
     tired = iter >= itmax;
   }

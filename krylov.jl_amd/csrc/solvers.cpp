@@ -13,118 +13,10 @@
 // only so far) additionally keeps the scalar recurrences and stopping tests on the device
 // (solver_device.hpp): no host round trip inside the loop, iterations are enqueued ahead.
 #include <chrono>
-#include <cmath>
-#include <limits>
 
-#include "khip_internal.hpp"
-#include "solver_device.hpp"
+#include "solver_host.hpp"
 
 using namespace khip;
-
-namespace {
-
-constexpr double kEps = std::numeric_limits<double>::epsilon();
-
-double tol_or_default(double t) { return std::isnan(t) ? std::sqrt(kEps) : t; }
-double timemax_of(const khip_options &o) {
-  return (std::isnan(o.timemax) || o.timemax <= 0) ? std::numeric_limits<double>::infinity() : o.timemax;
-}
-
-struct StatsBox {
-  khip_stats st;
-  std::vector<double> residuals;
-  int path = -1;       // which loop the last solve ran (khip_*_last_path): 2 device-resident / look-ahead, 1 host-driven fused, 0 primitive sequence
-  StatsBox() {
-    memset(&st, 0, sizeof(st));
-    snprintf(st.status, sizeof(st.status), "unknown");
-  }
-  void reset() {   // reset!(stats), src/krylov_stats.jl:38-44
-    residuals.clear();
-    st.residuals = nullptr;
-    st.nres = 0;
-    st.indefinite = 0;
-    st.npcCount = 0;
-    st.error[0] = 0;
-  }
-  void push(double v) { residuals.push_back(v); }
-  void publish() {
-    st.residuals = residuals.empty() ? nullptr : residuals.data();
-    st.nres = (int)residuals.size();
-  }
-  int fail(int code, const char *msg) {
-    snprintf(st.error, sizeof(st.error), "%s", msg);
-    set_error("%s", msg);
-    publish();
-    return code;
-  }
-  int fail_rc(int rc) {   // a primitive failed: message already in khip_last_error()
-    snprintf(st.error, sizeof(st.error), "%s", khip_last_error());
-    publish();
-    return rc;
-  }
-};
-
-int64_t padded(int64_t n) { return (n + 31) & ~(int64_t)31; }   // 256-byte multiples keep every slice 16-B aligned
-
-// stats.allocation_timer (src/krylov_utils.jl:281-288, allocate_if): every vector allocation of a workspace -- at its
-// creation and the lazy ones inside later solves -- adds its wall time to this accumulator; the creation / solve entry
-// points move it into the workspace's stats (take_alloc_seconds).
-static thread_local double g_alloc_seconds = 0.0;
-int alloc_vec(khip_ctx *ctx, int64_t n, double **out) {
-  const double t = now_s();
-  const int rc = khip_malloc(ctx, sizeof(double) * (size_t)padded(n > 0 ? n : 1), reinterpret_cast<void **>(out));
-  g_alloc_seconds += now_s() - t;
-  return rc;
-}
-double take_alloc_seconds() { const double v = g_alloc_seconds; g_alloc_seconds = 0.0; return v; }
-
-// Caller-owned work vectors (khip_*_workspace_adopt, khip_*_workspace_adopt_vector): the workspace of the reference owns
-// its vectors on the Julia side (src/krylov_workspaces.jl:236-291), so a binding hands their device pointers over and the
-// library must neither free nor replace them.  One list per workspace; everything not in it was allocated here.
-struct Borrowed {
-  std::vector<const double *> v;
-  bool has(const double *p) const {
-    for (const double *q : v) if (q == p) return true;
-    return false;
-  }
-  void add(const double *p) { if (p && !has(p)) v.push_back(p); }
-  void drop(const double *p) {
-    for (size_t i = 0; i < v.size(); ++i) if (v[i] == p) { v.erase(v.begin() + (long)i); return; }
-  }
-};
-void free_unless_borrowed(khip_ctx *ctx, const Borrowed &b, double *p) {
-  if (p && !b.has(p)) khip_free(ctx, p);
-}
-// slot <- ptr as a caller-owned vector (ptr == nullptr empties the slot); what the library had allocated there is freed
-// (`Borrowed` is a set of pointers, so a pointer may sit in ONE slot only -- the callers below refuse a pointer that
-// already is another vector of the workspace; handing a slot the pointer it already holds changes nothing, in particular not
-// who owns it.)
-void adopt_into(khip_ctx *ctx, Borrowed &b, double **slot, double *ptr) {
-  if (*slot == ptr) return;
-  if (*slot) { if (b.has(*slot)) b.drop(*slot); else khip_free(ctx, *slot); }
-  *slot = ptr;
-  b.add(ptr);
-}
-// ptr (non-null) already is a vector of the workspace other than `self`: the name of that slot, else nullptr
-template <class Tab>
-const char *held_elsewhere(const Tab &tab, const double *const *self, const double *ptr, const std::vector<double *> *basis = nullptr) {
-  if (!ptr) return nullptr;
-  for (const auto &e : tab) if (e.slot != self && *e.slot == ptr) return e.k;
-  if (basis) for (const double *v : *basis) if (v == ptr) return "V";
-  return nullptr;
-}
-
-// ---- options.verbose: the reference's per-iteration log (kdisplay, src/krylov_utils.jl:301) on stdout.  Column headers are
-// padded by hand: the labels are UTF-8 and printf pads bytes, Julia pads characters.
-inline bool kdisplay(int64_t iter, int verbose) { return verbose > 0 && iter % verbose == 0; }
-
-#define K(expr)                                   \
-  do {                                            \
-    int rc_k = (expr);                            \
-    if (rc_k != KHIP_OK) return ws->box.fail_rc(rc_k); \
-  } while (0)
-
-}  // namespace
 
 int khip::apply_op(khip_ctx *ctx, const khip_operator *op, const double *x, double *y) {
   if (op->apply) {
@@ -144,101 +36,44 @@ struct khip_cg_workspace {
   bool warm_start = false;
   Borrowed borrowed;                   // vectors of a caller's CgWorkspace (khip_cg_workspace_adopt)
   StatsBox box;
-  // device-resident loop state (fused = 2), allocated on first use
-  CgDevState *dev_state = nullptr;
-  CgDevState *snap = nullptr;          // pinned host snapshots [2]
-  CgcgDevState *cgcg_state = nullptr, *cgcg_snap = nullptr;   // single-reduction and pipelined variants
   double *pz = nullptr, *pq = nullptr;                        // pipelined variant: z = A s, q = A w (allocated on first use)
-  double *hist_dev = nullptr;
-  hipEvent_t snap_ev[2] = {nullptr, nullptr};
+  DeviceLoop<CgDevState> loop;                                // device-resident loops (fused = 2): cg! ...
+  DeviceLoop<CgcgDevState> cgcg_loop;                         // ... and the single-reduction and pipelined variants
 };
 
 namespace {
 
-constexpr int kDevChunk = 4;             // iterations enqueued between two snapshots of the device state
-
 // The loop of src/cg.jl:195-268 with scalars and stopping tests on the device.  Preconditions (checked by
 // the caller): CSR operator, M = I, radius = 0, no linesearch, no callback.  On return the vectors are in
 // the state the reference's loop leaves them in and `out` holds the final scalar state.
-int cg_device_loop(khip_cg_workspace *ws, const khip_csr *A, double gamma, double eps_tol, int64_t itmax, bool history,
-                   double t0, double timemax, CgDevState *out, bool *overtimed) {
+int cg_device_loop(khip_cg_workspace *ws, const khip_csr *A, double gamma, double eps_tol, const DeviceLoopArgs &a,
+                   CgDevState *out, bool *overtimed) {
   khip_ctx *ctx = ws->ctx;
   const int64_t n = ws->n;
-  // every resource is guarded on its own: hist_dev and the events are shared with the single-reduction loop below
-  if (!ws->dev_state) KHIP_CHECK_HIP(hipMalloc(&ws->dev_state, sizeof(CgDevState)));
-  if (!ws->snap) KHIP_CHECK_HIP(hipHostMalloc(reinterpret_cast<void **>(&ws->snap), 2 * sizeof(CgDevState), hipHostMallocDefault));
-  if (!ws->hist_dev) KHIP_CHECK_HIP(hipMalloc(&ws->hist_dev, sizeof(double) * (size_t)kHistWindowMax));
-  for (auto &e : ws->snap_ev) if (!e) KHIP_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  long long kHistWindow = ctx->tune.hist_window;
-  if (kHistWindow < kDevChunk) kHistWindow = kDevChunk;
-  if (kHistWindow > kHistWindowMax) kHistWindow = kHistWindowMax;
-  CgDevState *dev = ws->dev_state;
-  CgDevState h;
-  memset(&h, 0, sizeof(h));
+  CgDevState h{};
   h.gamma = gamma; h.pNorm2 = gamma; h.eps_tol = eps_tol; h.keps = kEps; h.rNorm = std::sqrt(gamma);
-  h.stop_seq = kSeqNever;
-  h.hist = history ? ws->hist_dev : nullptr;
-  h.hist_cap = kHistWindow;
-  KHIP_CHECK_HIP(hipMemcpyAsync(dev, &h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-  KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));          // h is a stack object
-
-  int64_t enq = 0;            // iterations enqueued
-  long long hist_base = 0;
-  std::vector<double> win;
-  auto drain_history = [&](long long upto_iter) -> int {      // entries for iterations (hist_base, upto_iter]
-    const long long cnt = upto_iter - hist_base;
-    if (!history || cnt <= 0) return KHIP_OK;
-    win.resize((size_t)cnt);
-    KHIP_CHECK_HIP(hipMemcpy(win.data(), ws->hist_dev, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
-    for (double v : win) ws->box.push(v);
-    return KHIP_OK;
-  };
-  int rc = KHIP_OK;
-  bool stopped = false;
-  for (int chunk = 0; !stopped; ++chunk) {
-    const int64_t c = std::min<int64_t>(kDevChunk, itmax - enq);
-    if (history && enq + c - hist_base > kHistWindow) {        // window full: empty it (rare: every 16384 iterations)
-      KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-      CgDevState cur;
-      KHIP_CHECK_HIP(hipMemcpy(&cur, dev, sizeof(cur), hipMemcpyDeviceToHost));
-      if (cur.stop_seq != kSeqNever) break;
-      if ((rc = drain_history(cur.iter)) != KHIP_OK) break;
-      hist_base = cur.iter;
-      KHIP_CHECK_HIP(hipMemcpy(&dev->hist_base, &hist_base, sizeof(hist_base), hipMemcpyHostToDevice));
-    }
-    for (int64_t i = 0; i < c && rc == KHIP_OK; ++i) {
-      const long long j = (long long)(enq + i);
-      ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j, EPI_CG_STEP1, dev};
-      const int s1 = take_slots(ctx, 1);
-      rc = spmv_any(ctx, A, ws->p, ws->Ap, s1);                                     // :196-197, epilogue :198-213
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, s1, 1);
-      if (rc != KHIP_OK) break;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j + 1, EPI_CG_STEP2, dev};
-      const int s2 = take_slots(ctx, 1);
-      rc = launch_axpy_dev_dot(ctx, n, &dev->alpha, ws->Ap, ws->r, ws->r, s2);      // :240, :242, epilogue :243-262
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, s2, 1);
-      ctx->ctl = SeqCtl{};
-      if (rc != KHIP_OK) break;
-      rc = launch_cg_update_dev(ctx, n, dev, 3 * j + 2, ws->r, ws->p, ws->x);       // :239 and :259
-    }
+  auto step = [&](CgDevState *dev, long long j) {
+    ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j, EPI_CG_STEP1, dev};
+    const int s1 = take_slots(ctx, 1);
+    int rc = spmv_any(ctx, A, ws->p, ws->Ap, s1);                                     // :196-197, epilogue :198-213
+    if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, s1, 1);
+    if (rc != KHIP_OK) return rc;
+    ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j + 1, EPI_CG_STEP2, dev};
+    const int s2 = take_slots(ctx, 1);
+    rc = launch_axpy_dev_dot(ctx, n, &dev->alpha, ws->Ap, ws->r, ws->r, s2);          // :240, :242, epilogue :243-262
+    if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, s2, 1);
     ctx->ctl = SeqCtl{};
-    if (rc != KHIP_OK) break;
-    enq += c;
-    const int b = chunk & 1;
-    KHIP_CHECK_HIP(hipMemcpyAsync(&ws->snap[b], dev, sizeof(CgDevState), hipMemcpyDeviceToHost, ctx->stream));
-    KHIP_CHECK_HIP(hipEventRecord(ws->snap_ev[b], ctx->stream));
-    if (chunk >= 1) {                                        // look at the PREVIOUS chunk: the queue never runs dry
-      KHIP_CHECK_HIP(hipEventSynchronize(ws->snap_ev[b ^ 1]));
-      if (ws->snap[b ^ 1].stop_seq != kSeqNever) stopped = true;
-    }
-    if (enq >= itmax) stopped = true;
-    if (!stopped && time_limit_reached(ctx, now_s() - t0, timemax)) { *overtimed = true; stopped = true; }
-  }
-  ctx->ctl = SeqCtl{};
-  KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  if (rc != KHIP_OK) return rc;
-  KHIP_CHECK_HIP(hipMemcpy(out, dev, sizeof(CgDevState), hipMemcpyDeviceToHost));
-  return drain_history(out->iter);
+    if (rc != KHIP_OK) return rc;
+    return launch_cg_update_dev(ctx, n, dev, 3 * j + 2, ws->r, ws->p, ws->x);         // :239 and :259
+  };
+  return ws->loop.run(ctx, h, a, step, out, overtimed);
+}
+
+// the initial state of the single-reduction and pipelined variants
+CgcgDevState cgcg_start(double gamma0, double delta0, double eps_tol) {
+  CgcgDevState h{};
+  h.gamma = gamma0; h.alpha = gamma0 / delta0; h.beta = 0.0; h.rNorm = std::sqrt(gamma0); h.eps_tol = eps_tol;
+  return h;
 }
 
 // Single-reduction CG (options.variant = 1; Chronopoulos & Gear 1989): two passes per iteration --
@@ -246,81 +81,22 @@ int cg_device_loop(khip_cg_workspace *ws, const khip_csr *A, double gamma, doubl
 //   product: w = A r fused with BOTH dots (r.w, r.r) in one reduction; its epilogue forms beta, alpha, the tests
 // -- i.e. ONE all-reduce per iteration on N GPUs instead of two, and 2 + 1 kernels instead of 3 + 2.  Not the
 // reference's recurrence: same Krylov space, different rounding (tests/test_gpu_solvers.py holds its parity budget).
-int cg_single_reduction_loop(khip_cg_workspace *ws, const khip_csr *A, double gamma0, double delta0, double eps_tol,
-                             int64_t itmax, bool history, double t0, double timemax, CgcgDevState *out, bool *overtimed) {
+int cg_single_reduction_loop(khip_cg_workspace *ws, const khip_csr *A, double gamma0, double delta0, double eps_tol, const DeviceLoopArgs &a,
+                             CgcgDevState *out, bool *overtimed) {
   khip_ctx *ctx = ws->ctx;
   const int64_t n = ws->n;
-  if (!ws->cgcg_state) {
-    KHIP_CHECK_HIP(hipMalloc(&ws->cgcg_state, sizeof(CgcgDevState)));
-    KHIP_CHECK_HIP(hipHostMalloc(reinterpret_cast<void **>(&ws->cgcg_snap), 2 * sizeof(CgcgDevState), hipHostMallocDefault));
-  }
-  if (!ws->hist_dev) KHIP_CHECK_HIP(hipMalloc(&ws->hist_dev, sizeof(double) * (size_t)kHistWindowMax));
-  for (auto &e : ws->snap_ev) if (!e) KHIP_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  long long window = ctx->tune.hist_window;
-  if (window < kDevChunk) window = kDevChunk;
-  if (window > kHistWindowMax) window = kHistWindowMax;
-  CgcgDevState *dev = ws->cgcg_state;
-  CgcgDevState h;
-  memset(&h, 0, sizeof(h));
-  h.gamma = gamma0; h.alpha = gamma0 / delta0; h.beta = 0.0; h.rNorm = std::sqrt(gamma0); h.eps_tol = eps_tol;
-  h.stop_seq = kSeqNever;
-  h.hist = history ? ws->hist_dev : nullptr;
-  h.hist_cap = window;
-  KHIP_CHECK_HIP(hipMemcpyAsync(dev, &h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-  KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
   double *x = ws->x, *r = ws->r, *p = ws->p, *s = ws->Ap, *w = ws->z;
-  int64_t enq = 0;
-  long long hist_base = 0;
-  std::vector<double> win;
-  auto drain_history = [&](long long upto_iter) -> int {
-    const long long cnt = upto_iter - hist_base;
-    if (!history || cnt <= 0) return KHIP_OK;
-    win.resize((size_t)cnt);
-    KHIP_CHECK_HIP(hipMemcpy(win.data(), ws->hist_dev, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
-    for (double val : win) ws->box.push(val);
-    return KHIP_OK;
-  };
-  int rc = KHIP_OK;
-  bool stopped = false;
-  for (int chunk = 0; !stopped; ++chunk) {
-    const int64_t cnt = std::min<int64_t>(kDevChunk, itmax - enq);
-    if (history && enq + cnt - hist_base > window) {
-      KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-      CgcgDevState cur;
-      KHIP_CHECK_HIP(hipMemcpy(&cur, dev, sizeof(cur), hipMemcpyDeviceToHost));
-      if (cur.stop_seq != kSeqNever) break;
-      if ((rc = drain_history(cur.iter)) != KHIP_OK) break;
-      hist_base = cur.iter;
-      KHIP_CHECK_HIP(hipMemcpy(&dev->hist_base, &hist_base, sizeof(hist_base), hipMemcpyHostToDevice));
-    }
-    for (int64_t i = 0; i < cnt && rc == KHIP_OK; ++i) {
-      const long long j = (long long)(enq + i);
-      rc = launch_cgcg_update(ctx, n, dev, 2 * j, w, r, p, s, x);
-      if (rc != KHIP_OK) break;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 2 * j + 1, EPI_CGCG, dev};
-      const int slot = take_slots(ctx, 2);
-      rc = spmv_any(ctx, A, r, w, slot, nullptr, 2);                              // w = A r ; (r.w, r.r)
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 2);
-      ctx->ctl = SeqCtl{};
-    }
+  auto step = [&](CgcgDevState *dev, long long j) {
+    int rc = launch_cgcg_update(ctx, n, dev, 2 * j, w, r, p, s, x);
+    if (rc != KHIP_OK) return rc;
+    ctx->ctl = SeqCtl{&dev->stop_seq, 2 * j + 1, EPI_CGCG, dev};
+    const int slot = take_slots(ctx, 2);
+    rc = spmv_any(ctx, A, r, w, slot, nullptr, 2);                                    // w = A r ; (r.w, r.r)
+    if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 2);
     ctx->ctl = SeqCtl{};
-    if (rc != KHIP_OK) break;
-    enq += cnt;
-    const int b = chunk & 1;
-    KHIP_CHECK_HIP(hipMemcpyAsync(&ws->cgcg_snap[b], dev, sizeof(CgcgDevState), hipMemcpyDeviceToHost, ctx->stream));
-    KHIP_CHECK_HIP(hipEventRecord(ws->snap_ev[b], ctx->stream));
-    if (chunk >= 1) {
-      KHIP_CHECK_HIP(hipEventSynchronize(ws->snap_ev[b ^ 1]));
-      if (ws->cgcg_snap[b ^ 1].stop_seq != kSeqNever) stopped = true;
-    }
-    if (enq >= itmax) stopped = true;
-    if (!stopped && time_limit_reached(ctx, now_s() - t0, timemax)) { *overtimed = true; stopped = true; }
-  }
-  ctx->ctl = SeqCtl{};
-  KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  if (rc != KHIP_OK) return rc;
-  KHIP_CHECK_HIP(hipMemcpy(out, dev, sizeof(CgcgDevState), hipMemcpyDeviceToHost));
-  return drain_history(out->iter);
+    return rc;
+  };
+  return ws->cgcg_loop.run(ctx, cgcg_start(gamma0, delta0, eps_tol), a, step, out, overtimed);
 }
 
 // Pipelined CG (Ghysels & Vanroose 2014), opt-in as options.variant = 2: per iteration ONE reduction (r.w, r.r) and one
@@ -329,90 +105,33 @@ int cg_single_reduction_loop(khip_cg_workspace *ws, const khip_csr *A, double ga
 // separate halo communicator; otherwise in program order).  Scalars: the same epilogue as the single-reduction variant
 // (beta = gamma' / gamma, alpha = gamma' / (delta - beta gamma' / alpha)).  Not the reference's recurrence: own parity budget.
 // On entry r = b - A x0, w = A r, p = s = z = 0-initialised by the first update (beta_0 = 0), state = (gamma0, alpha0, 0).
-int cg_pipelined_loop(khip_cg_workspace *ws, const khip_csr *A, double gamma0, double delta0, double eps_tol, int64_t itmax,
-                      bool history, double t0, double timemax, CgcgDevState *out, bool *overtimed) {
+int cg_pipelined_loop(khip_cg_workspace *ws, const khip_csr *A, double gamma0, double delta0, double eps_tol, const DeviceLoopArgs &a,
+                      CgcgDevState *out, bool *overtimed) {
   khip_ctx *ctx = ws->ctx;
   const int64_t n = ws->n;
-  if (!ws->cgcg_state) {
-    KHIP_CHECK_HIP(hipMalloc(&ws->cgcg_state, sizeof(CgcgDevState)));
-    KHIP_CHECK_HIP(hipHostMalloc(reinterpret_cast<void **>(&ws->cgcg_snap), 2 * sizeof(CgcgDevState), hipHostMallocDefault));
-  }
-  if (!ws->hist_dev) KHIP_CHECK_HIP(hipMalloc(&ws->hist_dev, sizeof(double) * (size_t)kHistWindowMax));
-  for (auto &e : ws->snap_ev) if (!e) KHIP_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  long long window = ctx->tune.hist_window;
-  if (window < kDevChunk) window = kDevChunk;
-  if (window > kHistWindowMax) window = kHistWindowMax;
-  CgcgDevState *dev = ws->cgcg_state;
-  CgcgDevState h;
-  memset(&h, 0, sizeof(h));
-  h.gamma = gamma0; h.alpha = gamma0 / delta0; h.beta = 0.0; h.rNorm = std::sqrt(gamma0); h.eps_tol = eps_tol;
-  h.stop_seq = kSeqNever;
-  h.hist = history ? ws->hist_dev : nullptr;
-  h.hist_cap = window;
-  KHIP_CHECK_HIP(hipMemcpyAsync(dev, &h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-  KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
   double *x = ws->x, *r = ws->r, *p = ws->p, *s = ws->Ap, *w = ws->z, *z = ws->pz, *q = ws->pq;
-  int64_t enq = 0;
-  long long hist_base = 0;
-  std::vector<double> win;
-  auto drain_history = [&](long long upto_iter) -> int {
-    const long long cnt = upto_iter - hist_base;
-    if (!history || cnt <= 0) return KHIP_OK;
-    win.resize((size_t)cnt);
-    KHIP_CHECK_HIP(hipMemcpy(win.data(), ws->hist_dev, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
-    for (double val : win) ws->box.push(val);
-    return KHIP_OK;
-  };
-  int rc = KHIP_OK;
-  bool stopped = false;
-  for (int chunk = 0; !stopped; ++chunk) {
-    const int64_t cnt = std::min<int64_t>(kDevChunk, itmax - enq);
-    if (history && enq + cnt - hist_base > window) {
-      KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-      CgcgDevState cur;
-      KHIP_CHECK_HIP(hipMemcpy(&cur, dev, sizeof(cur), hipMemcpyDeviceToHost));
-      if (cur.stop_seq != kSeqNever) break;
-      if ((rc = drain_history(cur.iter)) != KHIP_OK) break;
-      hist_base = cur.iter;
-      KHIP_CHECK_HIP(hipMemcpy(&dev->hist_base, &hist_base, sizeof(hist_base), hipMemcpyHostToDevice));
-    }
-    for (int64_t i = 0; i < cnt && rc == KHIP_OK; ++i) {
-      const long long j = (long long)(enq + i);
-      // (a) q = A w: needs nothing of the reduction still in flight on the communication stream
-      ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j, EPI_NONE, nullptr};
-      rc = spmv_any(ctx, A, w, q, -1);
-      if (rc != KHIP_OK) break;
-      // (b) the recurrences with the alpha, beta the PREVIOUS reduction's epilogue left in the state: wait for it now
-      if (ctx->comm) rc = comm_allreduce_dd_device_end(ctx);
-      if (rc == KHIP_OK) rc = launch_pcg_update(ctx, n, dev, 3 * j + 1, q, z, s, p, x, r, w);
-      if (rc != KHIP_OK) break;
-      // (c) (r.w, r.r) of the new iterate and the scalars of the next iteration; on several ranks its all-gather, the
-      //     cross-rank combine and the scalar epilogue run on the communication stream while the NEXT product (a) runs here
-      ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j + 2, EPI_CGCG, dev};
-      const int slot = take_slots(ctx, 2);
-      rc = launch_dot2(ctx, n, r, w, slot);
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device_begin(ctx, slot, 2);
-      ctx->ctl = SeqCtl{};
-    }
-    if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device_end(ctx);      // the snapshot below reads the state the epilogue writes
+  auto step = [&](CgcgDevState *dev, long long j) {
+    // (a) q = A w: needs nothing of the reduction still in flight on the communication stream
+    ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j, EPI_NONE, nullptr};
+    int rc = spmv_any(ctx, A, w, q, -1);
+    if (rc != KHIP_OK) return rc;
+    // (b) the recurrences with the alpha, beta the PREVIOUS reduction's epilogue left in the state: wait for it now
+    if (ctx->comm) rc = comm_allreduce_dd_device_end(ctx);
+    if (rc == KHIP_OK) rc = launch_pcg_update(ctx, n, dev, 3 * j + 1, q, z, s, p, x, r, w);
+    if (rc != KHIP_OK) return rc;
+    // (c) (r.w, r.r) of the new iterate and the scalars of the next iteration; on several ranks its all-gather, the
+    //     cross-rank combine and the scalar epilogue run on the communication stream while the NEXT product (a) runs here
+    ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j + 2, EPI_CGCG, dev};
+    const int slot = take_slots(ctx, 2);
+    rc = launch_dot2(ctx, n, r, w, slot);
+    if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device_begin(ctx, slot, 2);
     ctx->ctl = SeqCtl{};
-    if (rc != KHIP_OK) break;
-    enq += cnt;
-    const int b = chunk & 1;
-    KHIP_CHECK_HIP(hipMemcpyAsync(&ws->cgcg_snap[b], dev, sizeof(CgcgDevState), hipMemcpyDeviceToHost, ctx->stream));
-    KHIP_CHECK_HIP(hipEventRecord(ws->snap_ev[b], ctx->stream));
-    if (chunk >= 1) {
-      KHIP_CHECK_HIP(hipEventSynchronize(ws->snap_ev[b ^ 1]));
-      if (ws->cgcg_snap[b ^ 1].stop_seq != kSeqNever) stopped = true;
-    }
-    if (enq >= itmax) stopped = true;
-    if (!stopped && time_limit_reached(ctx, now_s() - t0, timemax)) { *overtimed = true; stopped = true; }
-  }
-  ctx->ctl = SeqCtl{};
-  KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  if (rc != KHIP_OK) return rc;
-  KHIP_CHECK_HIP(hipMemcpy(out, dev, sizeof(CgcgDevState), hipMemcpyDeviceToHost));
-  return drain_history(out->iter);
+    return rc;
+  };
+  auto before_snapshot = [&] {     // the snapshot reads the state the epilogue writes
+    return ctx->comm ? comm_allreduce_dd_device_end(ctx) : KHIP_OK;
+  };
+  return ws->cgcg_loop.run(ctx, cgcg_start(gamma0, delta0, eps_tol), a, step, before_snapshot, out, overtimed);
 }
 
 }  // namespace
@@ -464,32 +183,17 @@ int khip_cg_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *x, doub
 
 int khip_cg_workspace_adopt_vector(khip_cg_workspace *ws, const char *name, double *ptr) {
   KHIP_REQUIRE(ws && name, "cg_workspace_adopt_vector: null argument");
-  struct { const char *k; double **slot; bool required; } tab[] = {
-      {"x", &ws->x, true}, {"r", &ws->r, true}, {"p", &ws->p, true}, {"Ap", &ws->Ap, true},
-      {"z", &ws->z, false}, {"dx", &ws->dx, false}, {"npc_dir", &ws->npc_dir, false}};
-  for (auto &e : tab)
-    if (strcmp(e.k, name) == 0) {
-      KHIP_REQUIRE(ptr || !e.required, "cg_workspace_adopt_vector: x, r, p, Ap cannot be emptied");
-      if (const char *other = held_elsewhere(tab, e.slot, ptr, nullptr)) {
-        set_error("cg_workspace_adopt_vector: the pointer for '%s' already is the workspace's '%s' (every vector needs its own storage)", name, other);
-        return KHIP_ERR_INVALID;
-      }
-      adopt_into(ws->ctx, ws->borrowed, e.slot, ptr);
-      return KHIP_OK;
-    }
-  set_error("cg_workspace_adopt_vector: unknown vector '%s' (x, r, p, Ap, z, dx, npc_dir)", name);
-  return KHIP_ERR_INVALID;
+  using S = NamedSlot;
+  return adopt_named(ws->ctx, ws->borrowed, {{"x", &ws->x, S::Required}, {"r", &ws->r, S::Required}, {"p", &ws->p, S::Required},
+                     {"Ap", &ws->Ap, S::Required}, {"z", &ws->z, S::Optional}, {"dx", &ws->dx, S::Optional},
+                     {"npc_dir", &ws->npc_dir, S::Optional}}, "cg_workspace_adopt_vector", "vector", name, ptr);
 }
 
 int khip_cg_workspace_destroy(khip_cg_workspace *ws) {
   if (!ws) return KHIP_OK;
   for (double *v : {ws->dx, ws->x, ws->r, ws->npc_dir, ws->p, ws->Ap, ws->z, ws->pz, ws->pq}) free_unless_borrowed(ws->ctx, ws->borrowed, v);
-  if (ws->dev_state) (void)hipFree(ws->dev_state);
-  if (ws->snap) (void)hipHostFree(ws->snap);
-  if (ws->cgcg_state) (void)hipFree(ws->cgcg_state);
-  if (ws->cgcg_snap) (void)hipHostFree(ws->cgcg_snap);
-  if (ws->hist_dev) (void)hipFree(ws->hist_dev);
-  for (auto e : ws->snap_ev) if (e) (void)hipEventDestroy(e);
+  ws->loop.release();
+  ws->cgcg_loop.release();
   delete ws;
   return KHIP_OK;
 }
@@ -688,6 +392,7 @@ int khip_cg_solve(khip_cg_workspace *ws, const khip_operator *A, const khip_oper
   bool inconsistent = false, on_boundary = false, zero_curvature = false, user_requested_exit = false,
        overtimed = false;
   const char *status = "unknown";
+  const DeviceLoopArgs loop_args{itmax, t0, timemax, o.history != 0, {&ws->box.residuals}};
 
   if (o.variant == 1) {                                                           // single-reduction CG, opt-in
     if (A->apply || !A->csr || !MisI || radius != 0 || linesearch || o.callback)
@@ -703,7 +408,7 @@ int khip_cg_solve(khip_cg_workspace *ws, const khip_operator *A, const khip_oper
         return ws->box.fail(KHIP_ERR_NUMERIC,
                             "The linear operator `A` or the preconditioner `M` is not symmetric positive definite.");
       CgcgDevState fin;
-      K(cg_single_reduction_loop(ws, A->csr, gamma, two[0], eps_tol, itmax, o.history != 0, t0, timemax, &fin, &overtimed));
+      K(cg_single_reduction_loop(ws, A->csr, gamma, two[0], eps_tol, loop_args, &fin, &overtimed));
       iter = fin.iter;
       rNorm = fin.rNorm;
       solved = fin.solved != 0;
@@ -731,7 +436,7 @@ int khip_cg_solve(khip_cg_workspace *ws, const khip_operator *A, const khip_oper
         return ws->box.fail(KHIP_ERR_NUMERIC,
                             "The linear operator `A` or the preconditioner `M` is not symmetric positive definite.");
       CgcgDevState fin;
-      K(cg_pipelined_loop(ws, A->csr, gamma, two[0], eps_tol, itmax, o.history != 0, t0, timemax, &fin, &overtimed));
+      K(cg_pipelined_loop(ws, A->csr, gamma, two[0], eps_tol, loop_args, &fin, &overtimed));
       iter = fin.iter;
       rNorm = fin.rNorm;
       solved = fin.solved != 0;
@@ -744,7 +449,7 @@ int khip_cg_solve(khip_cg_workspace *ws, const khip_operator *A, const khip_oper
   ws->box.path = device_loop ? 2 : (fused ? 1 : 0);
   if (device_loop && !(solved || tired)) {
     CgDevState fin;
-    K(cg_device_loop(ws, A->csr, gamma, eps_tol, itmax, o.history != 0, t0, timemax, &fin, &overtimed));
+    K(cg_device_loop(ws, A->csr, gamma, eps_tol, loop_args, &fin, &overtimed));
     if (fin.not_spd)
       return ws->box.fail(KHIP_ERR_NUMERIC,
                           "The linear operator `A` or the preconditioner `M` is not symmetric positive definite.");
@@ -989,20 +694,10 @@ int khip_gmres_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, int memory, 
 
 int khip_gmres_workspace_adopt_vector(khip_gmres_workspace *ws, const char *name, double *ptr) {
   KHIP_REQUIRE(ws && name, "gmres_workspace_adopt_vector: null argument");
-  struct { const char *k; double **slot; bool required; } tab[] = {
-      {"x", &ws->x, true}, {"w", &ws->w, true}, {"p", &ws->p, false}, {"q", &ws->q, false}, {"dx", &ws->dx, false}};
-  for (auto &e : tab)
-    if (strcmp(e.k, name) == 0) {
-      KHIP_REQUIRE(ptr || !e.required, "gmres_workspace_adopt_vector: x and w cannot be emptied");
-      if (const char *other = held_elsewhere(tab, e.slot, ptr, &ws->V)) {
-        set_error("gmres_workspace_adopt_vector: the pointer for '%s' already is the workspace's '%s' (every vector needs its own storage)", name, other);
-        return KHIP_ERR_INVALID;
-      }
-      adopt_into(ws->ctx, ws->borrowed, e.slot, ptr);
-      return KHIP_OK;
-    }
-  set_error("gmres_workspace_adopt_vector: unknown vector '%s' (x, w, p, q, dx)", name);
-  return KHIP_ERR_INVALID;
+  using S = NamedSlot;
+  return adopt_named(ws->ctx, ws->borrowed, {{"x", &ws->x, S::Required}, {"w", &ws->w, S::Required}, {"p", &ws->p, S::Optional},
+                     {"q", &ws->q, S::Optional}, {"dx", &ws->dx, S::Optional}}, "gmres_workspace_adopt_vector", "vector", name,
+                     ptr, &ws->V);
 }
 
 // The basis of an adopted workspace as the caller holds it NOW (k >= the workspace's memory: after a solve with
@@ -1576,11 +1271,7 @@ struct khip_bicgstab_workspace {
   bool warm_start = false;
   Borrowed borrowed;                   // vectors of a caller's BicgstabWorkspace (khip_bicgstab_workspace_adopt)
   StatsBox box;
-  // device-resident loop state (fused = 2), allocated on first use
-  BicgDevState *dev_state = nullptr;
-  BicgDevState *snap = nullptr;        // pinned host snapshots [2]
-  double *hist_dev = nullptr;
-  hipEvent_t snap_ev[2] = {nullptr, nullptr};
+  DeviceLoop<BicgDevState> loop;       // device-resident loop (fused = 2)
 };
 
 namespace {
@@ -1588,94 +1279,35 @@ namespace {
 // The loop of src/bicgstab.jl:213-253 (M = N = I, CSR operator, no callback) with rho, alpha, omega, beta and the
 // stopping tests on the device: five passes per iteration, each carrying its sequence number; see cg_device_loop.
 int bicgstab_device_loop(khip_bicgstab_workspace *ws, const khip_csr *A, const double *c, double rho0, double rNorm0,
-                         double eps_tol, int64_t itmax, bool history, double t0, double timemax, BicgDevState *out,
-                         bool *overtimed) {
+                         double eps_tol, const DeviceLoopArgs &a, BicgDevState *out, bool *overtimed) {
   khip_ctx *ctx = ws->ctx;
   const int64_t n = ws->n;
-  if (!ws->dev_state) {
-    KHIP_CHECK_HIP(hipMalloc(&ws->dev_state, sizeof(BicgDevState)));
-    KHIP_CHECK_HIP(hipHostMalloc(reinterpret_cast<void **>(&ws->snap), 2 * sizeof(BicgDevState), hipHostMallocDefault));
-    KHIP_CHECK_HIP(hipMalloc(&ws->hist_dev, sizeof(double) * (size_t)kHistWindowMax));
-    for (auto &e : ws->snap_ev) KHIP_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  long long window = ctx->tune.hist_window;
-  if (window < kDevChunk) window = kDevChunk;
-  if (window > kHistWindowMax) window = kHistWindowMax;
-  BicgDevState *dev = ws->dev_state;
-  BicgDevState h;
-  memset(&h, 0, sizeof(h));
+  BicgDevState h{};
   h.rho = rho0; h.alpha = 1.0; h.omega = 1.0; h.rNorm = rNorm0; h.eps_tol = eps_tol;
-  h.stop_seq = kSeqNever;
-  h.hist = history ? ws->hist_dev : nullptr;
-  h.hist_cap = window;
-  KHIP_CHECK_HIP(hipMemcpyAsync(dev, &h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-  KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
   double *x = ws->x, *r = ws->r, *p = ws->p, *v = ws->v, *s = ws->s, *t = ws->qd;
-  int64_t enq = 0;
-  long long hist_base = 0;
-  std::vector<double> win;
-  auto drain_history = [&](long long upto_iter) -> int {
-    const long long cnt = upto_iter - hist_base;
-    if (!history || cnt <= 0) return KHIP_OK;
-    win.resize((size_t)cnt);
-    KHIP_CHECK_HIP(hipMemcpy(win.data(), ws->hist_dev, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
-    for (double val : win) ws->box.push(val);
-    return KHIP_OK;
-  };
-  int rc = KHIP_OK;
-  bool stopped = false;
-  for (int chunk = 0; !stopped; ++chunk) {
-    const int64_t cnt = std::min<int64_t>(kDevChunk, itmax - enq);
-    if (history && enq + cnt - hist_base > window) {
-      KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-      BicgDevState cur;
-      KHIP_CHECK_HIP(hipMemcpy(&cur, dev, sizeof(cur), hipMemcpyDeviceToHost));
-      if (cur.stop_seq != kSeqNever) break;
-      if ((rc = drain_history(cur.iter)) != KHIP_OK) break;
-      hist_base = cur.iter;
-      KHIP_CHECK_HIP(hipMemcpy(&dev->hist_base, &hist_base, sizeof(hist_base), hipMemcpyHostToDevice));
-    }
-    for (int64_t i = 0; i < cnt && rc == KHIP_OK; ++i) {
-      const long long j = (long long)(enq + i);
-      ctx->ctl = SeqCtl{&dev->stop_seq, 5 * j, EPI_BICG_A, dev};
-      int slot = take_slots(ctx, 1);
-      rc = spmv_any(ctx, A, p, v, slot, c, 0);                                  // :221-223  v = A p ; c.v -> alpha
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-      ctx->ctl = SeqCtl{};
-      if (rc != KHIP_OK) break;
-      rc = launch_bicg_sx(ctx, n, 0.0, r, v, p, s, x, dev, 5 * j + 1);               // :224-226
-      if (rc != KHIP_OK) break;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 5 * j + 2, EPI_BICG_B, dev};
-      slot = take_slots(ctx, 2);
-      rc = spmv_any(ctx, A, s, t, slot, nullptr, 1);                             // :228-230  t = A s ; t.s, t.t -> omega
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 2);
-      if (rc != KHIP_OK) break;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 5 * j + 3, EPI_BICG_C, dev};
-      slot = take_slots(ctx, 2);
-      rc = launch_bicg_xr(ctx, n, 0.0, s, t, s, c, x, r, slot, dev);                // :231-234, :240 -> beta, tests
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 2);
-      ctx->ctl = SeqCtl{};
-      if (rc != KHIP_OK) break;
-      rc = launch_bicg_p(ctx, n, 0.0, 0.0, v, r, p, dev, 5 * j + 4);                // :236-237
-    }
+  auto step = [&](BicgDevState *dev, long long j) {
+    ctx->ctl = SeqCtl{&dev->stop_seq, 5 * j, EPI_BICG_A, dev};
+    int slot = take_slots(ctx, 1);
+    int rc = spmv_any(ctx, A, p, v, slot, c, 0);                               // :221-223  v = A p ; c.v -> alpha
+    if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
     ctx->ctl = SeqCtl{};
-    if (rc != KHIP_OK) break;
-    enq += cnt;
-    const int b = chunk & 1;
-    KHIP_CHECK_HIP(hipMemcpyAsync(&ws->snap[b], dev, sizeof(BicgDevState), hipMemcpyDeviceToHost, ctx->stream));
-    KHIP_CHECK_HIP(hipEventRecord(ws->snap_ev[b], ctx->stream));
-    if (chunk >= 1) {
-      KHIP_CHECK_HIP(hipEventSynchronize(ws->snap_ev[b ^ 1]));
-      if (ws->snap[b ^ 1].stop_seq != kSeqNever) stopped = true;
-    }
-    if (enq >= itmax) stopped = true;
-    if (!stopped && time_limit_reached(ctx, now_s() - t0, timemax)) { *overtimed = true; stopped = true; }
-  }
-  ctx->ctl = SeqCtl{};
-  KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  if (rc != KHIP_OK) return rc;
-  KHIP_CHECK_HIP(hipMemcpy(out, dev, sizeof(BicgDevState), hipMemcpyDeviceToHost));
-  return drain_history(out->iter);
+    if (rc != KHIP_OK) return rc;
+    rc = launch_bicg_sx(ctx, n, 0.0, r, v, p, s, x, dev, 5 * j + 1);               // :224-226
+    if (rc != KHIP_OK) return rc;
+    ctx->ctl = SeqCtl{&dev->stop_seq, 5 * j + 2, EPI_BICG_B, dev};
+    slot = take_slots(ctx, 2);
+    rc = spmv_any(ctx, A, s, t, slot, nullptr, 1);                             // :228-230  t = A s ; t.s, t.t -> omega
+    if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 2);
+    if (rc != KHIP_OK) return rc;
+    ctx->ctl = SeqCtl{&dev->stop_seq, 5 * j + 3, EPI_BICG_C, dev};
+    slot = take_slots(ctx, 2);
+    rc = launch_bicg_xr(ctx, n, 0.0, s, t, s, c, x, r, slot, dev);                // :231-234, :240 -> beta, tests
+    if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 2);
+    ctx->ctl = SeqCtl{};
+    if (rc != KHIP_OK) return rc;
+    return launch_bicg_p(ctx, n, 0.0, 0.0, v, r, p, dev, 5 * j + 4);              // :236-237
+  };
+  return ws->loop.run(ctx, h, a, step, out, overtimed);
 }
 
 }  // namespace
@@ -1718,30 +1350,17 @@ int khip_bicgstab_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *x
 
 int khip_bicgstab_workspace_adopt_vector(khip_bicgstab_workspace *ws, const char *name, double *ptr) {
   KHIP_REQUIRE(ws && name, "bicgstab_workspace_adopt_vector: null argument");
-  struct { const char *k; double **slot; bool required; } tab[] = {
-      {"x", &ws->x, true}, {"r", &ws->r, true}, {"p", &ws->p, true}, {"v", &ws->v, true}, {"s", &ws->s, true},
-      {"qd", &ws->qd, true}, {"yz", &ws->yz, false}, {"t", &ws->t, false}, {"dx", &ws->dx, false}};
-  for (auto &e : tab)
-    if (strcmp(e.k, name) == 0) {
-      KHIP_REQUIRE(ptr || !e.required, "bicgstab_workspace_adopt_vector: x, r, p, v, s, qd cannot be emptied");
-      if (const char *other = held_elsewhere(tab, e.slot, ptr, nullptr)) {
-        set_error("bicgstab_workspace_adopt_vector: the pointer for '%s' already is the workspace's '%s' (every vector needs its own storage)", name, other);
-        return KHIP_ERR_INVALID;
-      }
-      adopt_into(ws->ctx, ws->borrowed, e.slot, ptr);
-      return KHIP_OK;
-    }
-  set_error("bicgstab_workspace_adopt_vector: unknown vector '%s' (x, r, p, v, s, qd, yz, t, dx)", name);
-  return KHIP_ERR_INVALID;
+  using S = NamedSlot;
+  return adopt_named(ws->ctx, ws->borrowed, {{"x", &ws->x, S::Required}, {"r", &ws->r, S::Required}, {"p", &ws->p, S::Required},
+                     {"v", &ws->v, S::Required}, {"s", &ws->s, S::Required}, {"qd", &ws->qd, S::Required},
+                     {"yz", &ws->yz, S::Optional}, {"t", &ws->t, S::Optional}, {"dx", &ws->dx, S::Optional}},
+                     "bicgstab_workspace_adopt_vector", "vector", name, ptr);
 }
 
 int khip_bicgstab_workspace_destroy(khip_bicgstab_workspace *ws) {
   if (!ws) return KHIP_OK;
   for (double *v : {ws->dx, ws->x, ws->r, ws->p, ws->v, ws->s, ws->qd, ws->yz, ws->t}) free_unless_borrowed(ws->ctx, ws->borrowed, v);
-  if (ws->dev_state) (void)hipFree(ws->dev_state);
-  if (ws->snap) (void)hipHostFree(ws->snap);
-  if (ws->hist_dev) (void)hipFree(ws->hist_dev);
-  for (auto e : ws->snap_ev) if (e) (void)hipEventDestroy(e);
+  ws->loop.release();
   delete ws;
   return KHIP_OK;
 }
@@ -1849,7 +1468,8 @@ int khip_bicgstab_solve(khip_bicgstab_workspace *ws, const khip_operator *A, con
   ws->box.path = device_loop ? 2 : (fused ? 1 : 0);
   if (device_loop && !(solved || tired)) {
     BicgDevState fin;
-    K(bicgstab_device_loop(ws, A->csr, c, next_rho, rNorm, eps_tol, itmax, o.history != 0, t0, timemax, &fin, &overtimed));
+    const DeviceLoopArgs loop_args{itmax, t0, timemax, o.history != 0, {&ws->box.residuals}};
+    K(bicgstab_device_loop(ws, A->csr, c, next_rho, rNorm, eps_tol, loop_args, &fin, &overtimed));
     iter = fin.iter;
     rNorm = fin.rNorm;
     solved = fin.solved != 0;

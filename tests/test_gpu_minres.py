@@ -184,6 +184,25 @@ def test_path2_is_bit_identical_to_path1(K, pctx, oracle, ending):
         assert s2.niter == 1
 
 
+def test_path2_history_window_drain(K, ctx, oracle):
+    """A history longer than the device window (ctx option hist_window): the three histories are drained in pieces and stay
+    identical to the host-driven loop's, and so does x."""
+    A_cpu, A = _operator(K, ctx, oracle, "poisson", 16)
+    b = np.cos(0.37 * np.arange(A_cpu.n)) + 0.5
+    kw = dict(atol=0.0, rtol=1e-12, etol=0.0)         # no forward-error exit: > 40 iterations
+    ctx.set_option("hist_window", 8)
+    try:
+        x2, s2, p2 = _run(K, ctx, A, b, fused=2, **kw)
+    finally:
+        ctx.set_option("hist_window", 1 << 14)
+    x1, s1, p1 = _run(K, ctx, A, b, fused=1, **kw)
+    assert (p1, p2) == (1, 2)
+    assert s2.niter == s1.niter > 40 and s2.status == s1.status
+    for f in ("residuals", "Aresiduals", "Acond"):
+        assert len(getattr(s2, f)) == s2.niter + 1 and np.array_equal(getattr(s1, f), getattr(s2, f)), f
+    assert np.array_equal(x1, x2)
+
+
 def test_fused_product(K, pctx, oracle):
     """The Lanczos step rides on the product exactly where the sliced kernel runs; its elementwise values are those of path 0's
     primitives (the residual estimates agree to the dots' rounding), and a warm start and Jacobi M take the same product."""

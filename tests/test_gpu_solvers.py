@@ -229,6 +229,24 @@ def test_cg_pipelined_variant_parity_budget(K, ctx, oracle, parity_log, n1):
     assert st4.solved and np.allclose(x4.to_host(), ref.x, rtol=0, atol=1e-6 * np.abs(ref.x).max())
 
 
+@pytest.mark.parametrize("variant", [1, 2])
+def test_cg_variant_history_window_drain(K, ctx, oracle, variant):
+    """variants 1 and 2 run only as device-resident loops: a history longer than the device window (ctx option hist_window)
+    is drained in pieces and gives the same bits as the same variant at the default window, and so does x."""
+    A = oracle.poisson3d(24)
+    dA = _upload(K, ctx, A)
+    b = ctx.array(np.random.default_rng(7).standard_normal(A.n))
+    ctx.set_option("hist_window", 8)
+    try:
+        x5, st5, _ = K.cg(dA, b, variant=variant, history=True, rtol=1e-12, atol=0.0)
+    finally:
+        ctx.set_option("hist_window", 1 << 14)
+    x6, st6, _ = K.cg(dA, b, variant=variant, history=True, rtol=1e-12, atol=0.0)
+    assert st5.niter == st6.niter > 40 and st5.status == st6.status
+    assert len(st5.residuals) == st5.niter + 1 and np.array_equal(st5.residuals, st6.residuals)
+    assert np.array_equal(x5.to_host(), x6.to_host())
+
+
 @pytest.mark.parametrize("n1,memory,sstep", [(12, 12, 4), (12, 10, 4), (16, 20, 1), (16, 20, 2), (16, 20, 5), (16, 24, 8), (20, 30, 4)])
 def test_gmres_sstep_variant_parity_budget(K, ctx, oracle, parity_log, n1, memory, sstep):
     """options.variant = 2 of gmres!: s-step GMRES: blocks of s monomial-basis vectors,
