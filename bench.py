@@ -8,6 +8,10 @@ process per GPU, RCCL over xGMI inside libkrylov_hip: all-gather of the (hi, lo)
 halo exchange before each SpMV).  Inputs are generated on the device, so the timed region starts with
 everything resident in HBM.
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line.  Everything else the
+line can carry -- the oracle parity and self-consistency legs, the CPU baseline, the int32-column roofline leg, the cfg 3 /
+cfg 5 legs and, at N > 1, the A/B legs and single-reduction CG -- takes runs of its own and is done only with --full.
+
 Prints ONE JSON line on rank 0 (stdout); diagnostics go to stderr.
 """
 import argparse
@@ -460,20 +464,23 @@ def main():
     ap.add_argument("--n1", type=int, default=512, help="grid size per dimension (default: cfg 2, 512^3)")
     ap.add_argument("--fused", type=int, default=2,
                     help="0 = reference primitive sequence, 1 = fused kernels, 2 = fused + device-resident scalars")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the side legs: oracle parity, CPU baseline, int32-column roofline, cfg 3 / cfg 5, "
+                         "and at N > 1 the A/B legs and single-reduction CG (off: the line carries the headline and what the timed steps give)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--compress", action="store_true",
                     help="NOT the headline: re-encode the operator as row templates (khip_csr_compress, 2 B of matrix data per row)")
     ap.add_argument("--variant", type=int, default=0,
                     help="NOT the headline: 1 = single-reduction CG (one all-reduce per iteration; different rounding)")
     ap.add_argument("--opt", action="append", default=[], help="tuning knob key=value (khip_ctx_set_option)")
-    ap.add_argument("--no-full-parity", action="store_true", help="skip the (untimed) full solve to rtol 1e-8 of the parity leg")
-    ap.add_argument("--no-ab", action="store_true", help="N > 1: skip the A/B legs (overlap_halo = 0, comm_priority = 0)")
+    ap.add_argument("--no-full-parity", action="store_true", help="with --full: skip the (untimed) full solve to rtol 1e-8 of the parity leg")
+    ap.add_argument("--no-ab", action="store_true", help="with --full and N > 1: skip the A/B legs (overlap_halo = 0, comm_priority = 0)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the (untimed for `value`) legs of BASELINE cfg 3 (gmres!) and cfg 5 (block_gmres!)")
+                    help="with --full: skip the (untimed for `value`) legs of BASELINE cfg 3 (gmres!) and cfg 5 (block_gmres!)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="exercise only the N-rank launch + rendezvous (gloo), no GPU work: tests/test_bench_launch.py")
     ap.add_argument("--also-variant1", action="store_true",
-                    help="also time single-reduction CG and report it as the nested entry single_reduction_cg (always done with --gpus > 1)")
+                    help="also time single-reduction CG and report it as the nested entry single_reduction_cg (done with --full at --gpus > 1 anyway)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed cg! returned (x, residual history, niter) as DIR/<name>.npy")
     args = ap.parse_args()
@@ -624,7 +631,7 @@ def main():
     ctx.set_option("profile_spmv", 0)
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, ws, n, r0, r1, rank, dist if world > 1 else None)
-    # N > 1: every rank's phase times to rank 0; then the same K iterations with the halo overlap off and with the communication
+    # N > 1: every rank's phase times to rank 0; then, with --full, the same K iterations with the halo overlap off and with the communication
     # stream at default priority (an A/B inside ONE launch: the one scaling run the driver may get should explain itself)
     phases, ab = None, None
     if use_comm:
@@ -633,8 +640,8 @@ def main():
             profs = [None] * world
             dist.all_gather_object(profs, prof_main)
         phases = summarize_phases(profs, args.steps)
-        ab = {}
-        if args.variant == 0 and not args.no_ab:
+        ab = {} if args.full else None
+        if args.full and args.variant == 0 and not args.no_ab:
             other_overlap = 1 - ctx.get_option("overlap_halo")           # the setting the headline did NOT run with
             for name, key, val in ((f"overlap_halo_{other_overlap}", "overlap_halo", other_overlap), ("comm_priority_0", "comm_priority", 0)):
                 old_val = ctx.get_option(key)
@@ -661,19 +668,19 @@ def main():
                             "setting": f"{key} = {val} (the headline runs with {key} = {old_val})"}
     # parity leg (untimed): the first PARITY_ITERS residual norms of a fresh solve against the CPU oracle's
     parity_hist = first_hist
-    if n1 == 512 and len(first_hist) <= PARITY_ITERS:
+    if args.full and n1 == 512 and len(first_hist) <= PARITY_ITERS:
         K.cg_(ws, A, b, atol=0.0, rtol=0.0, itmax=PARITY_ITERS, history=True, fused=args.fused, variant=args.variant)
         parity_hist = ws.stats.residuals.copy()
     # ... and (untimed) the benchmark definition's full solve to convergence: iteration count, status, whole history
     full = None
-    if n1 == 512 and args.variant == 0 and not args.no_full_parity:
+    if args.full and n1 == 512 and args.variant == 0 and not args.no_full_parity:
         K.cg_(ws, A, b, atol=0.0, rtol=1e-8, itmax=n, history=True, fused=args.fused)
         full = {"niter": ws.stats.niter, "status": ws.stats.status, "residuals": ws.stats.residuals.copy()}
     # single-reduction CG (Chronopoulos-Gear: ONE all-reduce per iteration) timed the same way, reported as a nested,
-    # clearly labelled entry beside the headline whenever the run is partitioned over several ranks
+    # clearly labelled entry beside the headline whenever a --full run is partitioned over several ranks
     sr = None
     sr_error = None
-    if (world > 1 or args.also_variant1) and args.variant == 0:
+    if ((args.full and world > 1) or args.also_variant1) and args.variant == 0:
         try:
             K.cg_(ws, A, b, atol=0.0, rtol=0.0, itmax=max(args.warmup, 1), fused=args.fused, variant=1)
             barrier()
@@ -700,7 +707,7 @@ def main():
     # switched off, i.e. the kernel that moves every algorithmic byte of SURVEY 8(d) (12 B per entry: Float64 value + int32
     # column).  HIP-event average over the same number of steps.
     int32_leg = None
-    if world == 1 and code_bits != 32 and not templates and args.variant == 0:
+    if args.full and world == 1 and code_bits != 32 and not templates and args.variant == 0:
         saved = {k: ctx.get_option(k) for k in ("spmv_codes", "profile_spmv")}     # a user's --opt spmv_codes=... survives the leg
         ctx.set_option("spmv_codes", 0)
         try:
@@ -730,7 +737,7 @@ def main():
             for k, v in saved.items():
                 ctx.set_option(k, v)
     others = None
-    if world == 1 and n1 == 512 and args.variant == 0 and not args.no_other_configs and not templates:
+    if args.full and world == 1 and n1 == 512 and args.variant == 0 and not args.no_other_configs and not templates:
         try:
             others = other_configs(K, ctx, log)
         except Exception as e:          # never lose the headline line to a side leg
@@ -782,8 +789,9 @@ def main():
             "bytes_per_iteration_algorithmic_fused": iter_bytes_local * world,
             "bytes_per_iteration_reference_sequence": iter_bytes_unfused_local * world,
             "final_residual_norm": float(first_hist[-1]), "solves_in_timed_region": solves,
-            "parity": parity_vs_oracle(n1, parity_hist, full),
-            "self_consistency": self_consistency(n1, parity_hist),
+            "full": args.full,
+            "parity": parity_vs_oracle(n1, parity_hist, full) if args.full else None,
+            "self_consistency": self_consistency(n1, parity_hist) if args.full else None,
             "rccl_ranks_seen": rccl_ranks,
             "comm": (dict(ctx.comm_info(), halo=dict(zip(("gather_mode", "n_ghost", "n_send"), A.halo_info))) if use_comm else None),
             "phases": phases, "ab": ab, "halo_probe": halo_probe,
@@ -802,7 +810,7 @@ def main():
                          "avg_ms": avg_spmv_ms, "launches_per_iteration": spmv_per_iter,
                          "kernel_source_sha": kernel_source_sha()},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(n1)
             except Exception as e:          # never lose the GPU line to a host-side problem

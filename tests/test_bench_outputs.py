@@ -94,3 +94,21 @@ def test_bench_dumps_the_last_timed_step(tmp_path, oracle):
     assert got["residuals"].shape == ref.residuals.shape
     assert float(np.max(np.abs(got["residuals"] - ref.residuals) / ref.residuals)) <= 1e-9
     assert np.allclose(got["x"], ref.x, rtol=0, atol=1e-9 * np.abs(ref.x).max())
+
+
+@pytest.mark.gpu
+def test_plain_run_leaves_the_side_legs_to_full():
+    """Without --full the line carries the headline and what the timed steps give, and none of the legs that take runs of
+    their own: no parity or self-consistency leg, no CPU baseline, no int32-column roofline, no cfg 3 / cfg 5, no A/B."""
+    p = subprocess.run([sys.executable, BENCH, "--n1", "48", "--steps", "5", "--warmup", "2"], capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "cg_iters_per_sec_poisson3d_csr_512cubed" and d["unit"] == "iter/s" and d["dtype"] == "f64"
+    assert d["higher_is_better"] is True and d["steps"] == 5 and d["ms_per_step"] == pytest.approx(1e3 / d["value"], rel=1e-9)
+    assert d["full"] is False and "cpu_baseline" not in d
+    for key in ("parity", "self_consistency", "roofline_int32_csr", "single_reduction_cg", "cfg3_gmres", "cfg5_block_gmres", "ab"):
+        assert d[key] is None, key
+    assert d["roofline"]["avg_ms"] > 0 and d["roofline"]["launches_per_iteration"] == 1.0     # from the timed steps' own brackets

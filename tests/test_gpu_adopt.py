@@ -169,14 +169,14 @@ def test_block_gmres_adopted_equals_owned(K, ctx, restart):
 
 def test_bench_line_names_the_adopt_entry_and_carries_the_int32_leg():
     """bench.py's one JSON line (here at 96^3, 6 steps): config.entry says the timed solve ran through khip_cg_workspace_adopt, and
-    the nested, labelled general-CSR leg (int32 columns, spmv_codes = 0) is present beside the headline's roofline."""
+    with --full the nested, labelled general-CSR leg (int32 columns, spmv_codes = 0) is present beside the headline's roofline."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, KHIP_SPMV_CODES="2")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--n1", "96", "--steps", "6", "--warmup", "2", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--n1", "96", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=300, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]

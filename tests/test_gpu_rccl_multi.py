@@ -108,8 +108,8 @@ def test_bench_with_one_rank_communicator_equals_the_plain_path():
     for force in ("0", "1"):
         env = dict(os.environ, KHIP_FORCE_COMM=force, HSA_ENABLE_IPC_MODE_LEGACY="0")
         env.pop("RANK", None); env.pop("WORLD_SIZE", None)
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n1", "96", "--steps", "30", "--warmup", "2", "--no-cpu-baseline",
-                            "--also-variant1"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n1", "96", "--steps", "30", "--warmup", "2", "--full",
+                            "--no-cpu-baseline", "--also-variant1"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
         assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
         lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
         assert len(lines) == 1, lines                                   # exactly one JSON line on stdout
@@ -141,7 +141,7 @@ def test_bench_gpus_n_runs_n_rccl_ranks(world):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "20", "--warmup", "5",
-                        "--no-full-parity"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                        "--full", "--no-full-parity"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
     assert len(lines) == 1, lines

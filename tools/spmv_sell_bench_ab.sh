@@ -3,7 +3,7 @@
 # Prints it/s, ms per iteration and the HIP-event average of the fused SpMV per setting.
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 run() {
-  out=$(timeout 300 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-other-configs --no-full-parity "$@" 2>/dev/null)
+  out=$(timeout 300 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-other-configs --no-full-parity "$@" 2>/dev/null)
   python - "$out" "$*" <<'PY'
 import json, sys
 o = json.loads(sys.argv[1]); r = o["roofline"]
