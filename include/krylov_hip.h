@@ -506,6 +506,44 @@ int khip_minres_fused_product(khip_minres_workspace *ws);
 double           *khip_minres_vector(khip_minres_workspace *ws, const char *name);
 size_t            khip_minres_workspace_bytes(khip_minres_workspace *ws);   /* 6n doubles without M and without warm start */
 
+/* ---- cg_lanczos_shift! (src/cg_lanczos_shift.jl:107-284), real Float64: the family (A + s_i I) x_i = b, i = 1 .. nshifts, from one
+ * Lanczos basis.  CgLanczosShiftWorkspace (src/krylov_workspaces.jl:616-660).  The shifts travel in their own struct; khip_options /
+ * khip_stats keep their layout (stats.residuals stays empty: each shift's history comes from khip_cg_lanczos_shift_residuals;
+ * stats.indefinite = any shift indefinite).  Device footprint: 2 nshifts + 3 vectors of n doubles (x_i, p_i, Mv, Mv_prev, Mv_next),
+ * + 1 (v) with M. */
+typedef struct khip_cg_lanczos_shift_workspace khip_cg_lanczos_shift_workspace;
+typedef struct {
+  const double *shifts;       /* host array of nshifts shifts s_i                         (src/cg_lanczos_shift.jl:95) */
+  int nshifts;                /* must equal the workspace's                               (:121-122) */
+  int check_curvature;        /* freeze the shifts whose (A + s_i I) shows curvature <= 0 (:98, :226-229) */
+} khip_cg_lanczos_shift_params;
+khip_cg_lanczos_shift_params khip_cg_lanczos_shift_default_params(void);   /* shifts = NULL, nshifts = 0, check_curvature = 0 */
+int khip_cg_lanczos_shift_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, int nshifts, khip_cg_lanczos_shift_workspace **out);
+/* CgLanczosShiftWorkspace on the caller's Mv, Mv_prev, Mv_next and x[0 .. nshifts), p[0 .. nshifts) (device pointers in HOST arrays);
+ * every pointer must be distinct.  adopt_vector names: "v" (the preconditioned vector, needed with M); a pointer that already is
+ * another vector of the workspace, x_i and p_i included, is refused. */
+int khip_cg_lanczos_shift_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, int nshifts, double *Mv, double *Mv_prev,
+                                          double *Mv_next, double *const *x, double *const *p, khip_cg_lanczos_shift_workspace **out);
+int khip_cg_lanczos_shift_workspace_adopt_vector(khip_cg_lanczos_shift_workspace *ws, const char *name, double *ptr);
+int khip_cg_lanczos_shift_workspace_destroy(khip_cg_lanczos_shift_workspace *ws);
+/* cg_lanczos_shift!(ws, A, b, shifts; M, check_curvature, atol, rtol, itmax, timemax, verbose, history, callback).  M == NULL means
+ * M = I, otherwise v <- M Mv (symmetric positive definite).  No warm start (the reference has none).  Loops
+ * (khip_cg_lanczos_shift_last_path): 2 = device-resident (CSR operator, M = I, no callback, verbose = 0, nshifts <= 64), 1 = host-driven
+ * on the same kernels (same bits as 2), 0 = one launch per primitive (options.fused = 0). */
+int khip_cg_lanczos_shift_solve(khip_cg_lanczos_shift_workspace *ws, const khip_operator *A, const khip_operator *M, const double *b,
+                                const khip_options *opts, const khip_cg_lanczos_shift_params *params);
+double           *khip_cg_lanczos_shift_solution(khip_cg_lanczos_shift_workspace *ws, int i);   /* x_i, i = 0 .. nshifts - 1 */
+const khip_stats *khip_cg_lanczos_shift_stats(khip_cg_lanczos_shift_workspace *ws);
+/* stats.residuals[i] of the last solve (history = true), owned by the workspace until its next solve */
+int khip_cg_lanczos_shift_residuals(khip_cg_lanczos_shift_workspace *ws, int i, const double **residuals, int *nres);
+/* the workspace's per-shift arrays after the last solve, 8 x nshifts doubles in this order: rNorms, σ, δhat, ω, γ, converged, not_cv,
+ * stats.indefinite (the last three as 0 / 1) */
+int khip_cg_lanczos_shift_arrays(khip_cg_lanczos_shift_workspace *ws, double *out);
+int khip_cg_lanczos_shift_last_path(khip_cg_lanczos_shift_workspace *ws);
+/* named work vectors: "Mv", "Mv_prev", "Mv_next", "v", "x1" .. "x<nshifts>", "p1" .. "p<nshifts>" */
+double           *khip_cg_lanczos_shift_vector(khip_cg_lanczos_shift_workspace *ws, const char *name);
+size_t            khip_cg_lanczos_shift_workspace_bytes(khip_cg_lanczos_shift_workspace *ws);   /* (2 nshifts + 3) n doubles without M */
+
 int khip_gmres_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, int memory, khip_gmres_workspace **out);
 /* GmresWorkspace on the caller's x, w and basis V_host[0 .. memory) (device pointers in a HOST array; `V::Vector{S}`,
  * src/krylov_workspaces.jl:2857-2873).  adopt_vector names: "x", "w", "p", "q", "dx".  adopt_basis replaces the whole list

@@ -463,6 +463,84 @@ function Krylov.minres!(ws::MinresWs, A::HIPCsr, b::HIPVector; M = I, ldiv::Bool
   return ws
 end
 
+# ------------------------------------------------------------------------------------------------ cg_lanczos_shift!  (src/cg_lanczos_shift.jl:107-284)
+struct LanczosShiftParams           # khip_cg_lanczos_shift_params: shifts (host array), nshifts, check_curvature
+  shifts::Ptr{Cdouble}; nshifts::Cint; check_curvature::Cint
+end
+const CgLanczosShiftWs = CgLanczosShiftWorkspace{Float64,Float64,HIPVector}
+function cg_lanczos_shift_handle(ws::CgLanczosShiftWs)
+  get!(HANDLES, ws) do
+    r = Ref{Ptr{Cvoid}}()
+    xs = Ptr{Cdouble}[v.ptr for v in ws.x];  ps = Ptr{Cdouble}[v.ptr for v in ws.p]
+    ck(ccall((:khip_cg_lanczos_shift_workspace_adopt, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                                                                   Ptr{Ptr{Cdouble}}, Ptr{Ptr{Cdouble}}, Ref{Ptr{Cvoid}}),
+             CTX[].h, ws.m, ws.n, ws.nshifts, ws.Mv.ptr, ws.Mv_prev.ptr, ws.Mv_next.ptr, xs, ps, r))
+    h = r[]
+    finalizer(_ -> ccall((:khip_cg_lanczos_shift_workspace_destroy, lib), Cint, (Ptr{Cvoid},), h), ws)
+    h
+  end
+end
+# stats.residuals[i], stats.indefinite and the workspace's per-shift arrays from the library (after the solve and before every callback)
+function sync_shift_state!(ws::CgLanczosShiftWs, h::Ptr{Cvoid}, history::Bool)
+  p = ws.nshifts
+  a = Vector{Float64}(undef, 8p)
+  ck(ccall((:khip_cg_lanczos_shift_arrays, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h, a))
+  for (k, dst) in enumerate((ws.rNorms, ws.σ, ws.δhat, ws.ω, ws.γ))
+    dst .= view(a, (k - 1) * p + 1:k * p)
+  end
+  for (k, dst) in enumerate((ws.converged, ws.not_cv, ws.stats.indefinite))
+    dst .= view(a, (4 + k) * p + 1:(5 + k) * p) .!= 0
+  end
+  for i in 1:p
+    empty!(ws.stats.residuals[i])
+    history || continue
+    ptr, cnt = Ref{Ptr{Cvoid}}(), Ref{Cint}(0)
+    ck(ccall((:khip_cg_lanczos_shift_residuals, lib), Cint, (Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}, Ref{Cint}), h, i - 1, ptr, cnt))
+    cnt[] > 0 && append!(ws.stats.residuals[i], unsafe_wrap(Array, Ptr{Float64}(ptr[]), Int(cnt[])))
+  end
+  return ws
+end
+
+function Krylov.cg_lanczos_shift!(ws::CgLanczosShiftWs, A::HIPCsr, b::HIPVector, shifts::AbstractVector{Float64}; M = I, ldiv::Bool = false,
+                                  check_curvature::Bool = false, atol::Float64 = √eps(Float64), rtol::Float64 = √eps(Float64), itmax::Int = 0,
+                                  timemax::Float64 = Inf, verbose::Int = 0, history::Bool = false, callback = nothing,
+                                  iostream::IO = Krylov.kstdout, fused::Int = 2)
+  if ldiv || !native_precond(M) || !native_log(verbose, iostream)
+    GENERIC_SOLVES[] += 1
+    return invoke(Krylov.cg_lanczos_shift!, Tuple{CgLanczosShiftWs,Any,AbstractVector{Float64},AbstractVector{Float64}}, ws, A, b, shifts;
+                  M, ldiv, check_curvature, atol, rtol, itmax, timemax, verbose, history,
+                  callback = callback === nothing ? (w -> false) : callback, iostream)
+  end
+  m, n = size(A)                                                                            # the reference's own argument checks, :115-122
+  (m == ws.m && n == ws.n) || error("(workspace.m, workspace.n) = ($(ws.m), $(ws.n)) is inconsistent with size(A) = ($m, $n)")
+  m == n || error("System must be square")
+  length(b) == n || error("Inconsistent problem size")
+  nshifts = length(shifts)
+  nshifts == ws.nshifts || error("workspace.nshifts = $(ws.nshifts) is inconsistent with length(shifts) = $nshifts")
+  Krylov.allocate_if(M !== I, ws, :v, HIPVector, ws.Mv)                                      # :133
+  h = cg_lanczos_shift_handle(ws)
+  ck(ccall((:khip_cg_lanczos_shift_workspace_adopt_vector, lib), Cint, (Ptr{Cvoid}, Cstring, Ptr{Cdouble}), h, "v", dptr(ws.v)))
+  sp = ccall((:khip_cg_lanczos_shift_stats, lib), Ptr{Stats}, (Ptr{Cvoid},), h)
+  cb = user_callback(callback)
+  # the callback reads ws.x, ws.stats and the per-shift arrays: they are brought over before it runs (the loop is host-driven then)
+  cbw = cb === nothing ? nothing : (w -> (sync_shift_state!(w, h, history); cb(w)))
+  cbf, cbd, box = callback_args(cbw, ws, sp, false)
+  opts = Ref(Options(; atol, rtol, itmax, timemax, history, fused, verbose, log_fd = logfd(iostream), callback = cbf, callback_data = cbd))
+  sh = Vector{Float64}(shifts)
+  prm = Ref(LanczosShiftParams(pointer(sh), Cint(nshifts), Cint(check_curvature)))
+  opA = Ref(Operator(A))
+  rc = GC.@preserve ws A b M sh opts prm opA box ccall((:khip_cg_lanczos_shift_solve, lib), Cint,
+                                                        (Ptr{Cvoid}, Ref{Operator}, Ptr{Operator}, Ptr{Cdouble}, Ref{Options}, Ptr{Cvoid}),
+                                                        h, opA, opref(M), b.ptr, opts, prm)
+  st = unsafe_load(sp)
+  sync_shift_state!(ws, h, history)
+  ws.stats.niter = st.niter;  ws.stats.solved = st.solved != 0;  ws.stats.timer = st.timer;  ws.stats.status = cstr(st.status)
+  NATIVE_SOLVES[] += 1;  LAST_PATH[] = ccall((:khip_cg_lanczos_shift_last_path, lib), Cint, (Ptr{Cvoid},), h)
+  finish_callback(box)
+  rc == 0 || failed(st)
+  return ws
+end
+
 # ------------------------------------------------------------------------------------------------ device matrix (block solvers)
 # Tall blocks are libkrylov_hip panels (ROW-major, rows padded to 16, padding rows zero), small blocks host matrices -- exactly
 # where the library keeps them (csrc/block.cpp) and where the reference's own small LAPACK calls run.  INTEGRATION.md has the

@@ -199,6 +199,25 @@ end
     @test ws.stats.solved
   end
 
+  @testset "CG-LANCZOS-SHIFT -- $FC" begin                            # one Lanczos basis for (A + s_i I) x_i = b
+    b = S(b_cpu);  shifts = [0.0, 1e-2, 1.0, 10.0]
+    x, stats = native(2) do; cg_lanczos_shift(A_gpu, b, shifts); end
+    @test stats.solved
+    for (i, s) in enumerate(shifts)
+      @test norm(b_cpu - (A_cpu + s * I) * Vector(x[i])) ≤ 10 * (atol + rtol * norm(b_cpu))
+    end
+    ws = CgLanczosShiftWorkspace(nA, nA, length(shifts), S); ws2 = CgLanczosShiftWorkspace(nA, nA, length(shifts), S)
+    native(2) do; krylov_solve(Val(:cg_lanczos_shift), A_gpu, b, shifts); end
+    native(2) do; cg_lanczos_shift!(ws, A_gpu, b, shifts; history = true); end
+    invoke(cg_lanczos_shift!, Tuple{typeof(ws2),Any,AbstractVector{Float64},AbstractVector{Float64}}, ws2, A_gpu, b, shifts; history = true)
+    @test ws.stats.niter == ws2.stats.niter
+    for i in eachindex(shifts)
+      @test ws.stats.residuals[i] ≈ ws2.stats.residuals[i] rtol = 1e-6
+    end
+    native(1) do; cg_lanczos_shift!(ws, A_gpu, b, shifts; M = KrylovHIP.jacobi(A_gpu)); end
+    @test ws.stats.solved
+  end
+
   @testset "block-GMRES -- $FC" begin
     p = 4
     B_cpu = hcat((U_cpu * (collect(1.0:nA) .^ (j / 4)) for j in 1:p)...)

@@ -58,6 +58,10 @@ class CMinresParams(C.Structure):
     _fields_ = [("lambda_", C.c_double), ("etol", C.c_double), ("conlim", C.c_double)]
 
 
+class CLanczosShiftParams(C.Structure):
+    _fields_ = [("shifts", c_double_p), ("nshifts", C.c_int), ("check_curvature", C.c_int)]
+
+
 class CStats(C.Structure):
     _fields_ = [("niter", C.c_int), ("solved", C.c_int), ("inconsistent", C.c_int), ("indefinite", C.c_int),
                 ("npcCount", C.c_int), ("timer", C.c_double), ("status", C.c_char * 96),
@@ -222,6 +226,20 @@ SIGNATURES = {
     "khip_minres_fused_product": (_int, [_vp]),
     "khip_minres_vector": (_vp, [_vp, C.c_char_p]),
     "khip_minres_workspace_bytes": (_sz, [_vp]),
+    "khip_cg_lanczos_shift_default_params": (CLanczosShiftParams, []),
+    "khip_cg_lanczos_shift_workspace_create": (_int, [_vp, _i64, _i64, _int, c_void_pp]),
+    "khip_cg_lanczos_shift_workspace_adopt": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _vp, c_void_pp, c_void_pp, c_void_pp]),
+    "khip_cg_lanczos_shift_workspace_adopt_vector": (_int, [_vp, C.c_char_p, _vp]),
+    "khip_cg_lanczos_shift_workspace_destroy": (_int, [_vp]),
+    "khip_cg_lanczos_shift_solve": (_int, [_vp, C.POINTER(COperator), C.POINTER(COperator), _vp, C.POINTER(COptions),
+                                           C.POINTER(CLanczosShiftParams)]),
+    "khip_cg_lanczos_shift_solution": (_vp, [_vp, _int]),
+    "khip_cg_lanczos_shift_stats": (C.POINTER(CStats), [_vp]),
+    "khip_cg_lanczos_shift_residuals": (_int, [_vp, _int, C.POINTER(c_double_p), C.POINTER(_int)]),
+    "khip_cg_lanczos_shift_arrays": (_int, [_vp, c_double_p]),
+    "khip_cg_lanczos_shift_last_path": (_int, [_vp]),
+    "khip_cg_lanczos_shift_vector": (_vp, [_vp, C.c_char_p]),
+    "khip_cg_lanczos_shift_workspace_bytes": (_sz, [_vp]),
     "khip_block_gmres_workspace_bytes": (_sz, [_vp, C.POINTER(C.c_size_t)]),
     "khip_test_gen_banded_random_host": (_int, [_i64, _int, _int, C.c_uint64, _int, _int, _i64, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_double_p, C.POINTER(_i64)]),
     "khip_test_small_dense": (_int, [_int, _int, _int, _int, c_double_p, c_double_p, c_double_p]),
@@ -1275,6 +1293,108 @@ class MinresWorkspace(_Workspace):
         return DeviceVector(self.ctx, self.n, ptr=p, owner=self) if p else None
 
 
+class LanczosShiftStats:
+    """LanczosShiftStats (src/krylov_stats.jl): residuals and indefinite per shift."""
+
+    def __init__(self, st: CStats, residuals, indefinite):
+        self.niter = st.niter
+        self.solved = bool(st.solved)
+        self.residuals = residuals
+        self.indefinite = indefinite
+        self.timer = st.timer
+        self.allocation_timer = st.allocation_timer
+        self.status = st.status.decode("utf-8")
+        self.error = st.error.decode("utf-8")
+
+    def __repr__(self):
+        return f"LanczosShiftStats(niter={self.niter}, solved={self.solved}, status={self.status!r})"
+
+
+class CgLanczosShiftWorkspace(_Workspace):
+    """CgLanczosShiftWorkspace(m, n, nshifts, S) (src/krylov_workspaces.jl:616-660): x and p are lists of nshifts DeviceVectors;
+    stats.residuals is one history per shift, stats.indefinite one flag per shift."""
+    _prefix = "cg_lanczos_shift"
+    ARRAYS = ("rNorms", "σ", "δhat", "ω", "γ", "converged", "not_cv", "indefinite")      # khip_cg_lanczos_shift_arrays order
+
+    def __init__(self, ctx: Context, m: int, n: int, nshifts: int, adopt: bool | None = None):
+        self.ctx, self.m, self.n, self.nshifts = ctx, m, n, int(nshifts)
+        self.adopted = _adopt_default() if adopt is None else bool(adopt)
+        self._h = C.c_void_p()
+        if self.adopted:
+            t0 = time.perf_counter()
+            self._vec = {k: ctx.empty(n) for k in ("Mv", "Mv_prev", "Mv_next")}          # v stays empty
+            self._x = [ctx.empty(n) for _ in range(self.nshifts)]
+            self._pv = [ctx.empty(n) for _ in range(self.nshifts)]
+            self._alloc_s = time.perf_counter() - t0
+            v = self._vec
+            xs = (C.c_void_p * self.nshifts)(*[u.ptr for u in self._x])
+            ps = (C.c_void_p * self.nshifts)(*[u.ptr for u in self._pv])
+            _ck(lib().khip_cg_lanczos_shift_workspace_adopt(ctx._h, m, n, self.nshifts, v["Mv"].ptr, v["Mv_prev"].ptr,
+                                                            v["Mv_next"].ptr, C.cast(xs, c_void_pp), C.cast(ps, c_void_pp),
+                                                            C.byref(self._h)))
+        else:
+            _ck(lib().khip_cg_lanczos_shift_workspace_create(ctx._h, m, n, self.nshifts, C.byref(self._h)))
+
+    def _owned(self, name):
+        return DeviceVector(self.ctx, self.n, ptr=lib().khip_cg_lanczos_shift_vector(self._h, name.encode()), owner=self)
+
+    @property
+    def x(self):
+        """workspace.x: one solution per shift."""
+        if self.adopted:
+            return list(self._x)
+        return [self._owned(f"x{i + 1}") for i in range(self.nshifts)]
+
+    @property
+    def p(self):
+        if self.adopted:
+            return list(self._pv)
+        return [self._owned(f"p{i + 1}") for i in range(self.nshifts)]
+
+    def arrays(self) -> dict:
+        """The workspace's per-shift host arrays (rNorms, σ, δhat, ω, γ, converged, not_cv) and stats.indefinite."""
+        out = np.zeros(8 * self.nshifts)
+        _ck(lib().khip_cg_lanczos_shift_arrays(self._h, out.ctypes.data_as(c_double_p)))
+        a = {k: out[i * self.nshifts:(i + 1) * self.nshifts].copy() for i, k in enumerate(self.ARRAYS)}
+        for k in ("converged", "not_cv", "indefinite"):
+            a[k] = a[k] != 0
+        return a
+
+    @property
+    def rNorms(self):
+        return self.arrays()["rNorms"]
+
+    @property
+    def converged(self):
+        return self.arrays()["converged"]
+
+    @property
+    def not_cv(self):
+        return self.arrays()["not_cv"]
+
+    @property
+    def stats(self) -> LanczosShiftStats:
+        res = []
+        for i in range(self.nshifts):
+            ptr, cnt = c_double_p(), _int()
+            _ck(lib().khip_cg_lanczos_shift_residuals(self._h, i, C.byref(ptr), C.byref(cnt)))
+            res.append([ptr[j] for j in range(cnt.value)])
+        st = LanczosShiftStats(lib().khip_cg_lanczos_shift_stats(self._h).contents, res, list(self.arrays()["indefinite"]))
+        if self.adopted:
+            st.allocation_timer += self._alloc_s
+        st.timer += getattr(self, "_timer_extra", 0.0)
+        return st
+
+    def vector(self, name: str):
+        if self.adopted and name in self._vec:
+            return self._vec[name]
+        p = lib().khip_cg_lanczos_shift_vector(self._h, name.encode())
+        return DeviceVector(self.ctx, self.n, ptr=p, owner=self) if p else None
+
+    def warm_start_(self, x0):
+        raise KhipError(-4, "cg_lanczos_shift! has no warm start")
+
+
 def _finish(ws, rc):
     ws._timer_extra = 0.0          # an entry point that did work of its own before the solve adds it afterwards
     if rc != 0:
@@ -1336,6 +1456,26 @@ def minres_(ws: MinresWorkspace, A, b: DeviceVector, M=None, λ=0.0, etol=None, 
     return _finish(ws, rc)
 
 
+def cg_lanczos_shift_(ws: CgLanczosShiftWorkspace, A, b: DeviceVector, shifts, M=None, ldiv=False, check_curvature=False, **kw):
+    """cg_lanczos_shift!(workspace, A, b, shifts; M, ldiv, check_curvature, atol, rtol, itmax, timemax, verbose, history, callback,
+    iostream) (src/cg_lanczos_shift.jl:107-284).  Returns the workspace."""
+    keep = []
+    if len(b) != ws.n:
+        raise KhipError(-1, "Inconsistent problem size")
+    sh = np.ascontiguousarray(shifts, dtype=np.float64).ravel()
+    if len(sh) != ws.nshifts:
+        raise KhipError(-1, f"workspace.nshifts = {ws.nshifts} is inconsistent with length(shifts) = {len(sh)}")
+    ws._allocate_if(M is not None, "v")                                                   # src/cg_lanczos_shift.jl:133
+    opts = _make_options(keep=keep, ws=ws, ldiv=ldiv, **kw)
+    prm = lib().khip_cg_lanczos_shift_default_params()
+    prm.shifts = sh.ctypes.data_as(c_double_p)
+    prm.nshifts = len(sh)
+    prm.check_curvature = int(bool(check_curvature))
+    rc = lib().khip_cg_lanczos_shift_solve(ws._h, _make_operator(ws.ctx, A, ws.n, keep), _make_operator(ws.ctx, M, ws.n, keep),
+                                           _p(b), C.byref(opts), C.byref(prm))
+    return _finish(ws, rc)
+
+
 def _local_rows(A):
     return A.m if isinstance(A, CsrMatrix) else None
 
@@ -1359,6 +1499,8 @@ FORWARDED_DEFAULTS = {
     "minres": dict(M=None, ldiv=False, linesearch=False, λ=0.0, atol=_SQRT_EPS, rtol=_SQRT_EPS, etol=_SQRT_EPS,
                    conlim=1.0 / _SQRT_EPS, itmax=0, timemax=math.inf, verbose=0, history=False, callback=default_callback,
                    iostream=None),
+    "cg_lanczos_shift": dict(M=None, ldiv=False, check_curvature=False, atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0, timemax=math.inf,
+                             verbose=0, history=False, callback=default_callback, iostream=None),
 }
 WORKSPACE_KWARGS = {"gmres": dict(memory=20), "block_gmres": dict(memory=5)}      # kwargs_workspace_gmres, _block_gmres
 # kwargs_workspace_minres (src/minres.jl:159): kept apart from WORKSPACE_KWARGS, whose contents tests/test_abi.py pins
@@ -1380,7 +1522,13 @@ def _forward(method: str, kw: dict) -> dict:
 def krylov_workspace(method: str, *args, ctx: Context | None = None, **kw):
     """krylov_workspace(Val(method), m, n, S; memory) / (Val(method), A, b; memory) (src/interface.jl:117-141, 237-244)."""
     cls = {"cg": CgWorkspace, "gmres": GmresWorkspace, "bicgstab": BicgstabWorkspace, "block_gmres": BlockGmresWorkspace,
-           "minres": MinresWorkspace}[method]
+           "minres": MinresWorkspace, "cg_lanczos_shift": CgLanczosShiftWorkspace}[method]
+    if method == "cg_lanczos_shift":                                            # (A, b, nshifts) / (m, n, nshifts)
+        if isinstance(args[1], DeviceVector):
+            A, b, nshifts = args
+            return cls(b.ctx, len(b), len(b), nshifts, **kw)
+        m, n, nshifts = args
+        return cls(ctx, m, n, nshifts, **kw)
     if len(args) == 2 and isinstance(args[1], DeviceVector):                  # (A, b)
         A, b = args
         return cls(b.ctx, len(b), len(b), **kw)
@@ -1401,6 +1549,11 @@ def krylov_solve_(ws, A, b, x0=None, **kw):
     """krylov_solve!(workspace, A, b[, x0]; kwargs...) (src/interface.jl:331-345, 306-320): dispatch on the workspace type; the x0
     form warm-starts first and charges that time to the solve, as the reference does."""
     method, inplace = _INPLACE[type(ws)]
+    if method == "cg_lanczos_shift":                                            # krylov_solve!(ws, A, b, shifts; kwargs...)
+        shifts = x0 if x0 is not None else kw.pop("shifts")
+        inplace(ws, A, b, shifts, **_forward(method, kw))
+        ws._timer_extra = 0.0
+        return ws
     full = _forward(method, kw)
     elapsed = 0.0
     if x0 is not None:
@@ -1418,6 +1571,15 @@ def krylov_solve(method: str, A, b, x0=None, ctx: Context | None = None, **kw):
     workspace (its creation charged to `timemax` and `stats.timer`), every keyword forwarded.  Returns (x, stats, workspace)."""
     wkw = {k: kw.pop(k) for k in list(kw) if k in _workspace_kwargs(method)}
     t0 = time.perf_counter()
+    if method == "cg_lanczos_shift":                     # krylov_solve(Val(:cg_lanczos_shift), A, b, shifts; kwargs...)
+        shifts = np.asarray(x0 if x0 is not None else kw.pop("shifts"), dtype=np.float64)
+        ws = krylov_workspace(method, A, b, len(shifts), **wkw)
+        elapsed = time.perf_counter() - t0
+        full = _forward(method, kw)
+        full["timemax"] = full["timemax"] - elapsed
+        cg_lanczos_shift_(ws, A, b, shifts, **full)
+        ws._timer_extra = elapsed
+        return ws.x, ws.stats, ws
     if method == "block_gmres":
         B = np.asarray(b, dtype=np.float64)
         ctx = ctx or A.ctx
@@ -1451,6 +1613,11 @@ def bicgstab(A, b: DeviceVector, x0=None, **kw):
 def minres(A, b: DeviceVector, x0=None, **kw):
     """Out-of-place minres(A, b[, x0]; window, kwargs...) -> (x, stats, workspace) (src/minres.jl:164-172)."""
     return krylov_solve("minres", A, b, x0, **kw)
+
+
+def cg_lanczos_shift(A, b: DeviceVector, shifts, **kw):
+    """Out-of-place cg_lanczos_shift(A, b, shifts; kwargs...) -> (x, stats, workspace), x a list of one DeviceVector per shift."""
+    return krylov_solve("cg_lanczos_shift", A, b, shifts, **kw)
 
 
 # --------------------------------------------------------------------------- Krylov processes
@@ -1887,4 +2054,5 @@ def block_gmres(A, B, X0=None, ctx=None, **kw):
 
 
 _INPLACE.update({CgWorkspace: ("cg", cg_), GmresWorkspace: ("gmres", gmres_), BicgstabWorkspace: ("bicgstab", bicgstab_),
-                 BlockGmresWorkspace: ("block_gmres", block_gmres_), MinresWorkspace: ("minres", minres_)})
+                 BlockGmresWorkspace: ("block_gmres", block_gmres_), MinresWorkspace: ("minres", minres_),
+                 CgLanczosShiftWorkspace: ("cg_lanczos_shift", cg_lanczos_shift_)})

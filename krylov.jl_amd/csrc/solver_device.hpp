@@ -15,7 +15,7 @@
 namespace khip {
 
 enum Epilogue { EPI_NONE = 0, EPI_CG_STEP1 = 1, EPI_CG_STEP2 = 2, EPI_BICG_A = 3, EPI_BICG_B = 4, EPI_BICG_C = 5, EPI_CGCG = 6,
-               EPI_MINRES_A = 7, EPI_MINRES_B = 8, EPI_MINRES_C = 9 };
+               EPI_MINRES_A = 7, EPI_MINRES_B = 8, EPI_MINRES_C = 9, EPI_LZSHIFT_A = 10, EPI_LZSHIFT_B = 11 };
 
 struct CgDevState {
   double gamma;        // r.z of the current iterate              (src/cg.jl:162, 257)
@@ -180,6 +180,86 @@ __host__ __device__ inline bool minres_step_c(MinresDevState &s, double xNorm, l
   return s.solved || tired || ill_cond;
 }
 
+// cg_lanczos_shift! (src/cg_lanczos_shift.jl:107-284): the Lanczos scalars and the per-shift CG scalars of a family
+// (A + s_i I) x_i = b.  The same code runs on the host (loops 0 and 1) and as the epilogue of the w.w reduction of an iteration
+// (device-resident loop): one source, the reference's IEEE operations in its order, so loops 1 and 2 produce the same bits.
+// The per-shift arrays sit in the state for the device-resident loop (p <= kShiftMax); the host loops keep their own.
+constexpr int kShiftMax = 64;            // shifts the device state carries; more shifts run the host-driven loop
+
+struct LanczosShiftDevState {
+  double delta;        // δ = vᴴ A v of the current iteration                (:200)
+  double beta;         // β: βₖ while the iteration runs, βₖ₊₁ after its step   (:187, :208)
+  double inv_beta;     // one(T) / β: kdiv!(v, β)                             (:209)
+  double rho;          // ‖v‖² (one(T) with M = I)                              (:214)
+  double eps_tol;      // ε = atol + rtol β₁                                   (:238)
+  long long stop_seq, iter, hist_base, hist_cap;
+  double *hist;        // device history window: row k - 1 - hist_base holds iteration k's rNorms, one entry per shift
+  int nshifts, check_curvature, solved, pad;
+  // not_cv at the top of the update loop (:226-229) as the list P2 walks: act[0] = count, act[1 + j] = shift;
+  // coef[3 j .. 3 j + 2] = (γ, σ, ω) of that shift, the coefficients of its kaxpy! and kaxpby!
+  int act[kShiftMax + 1];
+  int converged[kShiftMax], not_cv[kShiftMax], indefinite[kShiftMax];
+  long long nhist[kShiftMax];        // entries pushed to each shift's history after β₁: the last iteration the shift was active
+  double coef[3 * kShiftMax];
+  double shifts[kShiftMax], sigma[kShiftMax], dhat[kShiftMax], omega[kShiftMax], gamma[kShiftMax], rNorms[kShiftMax];
+};
+
+// the per-shift arrays the scalar code works on: the device state's own, or the host loops' (any number of shifts)
+struct LzShiftArrays {
+  const double *shifts;
+  double *sigma, *dhat, *omega, *gamma, *rNorms, *coef;
+  int *converged, *not_cv, *indefinite, *act;
+  long long *nhist;
+};
+__host__ __device__ inline LzShiftArrays lzshift_arrays(LanczosShiftDevState &s) {
+  return LzShiftArrays{s.shifts, s.sigma, s.dhat, s.omega, s.gamma, s.rNorms, s.coef, s.converged, s.not_cv, s.indefinite, s.act,
+                       s.nhist};
+}
+
+// β = knorm_elliptic(v, Mv) (:208): β² -> β, one(T) / β
+__host__ __device__ inline void lzshift_beta(LanczosShiftDevState &s, double beta2) {
+  s.beta = sqrt(beta2);
+  s.inv_beta = 1.0 / s.beta;
+}
+
+// the per-shift loops of iteration k (:212-252) with s.delta, s.rho and the new s.beta; hist_row: where the pushed rNorms go
+// (null: nowhere).  True when no shift is left (solved = !any(not_cv)).
+__host__ __device__ inline bool lzshift_step(LanczosShiftDevState &s, const LzShiftArrays &a, long long k, double *hist_row) {
+  const int p = s.nshifts;
+  for (int i = 0; i < p; ++i) {
+    a.dhat[i] = s.delta + s.rho * a.shifts[i];
+    a.gamma[i] = 1.0 / (a.dhat[i] - a.omega[i] / a.gamma[i]);
+  }
+  for (int i = 0; i < p; ++i) a.indefinite[i] |= (a.gamma[i] <= 0) ? 1 : 0;
+  int nact = 0;
+  for (int i = 0; i < p; ++i) {
+    a.not_cv[i] = s.check_curvature ? !(a.converged[i] || a.indefinite[i]) : !a.converged[i];
+    if (a.not_cv[i]) {
+      a.act[1 + nact] = i;
+      a.coef[3 * nact] = a.gamma[i];
+      a.omega[i] = s.beta * a.gamma[i];
+      a.sigma[i] = a.sigma[i] * -a.omega[i];
+      a.omega[i] = a.omega[i] * a.omega[i];
+      a.coef[3 * nact + 1] = a.sigma[i];
+      a.coef[3 * nact + 2] = a.omega[i];
+      ++nact;
+      a.rNorms[i] = fabs(a.sigma[i]);
+      a.converged[i] = a.rNorms[i] <= s.eps_tol;
+      if (hist_row) hist_row[i] = a.rNorms[i];       // the push uses this not_cv (:245-249)
+      a.nhist[i] = k;
+    }
+  }
+  a.act[0] = nact;
+  bool any = false;
+  for (int i = 0; i < p; ++i) {
+    a.not_cv[i] = s.check_curvature ? !(a.converged[i] || a.indefinite[i]) : !a.converged[i];
+    any = any || a.not_cv[i];
+  }
+  s.iter = k;
+  s.solved = any ? 0 : 1;
+  return !any;
+}
+
 __device__ __forceinline__ bool seq_skip(const long long *stop_seq, long long seq) {
   return stop_seq != nullptr && seq >= *stop_seq;
 }
@@ -253,6 +333,18 @@ __device__ inline void solver_epilogue(int epi, void *state, const double *v, lo
   } else if (epi == EPI_MINRES_C) {                // v[0] = x.x                 :348-451
     MinresDevState *st = static_cast<MinresDevState *>(state);
     if (minres_step_c(*st, sqrt(v[0]), st->iter + 1, st->err_vec)) st->stop_seq = seq + 1;
+  } else if (epi == EPI_LZSHIFT_A) {               // v[0] = v.(A v)             src/cg_lanczos_shift.jl:200
+    static_cast<LanczosShiftDevState *>(state)->delta = v[0];
+  } else if (epi == EPI_LZSHIFT_B) {               // v[0] = w.w = β²            :208-252
+    LanczosShiftDevState *st = static_cast<LanczosShiftDevState *>(state);
+    const long long k = st->iter + 1;
+    lzshift_beta(*st, v[0]);
+    double *row = nullptr;
+    if (st->hist) {
+      const long long idx = k - 1 - st->hist_base;
+      if (idx >= 0 && idx < st->hist_cap) row = st->hist + idx * st->nshifts;
+    }
+    if (lzshift_step(*st, lzshift_arrays(*st), k, row)) st->stop_seq = seq + 2;   // this iteration's P2 (seq + 1) still runs
   } else if (epi == EPI_BICG_A) {                  // v[0] = c.v                 src/bicgstab.jl:223
     BicgDevState *st = static_cast<BicgDevState *>(state);
     st->alpha = st->rho / v[0];

@@ -147,12 +147,18 @@ void set_history(MinresDevState &s, double *w) {
   s.hist_acond = w ? w + 2 * kHistWindowMax : nullptr;
 }
 
+// entries of column c of a history row that belong to a state's history (cg_lanczos_shift!: each shift's history is a prefix)
+template <class S> long long hist_rows(const S &, int) { return std::numeric_limits<long long>::max(); }
+long long hist_rows(const LanczosShiftDevState &s, int c) { return s.nhist[c]; }
+
 struct DeviceLoopArgs {
   int64_t itmax;
   double t0, timemax;
   bool history;
   std::vector<double> *drain_to[3];      // history stream h -> its host vector (unused streams: null)
   int first_chunk = kDevChunk;           // iterations of the first chunk
+  int width = 1;                         // columns != null: ONE stream of rows of `width` entries per iteration,
+  std::vector<double> *columns = nullptr; // column c -> columns[c], drained up to hist_rows(state, c)
 };
 
 // The driver of a loop whose scalar state S lives on the device (solver_device.hpp) and stops itself: iterations are
@@ -189,8 +195,10 @@ struct DeviceLoop {
     KHIP_TRY(alloc());
     int streams = 0;
     while (streams < 3 && a.drain_to[streams]) ++streams;
+    if (a.columns) streams = 1;
+    const size_t width = a.columns ? (size_t)a.width : 1;
     if (a.history && !hist)
-      KHIP_TRY(khip_malloc(ctx, sizeof(double) * (size_t)streams * kHistWindowMax, reinterpret_cast<void **>(&hist)));
+      KHIP_TRY(khip_malloc(ctx, sizeof(double) * (size_t)streams * kHistWindowMax * width, reinterpret_cast<void **>(&hist)));
     const long long window = std::min<long long>(std::max<long long>(ctx->tune.hist_window, kDevChunk), kHistWindowMax);
     h.stop_seq = kSeqNever;
     h.hist_base = 0;
@@ -202,13 +210,21 @@ struct DeviceLoop {
     int64_t enq = 0;            // iterations enqueued
     long long hist_base = 0;
     std::vector<double> win;
-    auto drain = [&](long long upto_iter) -> int {             // entries for iterations (hist_base, upto_iter]
+    auto drain = [&](long long upto_iter, const S &st) -> int {   // entries for iterations (hist_base, upto_iter]
       const long long cnt = upto_iter - hist_base;
       if (!a.history || cnt <= 0) return KHIP_OK;
-      win.resize((size_t)cnt);
+      win.resize((size_t)cnt * width);
       for (int s = 0; s < streams; ++s) {
-        KHIP_CHECK_HIP(hipMemcpy(win.data(), hist + (size_t)s * kHistWindowMax, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost));
-        a.drain_to[s]->insert(a.drain_to[s]->end(), win.begin(), win.end());
+        KHIP_CHECK_HIP(hipMemcpy(win.data(), hist + (size_t)s * kHistWindowMax * width, sizeof(double) * (size_t)cnt * width,
+                                 hipMemcpyDeviceToHost));
+        if (!a.columns) {
+          a.drain_to[s]->insert(a.drain_to[s]->end(), win.begin(), win.end());
+          continue;
+        }
+        for (size_t c = 0; c < width; ++c) {
+          const long long rows = std::min<long long>(cnt, hist_rows(st, (int)c) - hist_base);
+          for (long long r = 0; r < rows; ++r) a.columns[c].push_back(win[(size_t)r * width + c]);
+        }
       }
       return KHIP_OK;
     };
@@ -221,7 +237,7 @@ struct DeviceLoop {
         S cur;
         KHIP_CHECK_HIP(hipMemcpy(&cur, dev, sizeof(cur), hipMemcpyDeviceToHost));
         if (cur.stop_seq != kSeqNever) break;
-        if ((rc = drain(cur.iter)) != KHIP_OK) break;
+        if ((rc = drain(cur.iter, cur)) != KHIP_OK) break;
         hist_base = cur.iter;
         KHIP_CHECK_HIP(hipMemcpy(&dev->hist_base, &hist_base, sizeof(hist_base), hipMemcpyHostToDevice));
       }
@@ -244,7 +260,7 @@ struct DeviceLoop {
     KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     if (rc != KHIP_OK) return rc;
     KHIP_CHECK_HIP(hipMemcpy(out, dev, sizeof(S), hipMemcpyDeviceToHost));
-    return drain(out->iter);
+    return drain(out->iter, *out);
   }
   template <class Step>
   int run(khip_ctx *ctx, const S &h, const DeviceLoopArgs &a, Step &&step, S *out, bool *overtimed) {
