@@ -268,13 +268,19 @@ int khip_multi_axpy(khip_ctx *ctx, int64_t n, int k, const double *y_host,
 /* Panels are n-by-p ROW-MAJOR in HBM (p contiguous; DESIGN.md "panel layout").
  * ref: mul!(R, V', Q) / mul!(Q, V, R, -1, 1) src/block_gmres.jl:244-247, householder!
  * src/block_krylov_utils.jl:201-208, X += V*Y src/block_gmres.jl:324-326. */
-/* a panel holds n_pad = n rounded up to 16 rows; the padding rows must be (and stay) zero */
+/* a panel holds n_pad = n rounded up to 16 rows; the padding rows must be (and stay) zero: khip_panel_gemm_tn and
+ * khip_panel_norm read them.  khip_panel_from_colmajor zeroes them itself (P may have held anything); every other entry
+ * expects them zero and leaves them zero FOR FINITE FACTORS -- the kernels compute the padding rows like any other row
+ * (0 * psi = 0) and do not mask rows >= n, so a factor block with an Inf or NaN turns them into NaN (0 * Inf); the same
+ * column of every real row is non-finite then as well.  n = 0: khip_panel_gemm_tn returns Psi = 0, the updates do
+ * nothing.  (tests/test_gpu_panel_exact.py) */
 int khip_panel_rows(int64_t n, int64_t *n_pad);
 int khip_panel_from_colmajor(khip_ctx *ctx, int64_t n, int p, const double *X_colmajor, double *P);
 int khip_panel_to_colmajor(khip_ctx *ctx, int64_t n, int p, const double *P, double *X_colmajor);
 /* Psi_host (p-by-p, column-major, HOST) <- V^T Q */
 int khip_panel_gemm_tn(khip_ctx *ctx, int64_t n, int p, const double *V, const double *Q, double *Psi_host);
-/* Q <- beta*Q + alpha * V * Psi  (Psi p-by-p column-major HOST) */
+/* Q <- beta*Q + alpha * V * Psi  (Psi p-by-p column-major HOST).  beta == 0: the old Q is not read (it may hold NaN), and V
+ * may then be Q itself (in-place Q <- Q Psi, same bits as out of place) */
 int khip_panel_gemm_nn(khip_ctx *ctx, int64_t n, int p, double alpha, const double *V,
                        const double *Psi_host, double beta, double *Q);
 /* Block Gram-Schmidt sweep of Q against the k panels V[0..k) (device pointers in a HOST array) in the reference's

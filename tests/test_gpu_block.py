@@ -1,4 +1,6 @@
-"""GPU parity of the panel kernels (MFMA f64) and block_gmres_ against numpy / the CPU oracle.
+"""GPU parity of the panel kernels (MFMA f64) and block_gmres_ against numpy / the CPU oracle.  The exact pins of the panel
+kernels (per-entry bounds against exact references, every width, the edges of the launch geometry, padding rows, non-finite
+inputs) are in tests/test_gpu_panel_exact.py; what is here checks them at solver level and kernel against kernel.
 
 The panel QR on the device is CholeskyQR2 with LAPACK's Householder signs and tau recovered from the top p x p block
 (csrc/block.cpp): Q, R and tau are compared with LAPACK's geqrf / orgqr directly, no sign fix-up.  block-GMRES parity is
