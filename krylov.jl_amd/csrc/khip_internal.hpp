@@ -86,24 +86,17 @@ struct Tuning {
   int spmv_rows = 256;      // rows per workgroup of the stream kernel
   int spmv_vec = 1;         // nnz per lane per load in the stream kernel (1, 2)
   int spmv_nt = 0;          // non-temporal loads for the val/col streams (measured slower on MI355X)
-  int spmv_xcd = 0;         // XCD-aware tile remap: R > 0 runs of R tiles per XCD, -1 contiguous eighths, 0 off
-  int spmv_sweep_s = 0;     // plane sweep (spmv_xcd = -2): tiles per grid plane (0 = from the handle's band width)
-  int spmv_sweep_w = 16;    // plane sweep: consecutive tiles per XCD column
+  int spmv_xcd = 0;         // XCD-aware tile remap: R > 0 runs of R tiles per XCD, -1 (any negative value) contiguous eighths, 0 off
   int spmv_nty = -1;        // y store of the SpMV kernels: -1 = non-temporal when y is >= 512 MiB (beyond the Infinity Cache), else plain; 0 plain, 1 non-temporal, 2 write-through (sc1)
   int spmv_dot_early = 0;   // staged kernels with a fused dot: load dotw[row] before the row block's windows
-  int spmv_fake_gather = 0; // tuning experiment (wrong results): coalesced x reads
   int spmv_tiles = 1;       // staged kernel: consecutive row blocks per workgroup
   int spmv_template = 1;    // use the row-template kernel on handles that khip_csr_compress compressed
   int spmv_tmpl_rows = 8;   // template kernel: rows per lane (amortises the per-workgroup table load; 1.02 -> 0.86 ms at 512^3)
   int spmv_cap = 0;         // staged kernel LDS window in entries (0 = sized to the widest row block)
-  int spmv_lds_pad = 0;     // experiment: extra dynamic LDS bytes per workgroup (lowers occupancy)
-  int spmv_blockptr = 1;    // use the L2-resident block-pointer table in the stream kernel
-  int spmv_pipe = 0;        // staged kernel: software-pipelined form with this many consecutive row blocks per workgroup (0 = one block per workgroup, no pipeline; measured no faster: profiles/r02b_sweep_pipe.log)
   int cg_setup_fused = 1;   // cg! (fused paths, M = I, no warm start): x = 0, r = p = b, gamma = b.b in one pass (khip_cg_setup) instead of four primitives
   int spmv_sell = 2;        // coded operators with 8-bit codes: the sliced (64-row transposed) form -- every lane loads its own row's entries with coalesced 8-byte loads, no LDS window, no barrier in the row walk (1: default load policy, 2: non-temporal loads of the matrix words, 0: off = spmv_code_kernel); 512^3: 2.21 -> 1.97-2.00 ms fused, CG 275 -> 290-297 it/s (profiles/r06ap, r06aq)
   int spmv_sell_pair = 1;   // sliced form of a coded operator: the row's words in 16-byte pairs (half the vector-memory instructions of the matrix stream): 7-point 512^3 fused 1.92-2.00 -> 1.77-1.84 ms, 27-point 216^3 plain 0.53 -> 0.49 ms; 2 = for the int32 form too (96 instead of 88 B per 7-point row: no gain, off)
   int spmv_sell_narrow = 0; // sliced form: 1 = 4-bit codes in one 32-bit word per row where the operator allows (<= 15 diagonals, <= 8 entries per row): 60 instead of 64 B per 7-point row -- and 8-10 % SLOWER at 512^3 (fused 2.13-2.15 against 1.93-1.98 ms: slices of 7 units are no longer 4 KB blocks, and the codes are a second stream of 256-byte wave loads; profiles/r06au_spmv_sell_narrow_ab.log): off
-  int spmv_stream_nt = 0;   // 16-byte-load stream kernel: matrix stream loaded with the non-temporal policy
   int spmv_blk_pub = 0;     // fused dots of the staged / coded / delta SpMV kernels: 1 = workgroup-level fold in LDS, one wave runs the double-double tree (block_publish); measured equal to the per-wave trees (profiles/r04b_sweep_headline.log): off
   int spmv_delta = 0;       // stream kernel: block-delta column stream (coldelta.hip: 1 or 2 B per entry + 6 B per escape) -- 0: never (default: 18 % fewer bytes but no faster on the banded + random operator, slower on stencils; profiles/r04a_sweep_delta.log); 1: operators of >= 4 M entries where it saves at least a sixth of the column bytes; 2: whatever the size; 8 / 16: that width, always
   int spmv_wide = 0;        // stream kernel: 1 = the 16-byte-load form (spmv_delta_kernel<int32_t>) where the delta stream is not used (measured equal on the irregular operator, 8 % slower on the 27-point one); 0: the 8 + 4 byte loads of spmv_stream_kernel
@@ -196,7 +189,7 @@ struct khip_ctx {
   int next_slot = 0;
   khip::Tuning tune;
   khip::SeqCtl ctl;                    // empty except inside a device-resident solver loop
-  khip::LanczosEpi lz;                 // empty except for minres!'s fused product (spmv_takes_lanczos)
+  khip::LanczosEpi lz;                 // empty except for minres!'s fused product (SpmvPlan::carries_lanczos)
   khip::Comm *comm = nullptr;
   void *panel_scratch = nullptr;       // panel.hip: V^T Q partial tiles + Psi staging ring
   // SpMV launch profiling (events recorded on `stream`, resolved lazily)
@@ -360,10 +353,24 @@ int launch_spmv(khip_ctx *ctx, const khip_csr *A, const double *x, double *y, in
                 int64_t row_lo, int64_t row_hi, int64_t *wave_cursor = nullptr, bool finish = true,
                 const double *dotw = nullptr, int dot_sq = 0,      // dot_sq: 0 none, 1 second output y.y, 2 second output dotw.dotw
                 int64_t hole_lo = 0, int64_t hole_hi = 0);         // hole_hi > hole_lo: rows [hole_lo, hole_hi) are left out (two ranges, one launch where the kernel can)
-int spmv_kernel_choice(const khip_ctx *ctx, const khip_csr *A);
-// true when a full-range fused product on this handle runs the sliced kernel, which carries minres!'s Lanczos epilogue (ctx->lz);
-// performs the lazy builds launch_spmv would perform first, so the answer holds for the next launch
-bool spmv_takes_lanczos(khip_ctx *ctx, const khip_csr *A);
+int spmv_kernel_choice(const khip_ctx *ctx, const khip_csr *A);   // the kernel family as khip_spmv_kernel_info reports it
+// The form of the product launch_spmv runs on a handle under the context's current options.  Callers ask the predicates; the
+// handle's *_state fields and the spmv_* options behind them are spmv_plan's business alone.
+enum class SpmvForm { Template, Wave, Stream, Staged, Coded, Sliced, Sliced32, Ordered, Vector };
+struct SpmvPlan {
+  SpmvForm form = SpmvForm::Vector;
+  int rows = 256;           // stream / staged / coded / sliced: rows per row block
+  bool delta = false;       // Stream: reads the block-delta column stream (launches that start on one of its row blocks)
+  bool wide = false;        // Stream: the 16-byte-load kernel on the plain columns wherever the delta stream is not read
+  bool one_range = false;   // options under which no form takes two row ranges in one launch
+  bool staged_family() const { return form == SpmvForm::Staged || form == SpmvForm::Coded || form == SpmvForm::Sliced || form == SpmvForm::Sliced32; }
+  bool takes_two_ranges() const { return staged_family() && !one_range; }      // given that the first range is whole 256-row blocks
+  bool carries_dot_sq() const { return form != SpmvForm::Ordered && form != SpmvForm::Vector; }   // the second reduction output
+  bool carries_lanczos() const { return form == SpmvForm::Sliced || form == SpmvForm::Sliced32; } // minres!'s epilogue (ctx->lz), with a fused dot
+};
+// build = true performs the lazy per-handle builds launch_spmv would perform first, so the answer holds for the next launch;
+// build = false reads what the handle holds
+SpmvPlan spmv_plan(khip_ctx *ctx, const khip_csr *A, bool build);
 int launch_spmm(khip_ctx *ctx, const khip_csr *A, const double *X, double *Y, int p);
 int csr_finalize(khip_ctx *ctx, khip_csr *A);   // row statistics after arrays are resident
 int csr_transpose(khip_ctx *ctx, const khip_csr *A, khip_csr *T);   // T = A' (fresh handle, deterministic entry order)

@@ -221,7 +221,7 @@ int launch_p3(khip_ctx *ctx, int64_t n, const MinresDevState *st, double *w, dou
 }
 #undef KHIP_MR_LAUNCH
 
-// y = A v followed by P1, reduction v.y into results[slot].  fuse (spmv_takes_lanczos): ONE launch -- the sliced SpMV applies the
+// y = A v followed by P1, reduction v.y into results[slot].  fuse (SpmvPlan::carries_lanczos): ONE launch -- the sliced SpMV applies the
 // Lanczos epilogue to each row's product and forms v.y in its fused dot; otherwise the plain product, then P1.  Same elementwise
 // expressions either way; under ctx->ctl the epilogue of the reduction runs in its finish kernel.
 int lanczos_product(khip_ctx *ctx, const khip_operator *A, bool fuse, int64_t n, const MinresDevState *st, const double *v,
@@ -475,7 +475,7 @@ int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const k
   ws->box.path = device_loop ? 2 : (o.fused ? 1 : 0);
   // the Lanczos epilogue inside the product: fused loops on a CSR handle whose product runs the sliced kernel (both fused loops decide
   // alike, so they keep producing the same bits)
-  const bool fuse = ws->box.path >= 1 && A->csr && !A->apply && spmv_takes_lanczos(ctx, A->csr);
+  const bool fuse = ws->box.path >= 1 && A->csr && !A->apply && spmv_plan(ctx, A->csr, true).carries_lanczos();
   ws->fused_product = fuse;
 
   if (ws->box.path == 0) {

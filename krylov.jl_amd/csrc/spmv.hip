@@ -50,25 +50,8 @@ __device__ __forceinline__ void store_y(const SpmvArgs &a, int64_t row, double v
 // MI355X_MICROARCH.md), each XCD has its own 4 MiB L2.  xcd_run = R > 0 hands every XCD runs of R
 // CONSECUTIVE tiles inside each window of 8R workgroups, so the x entries shared by neighbouring rows
 // (a stencil's +-n1 couplings) are fetched into ONE L2 instead of three, while the chip-wide access
-// front stays compact (window = 8R tiles).  xcd_run = -1: one contiguous eighth per XCD.
-//
-// xcd_run = -2: PLANE SWEEP.  A 3-D stencil couples row i to i +- S tiles (the neighbouring grid planes); with
-// the natural order those x lines are long gone from the 4 MiB L2 when the sweep reaches the next plane
-// (S = 1024 tiles = 27 MB of matrix stream at 512^3), so x is fetched ~4x.  Here every XCD takes a column of W
-// consecutive tiles and walks it THROUGH all planes before moving on: tile order (t, k, w) -> k*S + t*W + w,
-// XCD p owning the columns t = p (mod 8).  The plane-to-plane reuse distance shrinks from S to W tiles.
-// Any (S, W) gives a permutation of the tiles, so results never depend on it.
-__device__ __forceinline__ int chunk_id(int b, int G, int xcd_run, int S = 0, int W = 0) {
-  if (xcd_run == -2) {
-    if (S <= 0 || W <= 0 || S % (8 * W) != 0) return b;
-    const int K = G / S;                       // full planes
-    if (b >= K * S) return b;
-    const int p = b & 7, l = b >> 3;
-    const int per = K * W;
-    const int tt = l / per, rem = l - tt * per;
-    const int k = rem / W, w = rem - k * W;
-    return k * S + (tt * 8 + p) * W + w;
-  }
+// front stays compact (window = 8R tiles).  xcd_run < 0 (-1 is the documented value): one contiguous eighth per XCD.
+__device__ __forceinline__ int chunk_id(int b, int G, int xcd_run) {
   if (xcd_run > 0) {
     const int win = 8 * xcd_run;
     const int full = (G / win) * win;
@@ -135,7 +118,10 @@ __global__ __launch_bounds__(kBlock) void spmv_stream_kernel(SpmvArgs a, RedArgs
         double xg[IT];
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
-          // a.fake_gather (tuning experiment only): replace the scattered gather by a coalesced read
+          // a.fake_gather is always 0: the option that set it (coalesced reads in place of the gather, wrong results) is gone.  The
+          // select stays for now because the compiler forms the gather addresses in two batches of four around this uniform
+          // branch; without it 28 instantiations of this kernel need 2-8 more VGPRs and lose a wave per SIMD
+          // (profiles/spmv_plan_refactor_ab.md).  To go together with a form of this loop that keeps the occupancy.
           const int32_t ci = a.fake_gather ? (int32_t)((tid + it * kBlock) & 2047) + (c[it] & 0) : c[it];
           xg[it] = gather_x<DIST>(a, ci);
         }
@@ -207,7 +193,7 @@ __global__ __launch_bounds__(kBlock) void spmv_stage_kernel(SpmvArgs a, RedArgs 
   const int64_t nrows = a.row_hi - a.row_lo - a.hole_len;
   const int64_t nrb = (nrows + ROWS - 1) / ROWS;
   const int tpb = a.tiles_per_block > 0 ? a.tiles_per_block : 1;
-  const int cid = chunk_id(blockIdx.x, gridDim.x, a.xcd_remap, a.sweep_s, a.sweep_w);
+  const int cid = chunk_id(blockIdx.x, gridDim.x, a.xcd_remap);
   const int64_t rb_begin = (int64_t)cid * tpb;
   const int64_t rb_end = (rb_begin + tpb < nrb) ? rb_begin + tpb : nrb;
   dd dacc[2];                                // [0] = w . y ; [1] = y . y (only when a.dot_sq)
@@ -348,7 +334,7 @@ __global__ __launch_bounds__(kBlock) void spmv_code_kernel(SpmvArgs a, RedArgs r
   const int64_t nrows = a.row_hi - a.row_lo - a.hole_len;
   const int64_t nrb = (nrows + ROWS - 1) / ROWS;
   const int tpb = a.tiles_per_block > 0 ? a.tiles_per_block : 1;
-  const int cid = chunk_id(blockIdx.x, gridDim.x, a.xcd_remap, a.sweep_s, a.sweep_w);
+  const int cid = chunk_id(blockIdx.x, gridDim.x, a.xcd_remap);
   const int64_t rb_begin = (int64_t)cid * tpb;
   const int64_t rb_end = (rb_begin + tpb < nrb) ? rb_begin + tpb : nrb;
   dd dacc[2];
@@ -377,23 +363,13 @@ __global__ __launch_bounds__(kBlock) void spmv_code_kernel(SpmvArgs a, RedArgs r
           __builtin_amdgcn_make_buffer_rsrc(const_cast<CODE *>(code + c0), 0, lim4 * (int)sizeof(CODE), kBufRsrcWord3);
       u32x4 v[4];
       cvec c[2];
-      // cache policy of the matrix stream (a.stream_nt; experiment of round 4): 0 default, 1 nt, 2 sc0, 3 sc0 nt, 4 sc1, 5 sc1 nt
-#define KHIP_WIN_LOADS(AUX)                                                                   \
-      _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                        \
-        const int o = q * (4 * kBlock) + 4 * tid;                                            \
-        v[2 * q] = __builtin_amdgcn_raw_buffer_load_b128(rv, o * 8, 0, AUX);                 \
-        v[2 * q + 1] = __builtin_amdgcn_raw_buffer_load_b128(rv, o * 8 + 16, 0, AUX);        \
-        c[q] = code_load<CODE>::template ld<AUX>(rc, o * (int)sizeof(CODE));                 \
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int o = q * (4 * kBlock) + 4 * tid;
+        v[2 * q] = __builtin_amdgcn_raw_buffer_load_b128(rv, o * 8, 0, 0);
+        v[2 * q + 1] = __builtin_amdgcn_raw_buffer_load_b128(rv, o * 8 + 16, 0, 0);
+        c[q] = code_load<CODE>::ld(rc, o * (int)sizeof(CODE));
       }
-      switch (a.stream_nt) {
-        case 1: KHIP_WIN_LOADS(2) break;
-        case 2: KHIP_WIN_LOADS(1) break;
-        case 3: KHIP_WIN_LOADS(3) break;
-        case 4: KHIP_WIN_LOADS(16) break;
-        case 5: KHIP_WIN_LOADS(18) break;
-        default: KHIP_WIN_LOADS(0) break;
-      }
-#undef KHIP_WIN_LOADS
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const int o = q * (4 * kBlock) + 4 * tid;
@@ -480,7 +456,7 @@ __global__ __launch_bounds__(kBlock) void spmv_sell_kernel(SpmvArgs a, RedArgs r
   const int64_t nrows = a.row_hi - a.row_lo - a.hole_len;
   const int64_t nrb = (nrows + ROWS - 1) / ROWS;
   const int tpb = a.tiles_per_block > 0 ? a.tiles_per_block : 1;
-  const int cid = chunk_id(blockIdx.x, gridDim.x, a.xcd_remap, a.sweep_s, a.sweep_w);
+  const int cid = chunk_id(blockIdx.x, gridDim.x, a.xcd_remap);
   const int64_t rb_begin = (int64_t)cid * tpb;
   const int64_t rb_end = (rb_begin + tpb < nrb) ? rb_begin + tpb : nrb;
   dd dacc[2];
@@ -633,185 +609,13 @@ __global__ __launch_bounds__(kBlock) void spmv_sell_kernel(SpmvArgs a, RedArgs r
   }
 }
 
-// ---------------------------------------------------------------- staged rows, software-pipelined ----
-// The staged kernels above run one dependent chain per workgroup -- row pointers -> window (val + columns) -> x gathers
-// -> y -- and only the middle link carries the bulk of the bytes: with 8 workgroups per CU about 40 % of them have their
-// window in flight at any time, ~50 KB per CU, and by Little's law that, not HBM, sets the rate (5.2-5.5 TB/s of real
-// traffic while the streaming BLAS-1 kernels reach 6.2-6.7).  This kernel gives every workgroup a run of `tiles_per_block`
-// CONSECUTIVE row blocks and keeps three of them in different stages at once:
-//     iteration t:   walk block t out of LDS (LDS reads, x gathers issued)
-//                    -> issue the window loads of block t+1 into registers   (its row pointers arrived an iteration ago)
-//                    -> issue the row-pointer loads of block t+2
-//                    -> wait for the gathers only (counted vmcnt: vector loads return in order and the gathers are the
-//                       OLDEST outstanding ones), finish the rows, store y
-// so a workgroup has a window in flight practically all the time.  Everything is vector memory (the block-uniform row
-// pointers too: scalar loads return out of order and would turn every LDS wait into a wait for them), the loop body is
-// straight-line, lanes without a k-th entry are predicated by selects (they gather x[0]), and barriers order LDS only
-// (s_waitcnt lgkmcnt(0) + s_barrier: __syncthreads() would drain the prefetches).  Arithmetic per row is unchanged --
-// stored order, one rounded multiply and one rounded add per entry -- so y is bit-identical to the other kernels.
-// CODE = uint8_t / uint16_t: dictionary-coded columns (colcode.hip); CODE = int32_t: the plain CSR column stream.
-// Requires every row block to fit one window (rows * max_row_nnz + 3 <= 2048) and nnz > 0; launch_spmv checks.
-template <> struct code_load<int32_t> {    // 4 columns = four dwords
+template <> struct code_load<int32_t> {    // 4 plain int32 columns = four dwords (spmv_delta_kernel on the CSR column stream)
   typedef u32x4 vec;
   template <int AUX = 0>
   static __device__ __forceinline__ vec ld(__amdgpu_buffer_rsrc_t r, int byte_off) {
     return __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, AUX);
   }
 };
-
-__device__ __forceinline__ void lds_only_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-struct RowPtrSet { int s, e, a, b; };      // block start / end (uniform), this lane's row start / end
-
-template <typename CODE, bool DOT, bool COMP, bool DIST>
-__global__ __launch_bounds__(kBlock) void spmv_pipe_kernel(SpmvArgs a, RedArgs ra) {
-  if (seq_skip(a.stop_seq, a.seq)) return;
-  typedef typename code_load<CODE>::vec cvec;
-  constexpr bool CODED = sizeof(CODE) < 4;
-  constexpr int UK = 8;
-  const int ROWS = a.stage_rows;
-  const int CAP = a.stage_cap;
-  extern __shared__ __attribute__((aligned(16))) unsigned char s_stage[];
-  double *s_val = reinterpret_cast<double *>(s_stage);
-  CODE *s_code = reinterpret_cast<CODE *>(s_stage + (size_t)CAP * sizeof(double));
-  int32_t *s_tab = reinterpret_cast<int32_t *>(s_stage + (size_t)CAP * (sizeof(double) + sizeof(CODE)));
-  const int tid = threadIdx.x;
-  const CODE *code = CODED ? reinterpret_cast<const CODE *>(a.code) : reinterpret_cast<const CODE *>(a.col);
-  const int64_t nrows = a.row_hi - a.row_lo;
-  const int64_t nrb = (nrows + ROWS - 1) / ROWS;
-  const int tpb = a.tiles_per_block > 0 ? a.tiles_per_block : 1;
-  const int cid = chunk_id(blockIdx.x, gridDim.x, a.xcd_remap, a.sweep_s, a.sweep_w);
-  const int64_t rb_begin = (int64_t)cid * tpb;
-  const int64_t rb_end = (rb_begin + tpb < nrb) ? rb_begin + tpb : nrb;
-  const int kmax = a.max_row;
-  dd dacc[2];
-  dacc[0] = dd{0.0, 0.0};
-  dacc[1] = dd{0.0, 0.0};
-  if (CODED)
-    for (int i = tid; i < a.code_T; i += kBlock) s_tab[i] = a.code_tab[i];
-
-  // row pointers of block rb; blocks past the run are empty (all four words equal) and cost one cached line
-  auto load_rp = [&](int64_t rb) -> RowPtrSet {
-    int64_t r0 = a.row_lo + rb * ROWS;
-    if (rb >= rb_end || r0 > a.row_hi) r0 = a.row_hi;
-    const int64_t rend = (r0 + ROWS < a.row_hi) ? r0 + ROWS : a.row_hi;
-    const int64_t ia = (r0 + tid < rend) ? r0 + tid : rend;
-    const int64_t ib = (r0 + tid + 1 < rend) ? r0 + tid + 1 : rend;
-    RowPtrSet p;
-    p.s = a.rowptr[r0];
-    p.e = a.rowptr[rend];
-    p.a = a.rowptr[ia];
-    p.b = a.rowptr[ib];
-    return p;
-  };
-  u32x4 v[4];
-  cvec c[2];
-  auto issue_window = [&](const RowPtrSet &p) {
-    const int s = __builtin_amdgcn_readfirstlane(p.s), e = __builtin_amdgcn_readfirstlane(p.e);
-    const int c0 = s & ~3;
-    const int lim4 = (e - c0 + 3) & ~3;
-    const __amdgpu_buffer_rsrc_t rv =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(a.val + c0), 0, lim4 * 8, kBufRsrcWord3);
-    const __amdgpu_buffer_rsrc_t rc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<CODE *>(code + c0), 0, lim4 * (int)sizeof(CODE), kBufRsrcWord3);
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int o = q * (4 * kBlock) + 4 * tid;
-      v[2 * q] = __builtin_amdgcn_raw_buffer_load_b128(rv, o * 8, 0, 0);
-      v[2 * q + 1] = __builtin_amdgcn_raw_buffer_load_b128(rv, o * 8 + 16, 0, 0);
-      c[q] = code_load<CODE>::ld(rc, o * (int)sizeof(CODE));
-    }
-  };
-
-  RowPtrSet p0 = load_rp(rb_begin);
-  issue_window(p0);
-  RowPtrSet p1 = load_rp(rb_begin + 1);
-
-  for (int64_t rb = rb_begin; rb < rb_end; ++rb) {
-    // window of block rb: registers -> LDS (waits for its loads; the row pointers issued behind them stay in flight)
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int o = q * (4 * kBlock) + 4 * tid;
-      if (o < CAP) {
-        *reinterpret_cast<u32x4 *>(s_val + o) = v[2 * q];
-        *reinterpret_cast<u32x4 *>(s_val + o + 2) = v[2 * q + 1];
-        *reinterpret_cast<cvec *>(s_code + o) = c[q];
-      }
-    }
-    lds_only_barrier();
-    const int64_t r0 = a.row_lo + rb * ROWS;
-    const int64_t rend = (r0 + ROWS < a.row_hi) ? r0 + ROWS : a.row_hi;
-    const bool live = r0 + tid < rend;
-    const int32_t row = (int32_t)(r0 + tid);
-    const int base = p0.a - (p0.s & ~3);
-    const int cnt = p0.b - p0.a;
-    double acc = 0.0;
-    int k0 = 0;
-    for (; k0 + UK < kmax; k0 += UK) {          // rows longer than UK entries: all batches but the last, plain
-      int32_t cc[UK];
-      double vv[UK], xx[UK];
-#pragma unroll
-      for (int u = 0; u < UK; ++u) {
-        const int j = (k0 + u < cnt) ? base + k0 + u : 0;
-        cc[u] = (int32_t)s_code[j];
-        vv[u] = s_val[j];
-      }
-#pragma unroll
-      for (int u = 0; u < UK; ++u) {
-        const int32_t col = CODED ? row + s_tab[cc[u]] : cc[u];
-        xx[u] = gather_x<DIST>(a, (k0 + u < cnt) ? col : 0);
-      }
-#pragma unroll
-      for (int u = 0; u < UK; ++u) {
-        const double prod = vv[u] * xx[u];
-        const double next = acc + prod;
-        acc = (k0 + u < cnt) ? next : acc;
-      }
-    }
-    {   // last batch, with the prefetches between the issue of its gathers and their use
-      int32_t cc[UK];
-      double vv[UK], xx[UK];
-#pragma unroll
-      for (int u = 0; u < UK; ++u) {
-        const int j = (k0 + u < cnt) ? base + k0 + u : 0;
-        cc[u] = (int32_t)s_code[j];
-        vv[u] = s_val[j];
-      }
-#pragma unroll
-      for (int u = 0; u < UK; ++u) {
-        const int32_t col = CODED ? row + s_tab[cc[u]] : cc[u];
-        xx[u] = gather_x<DIST>(a, (k0 + u < cnt) ? col : 0);
-      }
-      double wv = 0.0;
-      if (DOT) wv = a.dotw[live ? r0 + tid : rend - 1];
-      __builtin_amdgcn_sched_barrier(0);
-      issue_window(p1);                          // block rb + 1 (v, c are free: they went to LDS before the barrier)
-      const RowPtrSet p2 = load_rp(rb + 2);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < UK; ++u) {
-        const double prod = vv[u] * xx[u];
-        const double next = acc + prod;
-        acc = (k0 + u < cnt) ? next : acc;
-      }
-      if (live) {
-        store_y(a, r0 + tid, acc);
-        if (DOT) {
-          acc_prod<COMP>(dacc[0], wv, acc);
-          if (a.dot_sq == 1) acc_prod<COMP>(dacc[1], acc, acc);
-          else if (a.dot_sq == 2) acc_prod<COMP>(dacc[1], wv, wv);
-        }
-      }
-      p0 = p1;
-      p1 = p2;
-    }
-    lds_only_barrier();                          // every lane is done with the LDS window
-  }
-  if (DOT) {
-    if (a.dot_sq) wave_publish<2>(dacc, ra);
-    else wave_publish<1>(reinterpret_cast<dd (&)[1]>(dacc), ra);
-  }
-}
 
 // ---------------------------------------------------------------- stream, wide loads, block-delta columns ----
 // The stream kernel (products in nnz order into LDS, then one lane per row sums its segment in stored order) for
@@ -871,7 +675,10 @@ __global__ __launch_bounds__(kBlock) void spmv_delta_kernel(SpmvArgs a, RedArgs 
           __builtin_amdgcn_make_buffer_rsrc(const_cast<CODE *>(code + c0), 0, lim4 * (int)sizeof(CODE), kBufRsrcWord3);
       u32x4 v[4];
       cvec c[2];
-      if (a.stream_nt) {       // matrix stream with the non-temporal policy (read once, by this CU): x lines stay longer in the L2
+      // a.stream_nt is always 0 (the option that set it is retired); the non-temporal twin of the loads stays for now because without
+      // this uniform branch spmv_delta_kernel<int32_t, DOT, !COMP, !DIST> is allocated 64 instead of 69 VGPRs and changes occupancy
+      // (profiles/spmv_plan_refactor_ab.md): to go with the stream kernel's gather select
+      if (a.stream_nt) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
           const int o = q * (4 * kBlock) + 4 * tid;
@@ -1268,7 +1075,7 @@ static void launch_stream_cfg(khip_ctx *ctx, const SpmvArgs &a, const RedArgs &r
 template <int ROWS, bool NT>
 static void launch_stage_cfg(khip_ctx *ctx, const SpmvArgs &a, const RedArgs &ra, unsigned grid, bool dot, bool comp,
                              bool dist) {
-  size_t lds = (size_t)ctx->tune.spmv_lds_pad + 12u * (size_t)a.stage_cap;
+  size_t lds = 12u * (size_t)a.stage_cap;
   const size_t pub = dot && a.blk_pub ? sizeof(dd) * (size_t)kBlock * (a.dot_sq ? 2u : 1u) : 0u;    // block_publish reuses the window
   if (lds < pub) lds = pub;
 #define KHIP_L(DOT, COMP, DIST) \
@@ -1280,7 +1087,7 @@ static void launch_stage_cfg(khip_ctx *ctx, const SpmvArgs &a, const RedArgs &ra
 template <typename CODE>
 static void launch_code_cfg(khip_ctx *ctx, const SpmvArgs &a, const RedArgs &ra, unsigned grid, bool dot, bool comp,
                             bool dist) {
-  size_t lds = (size_t)ctx->tune.spmv_lds_pad + (8u + sizeof(CODE)) * (size_t)a.stage_cap + 4u * (size_t)a.code_T;
+  size_t lds = (8u + sizeof(CODE)) * (size_t)a.stage_cap + 4u * (size_t)a.code_T;
   const size_t pub = dot && a.blk_pub ? sizeof(dd) * (size_t)kBlock * (a.dot_sq ? 2u : 1u) : 0u;    // block_publish reuses the window
   if (lds < pub) lds = pub;
 #define KHIP_L(DOT, COMP, DIST) \
@@ -1304,17 +1111,6 @@ static void launch_sell_cfg(khip_ctx *ctx, const SpmvArgs &a, const RedArgs &ra,
   KHIP_DISPATCH_DCD(KHIP_L);
 #undef KHIP_L
 #undef KHIP_SELL
-}
-
-template <typename CODE>
-static void launch_pipe_cfg(khip_ctx *ctx, const SpmvArgs &a, const RedArgs &ra, unsigned grid, bool dot, bool comp,
-                            bool dist) {
-  const size_t lds = (size_t)ctx->tune.spmv_lds_pad + (8u + sizeof(CODE)) * (size_t)a.stage_cap +
-                     (sizeof(CODE) < 4 ? 4u * (size_t)a.code_T : 0u);
-#define KHIP_L(DOT, COMP, DIST) \
-  hipLaunchKernelGGL((spmv_pipe_kernel<CODE, DOT, COMP, DIST>), dim3(grid), dim3(kBlock), lds, ctx->stream, a, ra)
-  KHIP_DISPATCH_DCD(KHIP_L);
-#undef KHIP_L
 }
 
 template <typename CODE>
@@ -1373,10 +1169,11 @@ static inline unsigned pick_grid(khip_ctx *ctx, int64_t tiles, bool persist) {
   return (unsigned)(tiles < cap ? tiles : cap);
 }
 
-// dot_slot >= 0 fuses x . y.  Several launches (interior + boundary ranges of a distributed operator) can
-// feed ONE reduction: each passes the running partial count in *wave_cursor (updated here) and only the
-// last one sets `finish`, which folds all partials written so far into results[dot_slot].
-// which kernel launch_spmv will pick for this operator (the staged one is the only one with the y.y output)
+// longest row of an operator whose columns get dictionary coded: spmv_kernel_choice keeps such an operator on the staged family, and
+// spmv_plan tries the codes on exactly the operators that this turns from the stream kernel into the staged family
+constexpr int kCodedMaxRow = 64;
+
+// which kernel family this operator takes, as the number khip_spmv_kernel_info reports (spmv_plan resolves the family into a form)
 int spmv_kernel_choice(const khip_ctx *ctx, const khip_csr *A) {
   if (A->tmpl_id && ctx->tune.spmv_template) return 5;      // compressed handle (khip_csr_compress)
   int kernel = ctx->tune.spmv_kernel;
@@ -1387,52 +1184,83 @@ int spmv_kernel_choice(const khip_ctx *ctx, const khip_csr *A) {
   // operator whose columns are dictionary coded (colcode.hip: stencils of up to 64 entries per row) keeps the staged kernel,
   // which is the one that streams the codes.  Very long rows: strided vector kernel (not bit-identical).
   if (kernel == 0) {
-    const bool short_rows = A->mean_row_nnz <= 12.0 && A->max_row_nnz <= 64;
-    const bool coded = A->code_state == 1 && ctx->tune.spmv_codes != 0 && A->max_row_nnz <= 64;
+    const bool short_rows = A->mean_row_nnz <= 12.0 && A->max_row_nnz <= kCodedMaxRow;
+    const bool coded = A->code_state == 1 && ctx->tune.spmv_codes != 0 && A->max_row_nnz <= kCodedMaxRow;
     kernel = (short_rows || coded) ? 4 : (A->mean_row_nnz <= 96.0 ? 1 : 2);
   }
   return kernel;
 }
 
-// The decisions of launch_spmv's kernel-4 branch that lead to spmv_sell_kernel, with the same lazy builds (the coded stream at the
-// top of launch_spmv, then the sliced copies): the fused product carries the Lanczos epilogue exactly when this holds.
-bool spmv_takes_lanczos(khip_ctx *ctx, const khip_csr *A) {
-  if (ctx->tune.spmv_kernel == 0 && A->code_state == 0 && A->mean_row_nnz > 12.0 && A->mean_row_nnz <= 64.0 && A->max_row_nnz <= 64 &&
-      ctx->tune.spmv_codes && (ctx->tune.spmv_codes != 1 || A->nnz >= ((int64_t)1 << 22)) && ctx->tune.spmv_nt == 0 && !ctx->tune.spmv_fake_gather &&
-      !(A->tmpl_id && ctx->tune.spmv_template))
-    optional_build(csr_build_codes(ctx, const_cast<khip_csr *>(A)));
-  if (spmv_kernel_choice(ctx, A) != 4) return false;
-  khip_csr *Am = const_cast<khip_csr *>(A);
-  const bool nt = ctx->tune.spmv_nt != 0, fake = ctx->tune.spmv_fake_gather != 0;
-  const bool try_codes = ctx->tune.spmv_codes && (ctx->tune.spmv_codes != 1 || A->nnz >= ((int64_t)1 << 22)) && !nt && !fake;
-  if (try_codes && Am->code_state == 0) optional_build(csr_build_codes(ctx, Am));
-  const bool coded = try_codes && Am->code_state == 1;
-  if (coded && ctx->tune.spmv_sell && Am->code_bits == 8 && Am->sell_state == 0 && ctx->tune.spmv_pipe <= 0) optional_build(csr_build_sell(ctx, Am));
-  const bool sliced = coded && ctx->tune.spmv_sell && Am->sell_state == 1 && ctx->tune.spmv_pipe <= 0;
-  if (coded) return sliced;
-  int rows = ctx->tune.spmv_rows;
-  if (rows != 256 && rows != 128 && rows != 64 && rows != 32) rows = 256;
-  while (rows > 32 && rows * A->mean_row_nnz > 2048.0) rows >>= 1;
-  const bool try32 = ctx->tune.spmv_sell && !nt && !fake && ctx->tune.spmv_pipe <= 0 && rows == 256 &&
-                     (ctx->tune.spmv_codes == 2 || ctx->tune.spmv_sell >= 3 || A->nnz >= ((int64_t)1 << 22));
-  if (try32 && Am->sell32_state == 0) optional_build(csr_build_sell32(ctx, Am));
-  return try32 && Am->sell32_state == 1;
+// Which form of the product runs on this handle under the context's current options: the ONE place that holds the thresholds and
+// calls the lazy per-handle builds (build = true; each is tried once per handle).  launch_spmv launches what this returns; whoever
+// needs to know beforehand what a product can carry (api.cpp spmv_any, minres.cpp) asks the predicates of the same plan.
+SpmvPlan spmv_plan(khip_ctx *ctx, const khip_csr *A, bool build) {
+  const Tuning &t = ctx->tune;
+  khip_csr *Am = const_cast<khip_csr *>(A);        // the builds fill the handle's caches
+  const bool nt = t.spmv_nt != 0;
+  const bool big = A->nnz >= ((int64_t)1 << 22);   // bandwidth bound: below 4 M entries an iteration is latency bound
+  // spmv_codes: 1 = coded stream for operators large enough to be bandwidth bound (below that the table lookup costs ~5 %,
+  // profiles/r02_bench_sizes.jsonl), 2 = whenever the operator qualifies, 16 = two-byte codes, 0 = never
+  const bool try_codes = t.spmv_codes && (t.spmv_codes != 1 || big) && !nt;
+  // coded column stream (colcode.hip): tried where the staged family runs, or would run once the operator is coded -- rows of up to
+  // 64 entries on few diagonals (the 27-point stencil) go to the stream kernel otherwise (spmv_kernel_choice)
+  if (build && try_codes && A->code_state == 0 && !(A->tmpl_id && t.spmv_template) &&
+      (t.spmv_kernel == 4 || (t.spmv_kernel == 0 && A->max_row_nnz <= kCodedMaxRow)))
+    optional_build(csr_build_codes(ctx, Am));
+  SpmvPlan p;
+  p.one_range = t.spmv_persist != 0 || nt || t.spmv_delta != 0 || t.spmv_wide != 0;
+  int rows = t.spmv_rows;
+  const int kernel = spmv_kernel_choice(ctx, A);
+  if (kernel == 5) p.form = SpmvForm::Template;
+  else if (kernel == 6) p.form = SpmvForm::Wave;
+  else if (kernel == 3) p.form = SpmvForm::Ordered;
+  else if (kernel == 1) {
+    p.form = SpmvForm::Stream;
+    if (rows * A->mean_row_nnz > 2048.0) {           // keep one LDS pass per row block
+      rows = 256;
+      while (rows > 32 && rows * A->mean_row_nnz > 2048.0) rows >>= 1;
+    }
+    if (rows != 256 && rows != 128 && rows != 64 && rows != 32) rows = 256;
+    // 16-byte-load form (spmv_delta_kernel): with the block-delta column stream (coldelta.hip) where that saves bytes, else on the
+    // plain int32 columns
+    const int dl = t.spmv_delta;
+    const bool wide_ok = !nt && t.spmv_vec != 2 && t.spmv_persist == 0 && A->nnz > 0;
+    if (build && wide_ok && dl && (dl != 1 || big) && A->delta_state == 0) optional_build(csr_build_delta(ctx, Am, rows));
+    p.delta = wide_ok && dl && A->delta_state == 1;
+    p.wide = wide_ok && t.spmv_wide;
+  } else if (kernel == 4) {
+    if (rows != 256 && rows != 128 && rows != 64 && rows != 32) rows = 256;
+    const bool coded = try_codes && A->code_state == 1;
+    // sliced form of the coded operator (csr_build_sell)
+    if (build && coded && t.spmv_sell && A->code_bits == 8 && A->sell_state == 0) optional_build(csr_build_sell(ctx, Am));
+    if (coded && t.spmv_sell && A->sell_state == 1) p.form = SpmvForm::Sliced;      // no window: one row per lane whatever the row length
+    else {
+      // the LDS window of the staged / coded kernels holds a whole row block: fewer rows per block for longer rows (three quarters of
+      // the lanes idle in the row walk at 27 entries per row)
+      while (rows > 32 && rows * A->mean_row_nnz > 2048.0) rows >>= 1;
+      // ... and the sliced form of the int32 column stream, for operators that are not coded (or with spmv_codes = 0); the same size
+      // rule as the codes: below 4 M entries the handle keeps one copy of its entries
+      const bool try32 = !coded && t.spmv_sell && !nt && rows == 256 && (t.spmv_codes == 2 || t.spmv_sell >= 3 || big);
+      if (build && try32 && A->sell32_state == 0) optional_build(csr_build_sell32(ctx, Am));
+      p.form = coded ? SpmvForm::Coded : ((try32 && A->sell32_state == 1) ? SpmvForm::Sliced32 : SpmvForm::Staged);
+    }
+  } else p.form = SpmvForm::Vector;
+  p.rows = rows;
+  return p;
 }
 
+// dot_slot >= 0 fuses x . y.  Several launches (interior + boundary ranges of a distributed operator) can
+// feed ONE reduction: each passes the running partial count in *wave_cursor (updated here) and only the
+// last one sets `finish`, which folds all partials written so far into results[dot_slot].
 int launch_spmv(khip_ctx *ctx, const khip_csr *A, const double *x, double *y, int dot_slot, int64_t row_lo,
                 int64_t row_hi, int64_t *wave_cursor, bool finish, const double *dotw, int dot_sq, int64_t hole_lo, int64_t hole_hi) {
   int64_t local_cursor = 0;
   if (!wave_cursor) wave_cursor = &local_cursor;
-  // mid-length rows on few diagonals (the 27-point stencil): try the coded column stream once, it decides between the staged
-  // and the stream kernel (spmv_kernel_choice).  BEFORE the two-range decision below, which asks spmv_kernel_choice: a build
-  // that changed the choice after a hole had been accepted would hand a row range with a hole to a kernel that does not
-  // skip it (tests/test_gpu_dist.py: first product on a handle = the boundary launch).
-  if (ctx->tune.spmv_kernel == 0 && A->code_state == 0 && A->mean_row_nnz > 12.0 && A->mean_row_nnz <= 64.0 && A->max_row_nnz <= 64 &&
-      ctx->tune.spmv_codes && (ctx->tune.spmv_codes != 1 || A->nnz >= ((int64_t)1 << 22)) && ctx->tune.spmv_nt == 0 && !ctx->tune.spmv_fake_gather &&
-      !(A->tmpl_id && ctx->tune.spmv_template))
-    optional_build(csr_build_codes(ctx, const_cast<khip_csr *>(A)));
-  // minres!'s Lanczos epilogue rides only on the sliced kernel's fused dot (the caller asked spmv_takes_lanczos): anything else is a defect
-  if (ctx->lz.coef && (dot_slot < 0 || dot_sq || !spmv_takes_lanczos(ctx, A))) {
+  // BEFORE the two-range decision below: a build that changed the form after a hole had been accepted would hand a row range with
+  // a hole to a kernel that does not skip it (tests/test_gpu_dist.py: first product on a handle = the boundary launch)
+  const SpmvPlan plan = spmv_plan(ctx, A, true);
+  // minres!'s Lanczos epilogue rides only on the sliced kernel's fused dot (the caller asked the same plan): anything else is a defect
+  if (ctx->lz.coef && (dot_slot < 0 || dot_sq || !plan.carries_lanczos())) {
     set_error("spmv: the Lanczos epilogue reached a product that does not run the sliced kernel with a fused dot");
     return KHIP_ERR_INVALID;
   }
@@ -1443,16 +1271,12 @@ int launch_spmv(khip_ctx *ctx, const khip_csr *A, const double *x, double *y, in
     if (hole_lo == row_lo) row_lo = hole_hi; else row_hi = hole_lo;
     hole = false;
   }
-  if (hole) {
-    const bool one_launch = spmv_kernel_choice(ctx, A) == 4 && ((hole_lo - row_lo) & 255) == 0 && ctx->tune.spmv_pipe <= 0 &&
-                            ctx->tune.spmv_persist == 0 && ctx->tune.spmv_nt == 0 && ctx->tune.spmv_delta == 0 && ctx->tune.spmv_wide == 0;
-    if (!one_launch) {
-      KHIP_TRY(launch_spmv(ctx, A, x, y, dot_slot, row_lo, hole_lo, wave_cursor, false, dotw, dot_sq));
-      return launch_spmv(ctx, A, x, y, dot_slot, hole_hi, row_hi, wave_cursor, finish, dotw, dot_sq);
-    }
+  if (hole && !(plan.takes_two_ranges() && ((hole_lo - row_lo) & 255) == 0)) {
+    KHIP_TRY(launch_spmv(ctx, A, x, y, dot_slot, row_lo, hole_lo, wave_cursor, false, dotw, dot_sq));
+    return launch_spmv(ctx, A, x, y, dot_slot, hole_hi, row_hi, wave_cursor, finish, dotw, dot_sq);
   }
   const int nout = dot_sq ? 2 : 1;
-  if (dot_sq && spmv_kernel_choice(ctx, A) != 4 && spmv_kernel_choice(ctx, A) != 5 && spmv_kernel_choice(ctx, A) != 1 && spmv_kernel_choice(ctx, A) != 6) { set_error("spmv: the second reduction output needs the staged, stream, wave or template kernel"); return KHIP_ERR_UNSUPPORTED; }
+  if (dot_sq && !plan.carries_dot_sq()) { set_error("spmv: the second reduction output needs the staged, stream, wave or template kernel"); return KHIP_ERR_UNSUPPORTED; }
   if (row_hi <= row_lo) {
     if (dot_slot >= 0 && finish) {
       if (*wave_cursor == 0) {                                              // nothing at all: writes 0
@@ -1470,8 +1294,7 @@ int launch_spmv(khip_ctx *ctx, const khip_csr *A, const double *x, double *y, in
   a.row_lo = row_lo; a.row_hi = row_hi;
   a.hole_lo = hole ? hole_lo : INT64_MAX; a.hole_len = hole ? hole_hi - hole_lo : 0;
   a.xcd_remap = ctx->tune.spmv_xcd;
-  a.sweep_s = ctx->tune.spmv_sweep_s;
-  a.sweep_w = ctx->tune.spmv_sweep_w;
+  a.sweep_s = 0; a.sweep_w = 0;
   // y store: non-temporal once y is far beyond the 256 MiB Infinity Cache (512^3: 1 GiB) -- the coded product 2.04 -> 1.96 ms,
   // fused 2.18 -> 2.14, CG +1.3 % (profiles/r04l_sweep_nty.log, r04m); below that the next kernel finds y in the cache and the
   // cacheable store wins (-3 % at 256^3, r01).  Write-through (2) measures like the plain store.
@@ -1486,13 +1309,12 @@ int launch_spmv(khip_ctx *ctx, const khip_csr *A, const double *x, double *y, in
   a.tmpl_T = A->tmpl_T; a.tmpl_K = A->tmpl_K;
   a.dot_sq = dot_sq;
   a.nnz_bound = A->nnz + kPad;
-  a.fake_gather = ctx->tune.spmv_fake_gather;
-  a.code = nullptr; a.code_tab = nullptr; a.code_T = 0; a.stage_rows = 256; a.max_row = 0;
+  a.fake_gather = 0; a.stream_nt = 0;
+  a.code = nullptr; a.code_tab = nullptr; a.code_T = 0; a.stage_rows = 256;
   a.sell = nullptr; a.sell_off = nullptr; a.sell_units = 0; a.sell_cols = 0; a.sell_c4 = nullptr; a.sell_pair = 0;
   a.blk_pub = ctx->tune.spmv_blk_pub;
-  a.stream_nt = ctx->tune.spmv_stream_nt;
   a.dcode = nullptr; a.dbase = nullptr; a.desc_ptr = nullptr; a.desc_pos = nullptr; a.desc_col = nullptr;
-  a.blockptr = (ctx->tune.spmv_blockptr && A->blockptr && (row_lo & 255) == 0) ? A->blockptr : nullptr;
+  a.blockptr = (A->blockptr && (row_lo & 255) == 0) ? A->blockptr : nullptr;
   a.lz = ctx->lz.coef != nullptr; a.lz_sub_r1 = ctx->lz.sub_r1; a.lz_coef = ctx->lz.coef; a.lz_r1 = ctx->lz.r1;
   const bool dot = dot_slot >= 0, comp = ctx->tune.compensated != 0, dist = A->dist;
   const bool persist = ctx->tune.spmv_persist != 0;
@@ -1515,12 +1337,11 @@ int launch_spmv(khip_ctx *ctx, const khip_csr *A, const double *x, double *y, in
     ctx->prof_used += 2;
   }
 
-  const int kernel = spmv_kernel_choice(ctx, A);               // (the lazy code build that can change it ran at the top of this call)
-  if (hole && kernel != 4) { set_error("spmv: a two-range launch reached kernel %d, which takes one range", kernel); return KHIP_ERR_INVALID; }
+  const SpmvForm form = plan.form;
   unsigned grid = 1;
   RedArgs ra;
   int wpb = kWavesPerBlock;                   // reduction partials one workgroup of the chosen kernel writes
-  if (kernel == 6) {
+  if (form == SpmvForm::Wave) {
     // wave-private windows: a window that takes a typical 64-row group whole (+ 20 %), in 256-entry steps, at most 2048 entries
     int64_t cap = ctx->tune.spmv_cap > 0 ? ctx->tune.spmv_cap : (int64_t)(64.0 * A->mean_row_nnz * 1.2) + 3;
     cap = (cap + 255) & ~(int64_t)255;
@@ -1530,42 +1351,29 @@ int launch_spmv(khip_ctx *ctx, const khip_csr *A, const double *x, double *y, in
     if (dot) KHIP_TRY(ensure_reduction_scratch(ctx, *wave_cursor + (int64_t)grid * wpb, nout));
     ra = make_red_args(ctx, dot ? dot_slot : 0); ra.wave_offset = *wave_cursor;
     launch_wave_cfg(ctx, a, ra, grid, dot, comp, dist);
-  } else if (kernel == 5) {
+  } else if (form == SpmvForm::Template) {
     const int rpt = ctx->tune.spmv_tmpl_rows > 0 ? ctx->tune.spmv_tmpl_rows : 1;      // rows per lane: amortises the table load
     grid = pick_grid(ctx, (nrows + (int64_t)kBlock * rpt - 1) / ((int64_t)kBlock * rpt), false);
     if (dot) KHIP_TRY(ensure_reduction_scratch(ctx, *wave_cursor + (int64_t)grid * kWavesPerBlock, nout));
     ra = make_red_args(ctx, dot ? dot_slot : 0); ra.wave_offset = *wave_cursor;
     launch_template_cfg(ctx, a, ra, grid, dot, comp, dist);
-  } else if (kernel == 1) {
-    int rows = ctx->tune.spmv_rows;
-    if (rows * A->mean_row_nnz > 2048.0) {           // keep one LDS pass per row block
-      rows = 256;
-      while (rows > 32 && rows * A->mean_row_nnz > 2048.0) rows >>= 1;
-    }
-    if (rows != 256 && rows != 128 && rows != 64 && rows != 32) rows = 256;
-    grid = pick_grid(ctx, (nrows + rows - 1) / rows, persist);
-    if (dot) KHIP_TRY(ensure_reduction_scratch(ctx, *wave_cursor + (int64_t)grid * kWavesPerBlock, nout));
-    ra = make_red_args(ctx, dot ? dot_slot : 0); ra.wave_offset = *wave_cursor;
-    const int vec = ctx->tune.spmv_vec == 2 ? 2 : 1;
-    // 16-byte-load form (spmv_delta_kernel): with the block-delta column stream (coldelta.hip, built once per handle at the
-    // first product that gets here) where that saves bytes, else on the plain int32 columns
-    khip_csr *Am = const_cast<khip_csr *>(A);
-    const int dl = ctx->tune.spmv_delta;
-    const bool wide_ok = !nt && !a.fake_gather && vec != 2 && !persist && A->nnz > 0;
-    if (wide_ok && dl && (dl != 1 || A->nnz >= ((int64_t)1 << 22)) && Am->delta_state == 0)
-      optional_build(csr_build_delta(ctx, Am, rows));
-    const bool delta = wide_ok && dl && Am->delta_state == 1 && row_lo % Am->delta_rows == 0;
-    if (delta || (wide_ok && ctx->tune.spmv_wide)) {
-      a.stage_rows = delta ? Am->delta_rows : rows;
-      if (delta) { a.dcode = Am->dcode; a.dbase = Am->dbase; a.desc_ptr = Am->desc_ptr; a.desc_pos = Am->desc_pos; a.desc_col = Am->desc_col; }
+  } else if (form == SpmvForm::Stream) {
+    const int rows = plan.rows;
+    const bool delta = plan.delta && row_lo % A->delta_rows == 0;      // the delta stream's row blocks start at row 0
+    if (delta || plan.wide) {
+      a.stage_rows = delta ? A->delta_rows : rows;
+      if (delta) { a.dcode = A->dcode; a.dbase = A->dbase; a.desc_ptr = A->desc_ptr; a.desc_pos = A->desc_pos; a.desc_col = A->desc_col; }
       grid = pick_grid(ctx, (nrows + a.stage_rows - 1) / a.stage_rows, false);
       if (dot) KHIP_TRY(ensure_reduction_scratch(ctx, *wave_cursor + (int64_t)grid * kWavesPerBlock, nout));
       ra = make_red_args(ctx, dot ? dot_slot : 0); ra.wave_offset = *wave_cursor;
       if (!delta) launch_delta_cfg<int32_t>(ctx, a, ra, grid, dot, comp, dist);
-      else if (Am->delta_bits == 8) launch_delta_cfg<uint8_t>(ctx, a, ra, grid, dot, comp, dist);
+      else if (A->delta_bits == 8) launch_delta_cfg<uint8_t>(ctx, a, ra, grid, dot, comp, dist);
       else launch_delta_cfg<uint16_t>(ctx, a, ra, grid, dot, comp, dist);
-      rows = 0;        // launched
-    }
+    } else {
+      grid = pick_grid(ctx, (nrows + rows - 1) / rows, persist);
+      if (dot) KHIP_TRY(ensure_reduction_scratch(ctx, *wave_cursor + (int64_t)grid * kWavesPerBlock, nout));
+      ra = make_red_args(ctx, dot ? dot_slot : 0); ra.wave_offset = *wave_cursor;
+      const int vec = ctx->tune.spmv_vec == 2 ? 2 : 1;
 #define KHIP_ROWS(R)                                                                              \
   do {                                                                                            \
     if (vec == 2) { if (nt) launch_stream_cfg<R, 2, true>(ctx, a, ra, grid, dot, comp, dist);     \
@@ -1573,92 +1381,53 @@ int launch_spmv(khip_ctx *ctx, const khip_csr *A, const double *x, double *y, in
     else          { if (nt) launch_stream_cfg<R, 1, true>(ctx, a, ra, grid, dot, comp, dist);     \
                     else    launch_stream_cfg<R, 1, false>(ctx, a, ra, grid, dot, comp, dist); }  \
   } while (0)
-    switch (rows) {
-      case 0: break;
-      case 256: KHIP_ROWS(256); break;
-      case 128: KHIP_ROWS(128); break;
-      case 64: KHIP_ROWS(64); break;
-      default: KHIP_ROWS(32); break;
-    }
+      switch (rows) {
+        case 256: KHIP_ROWS(256); break;
+        case 128: KHIP_ROWS(128); break;
+        case 64: KHIP_ROWS(64); break;
+        default: KHIP_ROWS(32); break;
+      }
 #undef KHIP_ROWS
-  } else if (kernel == 4) {
-    khip_csr *Am = const_cast<khip_csr *>(A);
-    // spmv_codes: 1 = coded stream for operators large enough to be bandwidth bound (>= 4 M entries: below that an iteration is
-    // latency bound and the table lookup costs ~5 %, profiles/r02_bench_sizes.jsonl), 2 = whenever the operator qualifies,
-    // 16 = two-byte codes, 0 = never
-    const bool try_codes = ctx->tune.spmv_codes && (ctx->tune.spmv_codes != 1 || A->nnz >= ((int64_t)1 << 22)) && !nt && !a.fake_gather;
-    // coded column stream (colcode.hip): built once per handle, at the first product that gets here
-    if (try_codes && Am->code_state == 0) optional_build(csr_build_codes(ctx, Am));
-    const bool coded = try_codes && Am->code_state == 1;
-    // sliced form of the coded operator (csr_build_sell): built once per handle, at the first product that gets here with spmv_sell on
-    if (coded && ctx->tune.spmv_sell && Am->code_bits == 8 && Am->sell_state == 0 && ctx->tune.spmv_pipe <= 0) optional_build(csr_build_sell(ctx, Am));
-    const bool sliced = coded && ctx->tune.spmv_sell && Am->sell_state == 1 && ctx->tune.spmv_pipe <= 0;
-    int rows = ctx->tune.spmv_rows;
-    if (rows != 256 && rows != 128 && rows != 64 && rows != 32) rows = 256;
-    // the LDS window of the staged / coded kernels holds a whole row block: fewer rows per block for longer rows (three quarters of the
-    // lanes idle in the row walk at 27 entries per row).  The sliced form has no window: one row per lane whatever the row length.
-    if (!sliced) while (rows > 32 && rows * A->mean_row_nnz > 2048.0) rows >>= 1;
+    }
+  } else if (plan.staged_family()) {
+    const int rows = plan.rows;
     // row blocks per workgroup: with a fused dot, two -- the double-double tree at a workgroup's end is ~0.1 us of dependent
     // fp64 latency on a 2.5 us lifetime, and it is paid once per workgroup whatever it covered: 2.19 -> 2.10 ms fused at 512^3,
     // the plain product is unchanged and four blocks per workgroup cost more than they save (profiles/r04b_sweep_headline.log)
-    const int64_t nrb_all = (nrows + rows - 1) / rows;
-    a.tiles_per_block = ctx->tune.spmv_tiles > 0 ? ctx->tune.spmv_tiles : ((dot && nrb_all >= 8192) ? 2 : 1);
+    const int64_t nrb = (nrows + rows - 1) / rows;
+    a.tiles_per_block = ctx->tune.spmv_tiles > 0 ? ctx->tune.spmv_tiles : ((dot && nrb >= 8192) ? 2 : 1);
     {   // LDS window: the widest row block (+3 for the 4-entry alignment of its start), at most 2048 entries
       int64_t cap = ctx->tune.spmv_cap > 0 ? ctx->tune.spmv_cap : (int64_t)rows * A->max_row_nnz + 3;
       cap = (cap + 3) & ~(int64_t)3;
       a.stage_cap = (int)(cap < 64 ? 64 : (cap > 2048 ? 2048 : cap));
     }
-    const int64_t nrb4 = (nrows + rows - 1) / rows;
-    grid = pick_grid(ctx, (nrb4 + a.tiles_per_block - 1) / a.tiles_per_block, false);
-    if ((int64_t)grid * a.tiles_per_block < nrb4) a.tiles_per_block = (int)((nrb4 + grid - 1) / grid);
+    grid = pick_grid(ctx, (nrb + a.tiles_per_block - 1) / a.tiles_per_block, false);
+    if ((int64_t)grid * a.tiles_per_block < nrb) a.tiles_per_block = (int)((nrb + grid - 1) / grid);
     if (dot) KHIP_TRY(ensure_reduction_scratch(ctx, *wave_cursor + (int64_t)grid * kWavesPerBlock, nout));
     ra = make_red_args(ctx, dot ? dot_slot : 0); ra.wave_offset = *wave_cursor;
+    a.stage_rows = rows;
+    if (form == SpmvForm::Sliced || form == SpmvForm::Coded) { a.code = A->code; a.code_tab = A->code_tab; a.code_T = A->code_T; }
+    if (form == SpmvForm::Sliced) {
+      a.sell = A->sell; a.sell_off = A->sell_off; a.sell_units = A->sell_units; a.sell_cols = 0; a.sell_c4 = A->sell_c4; a.sell_pair = A->sell_pair;
+      launch_sell_cfg(ctx, a, ra, grid, dot, comp, dist);
+    } else if (form == SpmvForm::Sliced32) {
+      a.sell = A->sell32; a.sell_off = A->sell32_off; a.sell_units = A->sell32_units; a.sell_cols = 1; a.sell_pair = A->sell32_pair; a.sell_c4 = nullptr;
+      launch_sell_cfg(ctx, a, ra, grid, dot, comp, dist);
+    } else if (form == SpmvForm::Coded) {
+      if (A->code_bits == 8) launch_code_cfg<uint8_t>(ctx, a, ra, grid, dot, comp, dist);
+      else launch_code_cfg<uint16_t>(ctx, a, ra, grid, dot, comp, dist);
+    } else {
 #define KHIP_STG(R) do { if (nt) launch_stage_cfg<R, true>(ctx, a, ra, grid, dot, comp, dist); \
                          else launch_stage_cfg<R, false>(ctx, a, ra, grid, dot, comp, dist); } while (0)
-    if (coded) { a.code = Am->code; a.code_tab = Am->code_tab; a.code_T = Am->code_T; }
-    a.stage_rows = rows;
-    a.max_row = (int)A->max_row_nnz;
-    // ... and of the int32 column stream, for operators that are not coded (or with spmv_codes = 0); the same size rule as the codes:
-    // below 4 M entries an iteration is latency bound and the handle keeps one copy of its entries
-    const bool try32 = !coded && ctx->tune.spmv_sell && !nt && !a.fake_gather && ctx->tune.spmv_pipe <= 0 && rows == 256 &&
-                       (ctx->tune.spmv_codes == 2 || ctx->tune.spmv_sell >= 3 || A->nnz >= ((int64_t)1 << 22));
-    if (try32 && Am->sell32_state == 0) optional_build(csr_build_sell32(ctx, Am));
-    const bool sliced32 = try32 && Am->sell32_state == 1;
-    // software-pipelined form: needs one window per row block
-    const bool pipe = ctx->tune.spmv_pipe > 0 && !nt && !a.fake_gather && A->nnz > 0 && A->max_row_nnz >= 1 &&
-                      (int64_t)rows * A->max_row_nnz + 3 <= 2048 && ctx->tune.spmv_cap == 0;
-    if (pipe) {
-      a.tiles_per_block = ctx->tune.spmv_pipe;
-      grid = pick_grid(ctx, (nrb4 + a.tiles_per_block - 1) / a.tiles_per_block, false);
-      if ((int64_t)grid * a.tiles_per_block < nrb4) a.tiles_per_block = (int)((nrb4 + grid - 1) / grid);
-      if (dot) KHIP_TRY(ensure_reduction_scratch(ctx, *wave_cursor + (int64_t)grid * kWavesPerBlock, nout));
-      ra = make_red_args(ctx, dot ? dot_slot : 0); ra.wave_offset = *wave_cursor;
-      if (!coded) launch_pipe_cfg<int32_t>(ctx, a, ra, grid, dot, comp, dist);
-      else if (Am->code_bits == 8) launch_pipe_cfg<uint8_t>(ctx, a, ra, grid, dot, comp, dist);
-      else launch_pipe_cfg<uint16_t>(ctx, a, ra, grid, dot, comp, dist);
-      rows = 0;      // launched
-    } else if (coded && sliced) {
-      a.sell = Am->sell; a.sell_off = Am->sell_off; a.sell_units = Am->sell_units; a.sell_cols = 0; a.sell_c4 = Am->sell_c4; a.sell_pair = Am->sell_pair;
-      launch_sell_cfg(ctx, a, ra, grid, dot, comp, dist);
-      rows = 0;      // launched
-    } else if (sliced32) {
-      a.sell = Am->sell32; a.sell_off = Am->sell32_off; a.sell_units = Am->sell32_units; a.sell_cols = 1; a.sell_pair = Am->sell32_pair; a.sell_c4 = nullptr;
-      launch_sell_cfg(ctx, a, ra, grid, dot, comp, dist);
-      rows = 0;      // launched
-    } else if (coded) {
-      if (Am->code_bits == 8) launch_code_cfg<uint8_t>(ctx, a, ra, grid, dot, comp, dist);
-      else launch_code_cfg<uint16_t>(ctx, a, ra, grid, dot, comp, dist);
-      rows = 0;      // launched
-    }
-    switch (rows) {
-      case 0: break;
-      case 256: KHIP_STG(256); break;
-      case 128: KHIP_STG(128); break;
-      case 64: KHIP_STG(64); break;
-      default: KHIP_STG(32); break;
-    }
+      switch (rows) {
+        case 256: KHIP_STG(256); break;
+        case 128: KHIP_STG(128); break;
+        case 64: KHIP_STG(64); break;
+        default: KHIP_STG(32); break;
+      }
 #undef KHIP_STG
-  } else if (kernel == 3) {
+    }
+  } else if (form == SpmvForm::Ordered) {
     int L = ctx->tune.spmv_lanes;
     if (L == 0) {                                    // smallest power of two covering a typical row
       L = 4;

@@ -26,9 +26,9 @@ struct SpmvArgs {
   int64_t row_lo, row_hi;
   int64_t hole_lo, hole_len;   // staged / coded kernels: the launch covers [row_lo, hole_lo) and [hole_lo + hole_len, row_hi) -- the two boundary ranges of a row-partitioned product in ONE launch (hole_lo - row_lo is a multiple of the row block; hole_len = 0: none)
   int xcd_remap;         // see chunk_id() in spmv.hip
-  int sweep_s, sweep_w;  // plane sweep (xcd_remap == -2): tiles per plane, tiles per XCD column
+  int sweep_s, sweep_w;  // SpMM kernels (csr_aux.hip) only: plane sweep of the tiles -- tiles per plane, tiles per XCD column
   int nt_y;              // non-temporal store of y
-  int tiles_per_block;   // staged kernel: consecutive row blocks per workgroup (software pipeline depth)
+  int tiles_per_block;   // staged kernel: consecutive row blocks per workgroup
   int64_t nnz_bound;     // nnz + pad: prefetches beyond it are clamped
   int stage_cap;         // staged kernel: LDS window in entries (multiple of 4, <= 2048)
   const uint16_t *tmpl_id;   // row-template compressed handle (template kernel only)
@@ -38,12 +38,12 @@ struct SpmvArgs {
   int tmpl_T, tmpl_K;
   const double *dotw;    // left vector of the fused dot: results[slot] = dotw . y   (x for p.Ap; another vector for c.(A p))
   int dot_sq;            // staged kernel: also results[slot + 1] = y . y
-  int stream_nt;         // delta kernel: non-temporal policy on the val / column window loads
   int blk_pub;           // fused dots of the staged / coded / delta kernels: one double-double tree per workgroup (block_publish) instead of one per wave
   int dot_early;         // staged kernels: load dotw[row] before the row block's windows instead of after the row walk
   const long long *stop_seq;   // device-resident loop control (solver_device.hpp); null outside such loops
   long long seq;
-  int fake_gather;       // experiment: coalesced x reads instead of x[col] (WRONG results)
+  int stream_nt;         // always 0 (retired with its option); read by spmv_delta_kernel's window loads, see there
+  int fake_gather;       // always 0 (the experiment it switched is retired); read by spmv_stream_kernel's gather loop, see there
   // dictionary-coded column indices (colcode.hip): col = row + code_tab[code[k]]
   const void *code;          // uint8_t[nnz + pad] or uint16_t[nnz + pad]
   const int32_t *code_tab;   // sorted distinct (column - row) offsets, code_T entries
@@ -61,8 +61,7 @@ struct SpmvArgs {
   const int32_t *desc_ptr;   // [blocks + 1] first escape of every row block
   const uint16_t *desc_pos;  // escape: entry position inside its block
   const int32_t *desc_col;   // escape: column
-  int stage_rows;            // coded / pipelined / delta kernels: rows per block (256, 128, 64 or 32)
-  int max_row;               // pipelined kernel: longest row of the operator (uniform trip count of the row walk)
+  int stage_rows;            // coded / sliced / delta kernels: rows per block (256, 128, 64 or 32)
   // Lanczos epilogue of minres! (sliced kernel only, with the fused dot and dotw = x = v; read only when lz != 0):
   //   y = ((A v + lz_coef[0] v) * lz_coef[1]) + lz_coef[2] r1   (the r1 term when lz_sub_r1), results[slot] = v . y
   // with lz_coef = (lambda, 1 / beta, -beta / oldbeta) in device memory (MinresDevState)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What the long-range links of the banded + random operator cost (round 4): the same band (half width 13, 7 of 8 kept)
-with 0, 1 and 3 random links per row, 10.5 M rows; stream kernel forms x non-temporal matrix stream.  Fractions of 8 TB/s on
+with 0, 1 and 3 random links per row, 10.5 M rows; stream kernel forms.  Fractions of 8 TB/s on
 the algorithmic bytes.  Prints JSON lines."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -14,13 +14,11 @@ def timeit(fn):
     fn(); ctx.sync(); t0 = time.perf_counter()
     for _ in range(reps): fn()
     ctx.sync(); return (time.perf_counter() - t0) / reps
-FORMS = [("stream 8+4 B loads", dict(spmv_kernel=1, spmv_delta=0, spmv_wide=0, spmv_nt=0, spmv_stream_nt=0)),
-         ("stream 8+4 B loads, nt stream", dict(spmv_kernel=1, spmv_delta=0, spmv_wide=0, spmv_nt=1, spmv_stream_nt=0)),
-         ("16 B loads int32", dict(spmv_kernel=1, spmv_delta=0, spmv_wide=1, spmv_nt=0, spmv_stream_nt=0)),
-         ("16 B loads int32, nt stream", dict(spmv_kernel=1, spmv_delta=0, spmv_wide=1, spmv_nt=0, spmv_stream_nt=1)),
-         ("block-delta 8 bit", dict(spmv_kernel=1, spmv_delta=8, spmv_wide=1, spmv_nt=0, spmv_stream_nt=0)),
-         ("block-delta 8 bit, nt stream", dict(spmv_kernel=1, spmv_delta=8, spmv_wide=1, spmv_nt=0, spmv_stream_nt=1)),
-         ("staged rows int32", dict(spmv_kernel=4, spmv_delta=0, spmv_wide=0, spmv_nt=0, spmv_stream_nt=0))]
+FORMS = [("stream 8+4 B loads", dict(spmv_kernel=1, spmv_delta=0, spmv_wide=0, spmv_nt=0)),
+         ("stream 8+4 B loads, nt stream", dict(spmv_kernel=1, spmv_delta=0, spmv_wide=0, spmv_nt=1)),
+         ("16 B loads int32", dict(spmv_kernel=1, spmv_delta=0, spmv_wide=1, spmv_nt=0)),
+         ("block-delta 8 bit", dict(spmv_kernel=1, spmv_delta=8, spmv_wide=1, spmv_nt=0)),
+         ("staged rows int32", dict(spmv_kernel=4, spmv_delta=0, spmv_wide=0, spmv_nt=0))]
 for links in (0, 1, 3):
     ref = None
     for form, opts in FORMS:
