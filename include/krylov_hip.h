@@ -82,7 +82,10 @@ int khip_csr_create(khip_ctx *ctx, int64_t m, int64_t n, int64_t nnz, const void
 /* Distributed form (ref recipe docs/src/custom_workspaces.md:477-586):
  * this rank owns global rows [row0, row0+m) of an n_global-square operator; col[] holds
  * GLOBAL indices.  Requires khip_comm_init on ctx.  Builds the halo plan (needed remote
- * columns, send lists) and remaps columns to [owned | ghost] numbering. */
+ * columns, send lists) and remaps columns to [owned | ghost] numbering.
+ * A product on such a handle gives, whatever kernel form, halo mode and "overlap_halo" setting, the y of the serial stored-order
+ * loop bit for bit on every rank (the vector kernel, "spmv_kernel" = 2: every row within gamma(row length) sum|a_ij x_j|), and
+ * its fused scalars (khip_spmv_dot / _dotw / _dot2) come back with identical bits on all ranks. */
 int khip_csr_create_dist(khip_ctx *ctx, int64_t n_global, int64_t row0, int64_t m, int64_t nnz,
                          const void *rowptr, int rowptr_bits, const int32_t *col,
                          const double *val, int index_base, int on_device, khip_csr **out);

@@ -2,7 +2,8 @@
 
 exact_dot / exact_norm return the correctly rounded value of sum x_i y_i / sqrt(sum x_i^2); dot2_bound is the error bound a
 Dot2-shaped reduction has to meet against it; gen_dot builds ill-conditioned pairs whose large cancelling partners sit where a
-reduction tree is most likely to lose them.  Imported by tests/test_exact_reduction_host.py and tests/test_gpu_reduction_exact.py.
+reduction tree is most likely to lose them; Tally logs and judges one result against them.  Imported by tests/test_exact_reduction_host.py,
+tests/test_gpu_reduction_exact.py and tests/partition_model.py (the partitioned SpMV's fused scalars and row bounds).
 
 Exactness window: every product x_i y_i is 0 or has a magnitude in [2^-969, 2^1000].  Above it the error-free products and
 their sum could overflow; below it the error term of a product (down to 2^-106 of it) is no longer a double.  Inputs outside
@@ -250,3 +251,28 @@ def gen_dot(n, cond, rng, place="waves", y=None, starts=None):
         s = exact_dot(x, y)
     achieved = math.inf if s == 0 else absum(x, y) / abs(float(s))
     return x, y, achieved
+
+
+def ulp(v):
+    return math.ulp(abs(v))
+
+
+class Tally:
+    """Per family: the largest |d - s| / bound, the share of results equal to the exactly rounded value, the conditions."""
+
+    def __init__(self, log, family):
+        self.log, self.family = log, family
+
+    def dot(self, what, d, x, y, cond, n=None):
+        n = x.size if n is None else n
+        s, a = exact_dot(x, y), absum(x, y)
+        bound = dot2_bound(n, s, a)
+        self.log(test="exact_reduction", family=self.family, what=what, n=int(n), cond=float(cond),
+                 ratio=abs(d - s) / bound if bound > 0 else (0.0 if d == s else math.inf), exact=bool(d == s))
+        return abs(d - s) <= bound, (what, n, cond, d, s, bound)
+
+    def sq(self, what, d, x):
+        s = exact_dot(x, x)
+        self.log(test="exact_reduction", family=self.family, what=what, n=int(x.size), cond=1.0,
+                 ratio=abs(d - s) / ulp(s) if s else 0.0, exact=bool(d == s))
+        return abs(d - s) <= ulp(s), (what, x.size, d, s)

@@ -97,6 +97,7 @@ def test_distributed_spmv_and_cg_local_ranks(K, oracle, world, n1):
             c.set_option("overlap_halo", overlap)
             y = A.matvec(c.array(x[r0:r1])).to_host()
             out[f"y{overlap}"] = y
+            out[f"form{overlap}"] = (A.spmv_kernel_choice, A.code_info[0], A.sell_info[0], A.sell_narrow)
             yv = c.empty(r1 - r0)
             out[f"d{overlap}"] = K.spmv_dot(A, c.array(x[r0:r1]), yv)
         c.set_option("overlap_halo", 1)
@@ -114,6 +115,10 @@ def test_distributed_spmv_and_cg_local_ranks(K, oracle, world, n1):
     for rank, out in enumerate(res):
         r0, r1 = starts[rank], starts[rank + 1]
         for overlap in (1, 0):
+            if world in (3, 4):
+                # the form these slabs run under the session's options (tests/conftest.py: spmv_codes = 2): the staged family on
+                # 8-bit diagonal codes in its sliced form, byte-coded words -- not whatever the slab happens to get
+                assert out[f"form{overlap}"] == (4, 8, 1, False), (rank, overlap, out[f"form{overlap}"])
             assert np.array_equal(out[f"y{overlap}"], y_ref[r0:r1]), (rank, overlap)        # bit-identical to the oracle
             assert abs(out[f"d{overlap}"] - d_ref) <= 4 * np.finfo(float).eps * abs(d_ref) + 1e-16 * np.abs(x * y_ref).sum()
         for fused in (2, 1, 0):

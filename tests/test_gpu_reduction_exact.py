@@ -24,6 +24,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import exact_reduction as er  # noqa: E402
+from exact_reduction import Tally, ulp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -45,10 +46,6 @@ def finish_geometry(n, vec, u):
 N_G1, N_GMID, N_G256 = 100003, (1 << 20) + 1, (1 << 25) + (1 << 20) + 1
 
 
-def ulp(v):
-    return math.ulp(abs(v))
-
-
 def _dev(ctx, a, misalign=False):
     if not misalign:
         return ctx.array(a)
@@ -57,27 +54,6 @@ def _dev(ctx, a, misalign=False):
     v.copy_from_host(a)
     v._base = base
     return v
-
-
-class Tally:
-    """Per family: the largest |d - s| / bound, the share of results equal to the exactly rounded value, the conditions."""
-
-    def __init__(self, log, family):
-        self.log, self.family = log, family
-
-    def dot(self, what, d, x, y, cond, n=None):
-        n = x.size if n is None else n
-        s, a = er.exact_dot(x, y), er.absum(x, y)
-        bound = er.dot2_bound(n, s, a)
-        self.log(test="exact_reduction", family=self.family, what=what, n=int(n), cond=float(cond),
-                 ratio=abs(d - s) / bound if bound > 0 else (0.0 if d == s else math.inf), exact=bool(d == s))
-        return abs(d - s) <= bound, (what, n, cond, d, s, bound)
-
-    def sq(self, what, d, x):
-        s = er.exact_dot(x, x)
-        self.log(test="exact_reduction", family=self.family, what=what, n=int(x.size), cond=1.0,
-                 ratio=abs(d - s) / ulp(s) if s else 0.0, exact=bool(d == s))
-        return abs(d - s) <= ulp(s), (what, x.size, d, s)
 
 
 @pytest.fixture
