@@ -34,6 +34,19 @@ int khip_test_set_halo_self(khip_ctx *ctx, int enable);
  * sequence.  out10 = grid dims[3], skewed basis, blocks lower / upper, largest face list, 48-byte records possible,
  * largest row, rows of the largest block rounded up to the wave. */
 int khip_test_ilu_blocks_host(int64_t n, const int64_t *rowptr, const int32_t *col, int mode, int64_t *out10);
+/* test-only: which row path the blocks of the triangular solves take, from the one decision the launch uses.  paths48:
+ * [0..15] lower and [16..31] upper triangle: blocks on the 48-byte records, the 176-byte records, the packed lists; packed
+ * blocks inside a handle that has records (64 local levels or more, or a level wider than the wave); blocks with a row of
+ * more than 16 entries; blocks with more than 1024 face rows; largest face list; largest row; most local levels; widest
+ * local level; rows_cap; dynamic LDS bytes; workgroups launched (0 in the host-only form); blocks.  [32..37] batched
+ * small-level launches and single-level launches of the factorisation, the lower and the upper level solve.  [38] 1 = block
+ * schedule in use, [39] why an attempted one is not (1: LDS, 2: 16-bit slot range), [40] 1 = the create path attempts one
+ * (option, grid or rows-per-level gate), [41] [42] levels of the lower / upper triangle.
+ * khip_test_ilu0_paths: a live operator.  khip_test_ilu_paths_host: host-only, the arguments of khip_test_ilu_blocks_host
+ * plus the value of option ilu_blocks the operator would be created under (3 implies mode 3). */
+int khip_test_ilu0_paths(const khip_operator *op, int64_t *paths48);
+int khip_test_ilu_paths_host(int64_t n, const int64_t *rowptr, const int32_t *col, int mode, int ilu_blocks, int64_t *out10,
+                             int64_t *paths48);
 
 /* test-only, host-only: the rows [row0, row0 + m) of khip_gen_banded_random into host arrays (no device): rowptr_out has m + 1
  * entries; col_out / val_out may be null on a first call that only asks for the row pointers and *nnz_out. */

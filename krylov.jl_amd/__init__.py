@@ -132,6 +132,8 @@ SIGNATURES = {
     "khip_ilu0_set_graph": (_int, [C.POINTER(COperator), _int]),
     "khip_ilu0_block_info": (_int, [C.POINTER(COperator), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_int)]),
     "khip_test_ilu_blocks_host": (_int, [_i64, C.POINTER(_i64), C.POINTER(C.c_int32), _int, C.POINTER(_i64)]),
+    "khip_test_ilu0_paths": (_int, [C.POINTER(COperator), C.POINTER(_i64)]),
+    "khip_test_ilu_paths_host": (_int, [_i64, C.POINTER(_i64), C.POINTER(C.c_int32), _int, _int, C.POINTER(_i64), C.POINTER(_i64)]),
     "khip_spmv_dot": (_int, [_vp, _vp, _vp, _vp, c_double_p]),
     "khip_axpy2_dot": (_int, [_vp, _i64, _dbl, _vp, _vp, _vp, _vp, c_double_p]),
     "khip_waxpy": (_int, [_vp, _i64, _vp, _vp, _dbl, _vp]),
@@ -959,6 +961,32 @@ class SimpleStats:
         return f"SimpleStats(niter={self.niter}, solved={self.solved}, status={self.status!r})"
 
 
+_ILU_PATH_FIELDS = ("fast", "wide", "packed", "packed_pad0", "long_row_blocks", "long_face_blocks", "max_faces", "max_row",
+                    "max_levels", "max_width", "rows_cap", "lds", "workgroups", "blocks")
+
+
+def _ilu_paths_dict(out):
+    """paths48 of khip_test_ilu0_paths / khip_test_ilu_paths_host (include/krylov_hip_test.h) as a dict."""
+    tri = lambda o: {k: int(out[o + i]) for i, k in enumerate(_ILU_PATH_FIELDS)}
+    lev = lambda o: {"batched": int(out[o]), "single": int(out[o + 1])}
+    return {"lower": tri(0), "upper": tri(16), "levels": {"factor": lev(32), "lower": lev(34), "upper": lev(36)},
+            "blocks_in_use": int(out[38]), "fallback": int(out[39]), "attempted": int(out[40]), "nlevels": (int(out[41]), int(out[42]))}
+
+
+def ilu_paths_host(rowptr, col, ilu_blocks=1, mode=1):
+    """Test-only, no device: what Ilu0.path_info() would report for an operator with this CSR pattern created under option
+    ilu_blocks (workgroups = 0: it depends on the device), plus the fields of khip_test_ilu_blocks_host under "analysis"."""
+    rp = np.ascontiguousarray(rowptr, dtype=np.int64)
+    ci = np.ascontiguousarray(col, dtype=np.int32)
+    out10, out48 = (_i64 * 10)(), (_i64 * 48)()
+    _ck(lib().khip_test_ilu_paths_host(len(rp) - 1, rp.ctypes.data_as(C.POINTER(_i64)), ci.ctypes.data_as(C.POINTER(C.c_int32)), mode,
+                                       ilu_blocks, out10, out48))
+    d = _ilu_paths_dict(out48)
+    d["analysis"] = dict(dims=tuple(out10[0:3]), skew=out10[3], nb=(out10[4], out10[5]), max_ext=out10[6], rec_ok=out10[7],
+                         max_row=out10[8], rows_cap=out10[9])
+    return d
+
+
 class Ilu0:
     """ILU(0) of A on its own pattern as the operator y = U \\ (L \\ x); for SPD A this is IC(0).  Usable as the
     M / N argument of cg_ / gmres_ / bicgstab_ (the reference's ic02 / ilu02 recipes, docs/src/gpu.md:74-163)."""
@@ -989,6 +1017,15 @@ class Ilu0:
         dims, nb, failed = (_i64 * 3)(), _i64(), _int()
         _ck(lib().khip_ilu0_block_info(C.byref(self.op), dims, C.byref(nb), C.byref(failed)))
         return tuple(dims), nb.value, failed.value
+
+    def path_info(self):
+        """Test-only: which row path the blocks of the two block solves take ("lower" / "upper": blocks on the fast, wide and
+        packed path, packed ones inside a handle with records, blocks with rows > 16 entries or > 1024 face rows, the largest
+        face list / row / local level count / local level, rows_cap, LDS bytes, workgroups launched, blocks) and how the level
+        schedule is launched ("levels": batched small-level launches and single-level launches per kind)."""
+        out = (_i64 * 48)()
+        _ck(lib().khip_test_ilu0_paths(C.byref(self.op), out))
+        return _ilu_paths_dict(out)
 
     def values(self):
         """Factor values on A's pattern (host copy)."""

@@ -201,6 +201,18 @@ struct IluBlockHdr {
   int32_t pad;
 };
 
+// Path report of one triangle (test exports khip_test_ilu0_paths / khip_test_ilu_paths_host)
+enum {
+  kPathFast = 0, kPathWide, kPathPacked,     // blocks on the 48-byte records, the 176-byte records, the packed entry lists
+  kPathPackedPad,                            // ... of the packed ones: in a handle that has records (the block's pad is 0)
+  kPathLongRow,                              // blocks with a row of more than 16 entries
+  kPathLongFaces,                            // blocks with more than 1024 face rows
+  kPathMaxFaces, kPathMaxRow, kPathMaxLevels, kPathMaxWidth,      // largest face list, row, local level count, local level
+  kPathRowsCap, kPathLds, kPathGrid, kPathBlocks,
+  kIluPathFields = 16
+};
+enum { kIluFallbackNone = 0, kIluFallbackLds = 1, kIluFallbackRange = 2 };
+
 struct IluBlkArgs {
   const IluBlockHdr *hdr;
   const int32_t *row_gid;              // [n]
@@ -550,7 +562,11 @@ struct khip_ilu0 {
     int epoch = 0;
     unsigned ticket_base = 0;
     size_t lds = 0;
+    int64_t paths[kIluPathFields] = {0};       // which row path its blocks take (khip_test_ilu0_paths)
   } blk_lo, blk_up;
+  bool blk_attempted = false;
+  int64_t blk_fallback_lds[2] = {0, 0};      // ... and the LDS bytes the two triangles would have needed (kIluFallbackLds)
+  int blk_fallback = 0;                      // why a block schedule that was attempted is not in use (kIluFallback...)
   int *blk_fail = nullptr;
   int *blk_fail_host = nullptr, *blk_fail_host_dev = nullptr;   // pinned mirror of "a wait gave up" and its device address
   int64_t grid_dims[3] = {0, 0, 0};          // detected grid (0: none, level scheduling)
@@ -569,29 +585,43 @@ IluView view_of(const khip_ilu0 *P) { return IluView{P->A->col, P->row_lo, P->di
 
 unsigned grid_for(int64_t rows) { return (unsigned)((rows + kIluBlock - 1) / kIluBlock); }
 
+// The launches of one triangle's level schedule: a run of at least two consecutive small levels (<= kIluBlock rows each) is one
+// single-workgroup launch, every other level its own.  on_run(l, e) gets the levels [l, e) of a run, on_level(l) a single level.
+template <typename OnRun, typename OnLevel>
+void for_level_launches(const std::vector<int64_t> &lvl, OnRun on_run, OnLevel on_level) {
+  const int nl = (int)lvl.size() - 1;
+  int l = 0;
+  while (l < nl) {
+    int e = l;
+    while (e < nl && lvl[e + 1] - lvl[e] <= kIluBlock) ++e;
+    if (e - l >= 2) {
+      on_run(l, e);
+      l = e;
+      continue;
+    }
+    on_level(l);
+    ++l;
+  }
+}
+
 // all levels of one triangle: runs of small levels in one single-workgroup launch, every other level its own launch
 template <int KIND>
 int enqueue_levels(khip_ilu0 *P, const std::vector<int64_t> &lvl, const int64_t *d_lvl, const int32_t *perm, const double *x,
                    double *y) {
   khip_ctx *ctx = P->ctx;
   const IluView v = view_of(P);
-  const int nl = (int)lvl.size() - 1;
-  int l = 0;
-  while (l < nl) {
-    int e = l;
-    while (e < nl && lvl[e + 1] - lvl[e] <= kIluBlock) ++e;
-    if (e - l >= 2) {                                  // a run of at least two small levels
-      hipLaunchKernelGGL((ilu_small_levels_kernel<KIND>), dim3(1), dim3(kIluBlock), 0, ctx->stream, v, perm, d_lvl, l, e, x, y,
-                         P->bad_row);
-      l = e;
-      continue;
-    }
-    const int64_t lo = lvl[l], hi = lvl[l + 1];
-    if (KIND == 0) hipLaunchKernelGGL(ilu0_factor_level_kernel, dim3(grid_for(hi - lo)), dim3(kIluBlock), 0, ctx->stream, v, perm, lo, hi, P->bad_row);
-    else if (KIND == 1) hipLaunchKernelGGL(trsv_lower_level_kernel, dim3(grid_for(hi - lo)), dim3(kIluBlock), 0, ctx->stream, v, perm, lo, hi, x, y);
-    else hipLaunchKernelGGL(trsv_upper_level_kernel, dim3(grid_for(hi - lo)), dim3(kIluBlock), 0, ctx->stream, v, perm, lo, hi, y);
-    ++l;
-  }
+  for_level_launches(
+      lvl,
+      [&](int l, int e) {
+        hipLaunchKernelGGL((ilu_small_levels_kernel<KIND>), dim3(1), dim3(kIluBlock), 0, ctx->stream, v, perm, d_lvl, l, e, x, y,
+                           P->bad_row);
+      },
+      [&](int l) {
+        const int64_t lo = lvl[l], hi = lvl[l + 1];
+        if (KIND == 0) hipLaunchKernelGGL(ilu0_factor_level_kernel, dim3(grid_for(hi - lo)), dim3(kIluBlock), 0, ctx->stream, v, perm, lo, hi, P->bad_row);
+        else if (KIND == 1) hipLaunchKernelGGL(trsv_lower_level_kernel, dim3(grid_for(hi - lo)), dim3(kIluBlock), 0, ctx->stream, v, perm, lo, hi, x, y);
+        else hipLaunchKernelGGL(trsv_upper_level_kernel, dim3(grid_for(hi - lo)), dim3(kIluBlock), 0, ctx->stream, v, perm, lo, hi, y);
+      });
   KHIP_CHECK_HIP(hipGetLastError());
   return KHIP_OK;
 }
@@ -791,6 +821,7 @@ struct HostBlocks {            // what the analysis of one triangle produces (ho
   std::vector<uint16_t> row_eptr, lvl, ent_slot;
   std::vector<unsigned long long> rec_meta;
   bool rec_ok = true;
+  bool range_fail = false;      // a block does not fit the 16-bit slot / entry range
   int64_t nb = 0;
   int max_ent = 0, max_ext = 0, max_lvl = 0, max_row_ent = 0, rows_cap = kBlkRows, rc = KHIP_OK;
 };
@@ -1000,11 +1031,77 @@ int analyse_blocks(const HostPattern &H, const Partition &part, bool upper, Host
     }
     for (int32_t k = h.ext0; k < h.ext0 + h.next; ++k) ext_mark[(size_t)ext_gid[(size_t)k]] = -1;
     for (int k = 0; k < nr; ++k) lpos[(size_t)sorted[(size_t)k]] = -1;
-    if (nr > RC || ne > 60000 || RC + h.next > 65535) return KHIP_ERR_INVALID;
+    if (nr > RC || ne > 60000 || RC + h.next > 65535) { hb.range_fail = true; return KHIP_ERR_INVALID; }
     max_ent = std::max(max_ent, ne); max_ext = std::max(max_ext, h.next); max_lvl = std::max(max_lvl, nl);
   }
   hb.nb = nb; hb.max_ent = max_ent; hb.max_ext = max_ext; hb.max_lvl = max_lvl;
   return KHIP_OK;
+}
+
+// Which row path the blocks of one triangle take, and the LDS layout that follows -- the one decision behind the launch
+// (upload_blocks) and behind the host-only report (khip_test_ilu_paths_host).
+//   rec_ok: 48-byte records (every row <= 3 entries, every face list within the fixed ext slots; not with ilu_blocks = 2),
+//   wide:   176-byte records (every row <= 16 entries, slots in range; not with ilu_blocks = 2),
+//   a block whose pad is 0 (64 local levels or more, or a level wider than the wave) takes the packed lists in either case.
+struct IluPathPlan {
+  bool rec_ok = false, wide = false, fits = false;
+  int max_ent = 0, max_ext = 0;
+  size_t lds = 0;
+};
+constexpr size_t kIluLdsLimit = (size_t)150 * 1024;
+
+IluPathPlan plan_paths(const HostBlocks &hb, bool upper, int ilu_blocks) {
+  IluPathPlan p;
+  p.rec_ok = hb.rec_ok;
+  p.max_ent = hb.max_ent;
+  p.max_ext = hb.max_ext;
+  const int max_lvl = hb.max_lvl;
+  if (p.max_ext > kRecExtCap - 2 || ilu_blocks == 2) p.rec_ok = false;      // ilu_blocks = 2: packed lists only (tests)
+  const int RC = hb.rows_cap;
+  p.wide = !p.rec_ok && ilu_blocks != 2 && hb.max_row_ent <= 16 && (size_t)RC + p.max_ext + 2 < 65535;
+  if (p.wide) {
+    p.max_ent = std::max(p.max_ent, RC * kWideDoubles);             // the wide records share the LDS region of the packed entries
+    p.max_ext += 2;                                                 // ... and the y array gets a 0.0 and a dump slot behind the faces
+  }
+  if (p.rec_ok) {
+    p.max_ent = std::max(p.max_ent, RC * kRecDoubles);              // the records share the LDS region of the packed entries
+    p.max_ext = kRecExtCap;                                         // ... and the y array has its fixed 0.0 and dump slots
+  }
+  p.lds = sizeof(double) * ((size_t)RC + p.max_ext + 1 + RC + (upper ? RC : 0) + p.max_ent) +
+          sizeof(uint16_t) * ((size_t)((p.max_ent + 3) & ~3) + RC + 2 + ((max_lvl + 2 + 1) & ~1)) + sizeof(int32_t) * RC;
+  p.fits = p.lds <= kIluLdsLimit;
+  return p;
+}
+
+// the path report of one triangle under a plan (out: kIluPathFields values; kPathGrid is the launcher's to fill)
+void count_paths(const HostBlocks &hb, const IluPathPlan &plan, int64_t *out) {
+  for (int k = 0; k < kIluPathFields; ++k) out[k] = 0;
+  for (int64_t t = 0; t < hb.nb; ++t) {
+    const IluBlockHdr &h = hb.hdr[(size_t)t];
+    const bool fast = plan.rec_ok && h.pad != 0, wide = !fast && plan.wide && h.pad != 0;
+    out[fast ? kPathFast : wide ? kPathWide : kPathPacked]++;
+    if (!fast && !wide && (plan.rec_ok || plan.wide)) out[kPathPackedPad]++;
+    int row_max = 0, width_max = 0;
+    const uint16_t *ep = hb.row_eptr.data() + (size_t)h.row0 + (size_t)t;
+    for (int r = 0; r < h.nrows; ++r) row_max = std::max(row_max, (int)ep[r + 1] - (int)ep[r]);
+    const uint16_t *lv = hb.lvl.data() + (size_t)h.lvl0;
+    for (int l = 0; l < h.nlvl; ++l) width_max = std::max(width_max, (int)lv[l + 1] - (int)lv[l]);
+    if (row_max > 16) out[kPathLongRow]++;
+    if (h.next > 1024) out[kPathLongFaces]++;
+    out[kPathMaxFaces] = std::max<int64_t>(out[kPathMaxFaces], h.next);
+    out[kPathMaxRow] = std::max<int64_t>(out[kPathMaxRow], row_max);
+    out[kPathMaxLevels] = std::max<int64_t>(out[kPathMaxLevels], h.nlvl);
+    out[kPathMaxWidth] = std::max<int64_t>(out[kPathMaxWidth], width_max);
+  }
+  out[kPathRowsCap] = hb.rows_cap;
+  out[kPathLds] = (int64_t)plan.lds;
+  out[kPathBlocks] = hb.nb;
+}
+
+// the launches of a level schedule: out[0] batched runs of small levels, out[1] single levels
+void count_level_launches(const std::vector<int64_t> &lvl, int64_t *out) {
+  out[0] = out[1] = 0;
+  for_level_launches(lvl, [&](int, int) { out[0]++; }, [&](int) { out[1]++; });
 }
 
 // uploads the analysis of one triangle and builds what needs the factor values (the numeric factorisation is complete)
@@ -1015,25 +1112,16 @@ int upload_blocks(khip_ilu0 *P, bool upper, HostBlocks &hb, khip_ilu0::Blocks &B
   std::vector<int32_t> &row_gid = hb.row_gid, &ext_gid = hb.ext_gid, &dep = hb.dep, &src = hb.src, &diag_src = hb.diag_src, &rec_src = hb.rec_src;
   std::vector<uint16_t> &row_eptr = hb.row_eptr, &lvl = hb.lvl, &ent_slot = hb.ent_slot;
   std::vector<unsigned long long> &rec_meta = hb.rec_meta;
-  bool rec_ok = hb.rec_ok;
-  int max_ent = hb.max_ent, max_ext = hb.max_ext, max_lvl = hb.max_lvl;
-  if (max_ext > kRecExtCap - 2 || ctx->tune.ilu_blocks == 2) rec_ok = false;      // ilu_blocks = 2: packed lists only (tests)
+  const IluPathPlan plan = plan_paths(hb, upper, ctx->tune.ilu_blocks);
+  const bool rec_ok = plan.rec_ok;
+  const int max_ent = plan.max_ent, max_ext = plan.max_ext, max_lvl = hb.max_lvl;
   const int RC = hb.rows_cap;
-  const bool wide = !rec_ok && ctx->tune.ilu_blocks != 2 && hb.max_row_ent <= 16 && (size_t)RC + max_ext + 2 < 65535;
-  if (wide) {
-    max_ent = std::max(max_ent, RC * kWideDoubles);                 // the wide records share the LDS region of the packed entries
-    max_ext += 2;                                                   // ... and the y array gets a 0.0 and a dump slot behind the faces
-    B.want_wide = true;
-  }
-  if (rec_ok) {
-    max_ent = std::max(max_ent, RC * kRecDoubles);                  // the records share the LDS region of the packed entries
-    max_ext = kRecExtCap;                                           // ... and the y array has its fixed 0.0 and dump slots
-  }
+  B.want_wide = plan.wide;
   B.nb = (int)nb; B.max_ent = max_ent; B.max_ext = max_ext; B.max_lvl = max_lvl;
   B.rows_cap = RC;
-  B.lds = sizeof(double) * ((size_t)RC + max_ext + 1 + RC + (upper ? RC : 0) + max_ent) +
-          sizeof(uint16_t) * ((size_t)((max_ent + 3) & ~3) + RC + 2 + ((max_lvl + 2 + 1) & ~1)) + sizeof(int32_t) * RC;
-  if (B.lds > (size_t)150 * 1024) return KHIP_ERR_INVALID;
+  B.lds = plan.lds;
+  if (!plan.fits) { P->blk_fallback = kIluFallbackLds; return KHIP_ERR_INVALID; }
+  count_paths(hb, plan, B.paths);
   bool all_fast = rec_ok;                         // every block on the row-record path: the packed entry arrays are not needed
   for (const IluBlockHdr &hh : hdr) all_fast = all_fast && hh.pad != 0;
   int rc = upload(ctx, hdr, &B.hdr);
@@ -1069,6 +1157,8 @@ int upload_blocks(khip_ilu0 *P, bool upper, HostBlocks &hb, khip_ilu0::Blocks &B
   int per_cu = (int)((size_t)(160 * 1024) / std::max<size_t>(B.lds, 1));
   per_cu = std::max(1, std::min(per_cu, 16));
   B.grid = (int)std::min<int64_t>(nb, (int64_t)ctx->num_cu * per_cu);
+  if (ctx->tune.ilu_grid > 0) B.grid = std::min(B.grid, ctx->tune.ilu_grid);      // tests: few workgroups, many blocks each (it only lowers the grid)
+  B.paths[kPathGrid] = B.grid;
   return KHIP_OK;
 }
 
@@ -1187,6 +1277,7 @@ int khip_ilu0_create(khip_ctx *ctx, const khip_csr *A, khip_operator *op_out) {
     const long avail_pages = sysconf(_SC_AVPHYS_PAGES), page = sysconf(_SC_PAGESIZE);
     const bool host_ok = avail_pages <= 0 || page <= 0 || (double)avail_pages * (double)page > 200.0 * (double)n;
     if (host_ok && (grid || (n >= 4096 && nlev > 0 && 2 * n / nlev >= 32))) {
+      P->blk_attempted = true;
       KHIP_CHECK_HIP(hipMalloc(&P->blk_fail, sizeof(int)));
       KHIP_CHECK_HIP(hipMemsetAsync(P->blk_fail, 0, sizeof(int), ctx->stream));
       if (hipHostMalloc(reinterpret_cast<void **>(&P->blk_fail_host), sizeof(int), hipHostMallocMapped) == hipSuccess) {
@@ -1209,6 +1300,15 @@ int khip_ilu0_create(khip_ctx *ctx, const khip_csr *A, khip_operator *op_out) {
       analyse(false, hlo);
       tup.join();
       int rb = hlo.rc != KHIP_OK ? hlo.rc : hup.rc;
+      if (hlo.range_fail || hup.range_fail) P->blk_fallback = kIluFallbackRange;
+      if (rb == KHIP_OK) {                     // both triangles must fit in LDS (the report names what either would have needed)
+        const IluPathPlan pl = plan_paths(hlo, false, ctx->tune.ilu_blocks), pu = plan_paths(hup, true, ctx->tune.ilu_blocks);
+        if (!pl.fits || !pu.fits) {
+          P->blk_fallback = kIluFallbackLds;
+          P->blk_fallback_lds[0] = (int64_t)pl.lds; P->blk_fallback_lds[1] = (int64_t)pu.lds;
+          rb = KHIP_ERR_INVALID;
+        }
+      }
       if (rb == KHIP_OK) rb = upload_blocks(P, false, hlo, P->blk_lo);
       if (rb == KHIP_OK) rb = pack_block_values(P, P->blk_lo, hlo.src, hlo.diag_src, false);
       if (rb == KHIP_OK) rb = upload_blocks(P, true, hup, P->blk_up);
@@ -1273,7 +1373,10 @@ int khip_debug_ilu_trace(unsigned long long *out512) {
 // sequence), 3 = level sequence.  out: [0..2] grid dims (0 if none), [3] 1 = skewed basis, [4] blocks lower, [5] blocks upper,
 // [6] largest face list, [7] 1 = 48-byte records possible (lower), [8] largest row (entries in a triangle), [9] rows_cap.
 // Returns KHIP_ERR_INVALID if a block would depend on a later one (the analysis checks every dependency).
-int khip_test_ilu_blocks_host(int64_t n, const int64_t *rowptr, const int32_t *colidx, int mode, int64_t *out10) {
+// ... and with paths48 (khip_test_ilu_paths_host) what khip_test_ilu0_paths reports for a live operator created under option
+// ilu_blocks, from the same plan_paths / count_paths / count_level_launches the create path runs.
+static int ilu_host_analysis(int64_t n, const int64_t *rowptr, const int32_t *colidx, int mode, int ilu_blocks, int64_t *out10,
+                             int64_t *paths48) {
   KHIP_REQUIRE(n > 0 && rowptr && colidx && out10, "test_ilu_blocks_host: bad arguments");
   const int64_t nnz = rowptr[n];
   std::vector<int32_t> col(colidx, colidx + nnz), row_lo((size_t)n), diag((size_t)n), row_hi((size_t)n), lev_lo((size_t)n), lev_up((size_t)n);
@@ -1304,6 +1407,16 @@ int khip_test_ilu_blocks_host(int64_t n, const int64_t *rowptr, const int32_t *c
   int64_t dims[3] = {0, 0, 0};
   int skew[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   const bool grid = mode != 3 && detect_grid(H, dims, skew);
+  if (paths48) {
+    for (int k = 0; k < 48; ++k) paths48[k] = 0;
+    count_level_launches(lvl_lo, paths48 + 32);                       // the factorisation runs the lower triangle's levels
+    count_level_launches(lvl_lo, paths48 + 34);
+    count_level_launches(lvl_up, paths48 + 36);
+    const int64_t nlev = (int64_t)nlev_lo + nlev_up;
+    paths48[40] = ilu_blocks != 0 && (grid || (n >= 4096 && nlev > 0 && 2 * n / nlev >= 32));      // the gate of khip_ilu0_create
+    paths48[41] = nlev_lo;
+    paths48[42] = nlev_up;
+  }
   for (int k = 0; k < 3; ++k) out10[k] = grid ? dims[k] : 0;
   out10[3] = grid && skew[1] != 0;
   HostBlocks hb[2];
@@ -1311,6 +1424,12 @@ int khip_test_ilu_blocks_host(int64_t n, const int64_t *rowptr, const int32_t *c
     Partition part;
     int rc = grid ? make_grid_partition(H, dims, skew, up != 0, part) : make_level_partition(n, up ? perm_up : perm_lo, up ? lvl_up : lvl_lo, part);
     if (rc == KHIP_OK) rc = analyse_blocks(H, part, up != 0, hb[up]);
+    if (rc != KHIP_OK && paths48 && hb[up].range_fail) {              // khip_ilu0_create keeps the level schedule
+      paths48[39] = kIluFallbackRange;
+      for (int k = 0; k < 3; ++k) out10[k] = 0;
+      for (int k = 3; k < 10; ++k) out10[k] = 0;
+      return KHIP_OK;
+    }
     if (rc != KHIP_OK) return rc;
     // every row in exactly one block
     std::vector<char> seen((size_t)n, 0);
@@ -1319,6 +1438,53 @@ int khip_test_ilu_blocks_host(int64_t n, const int64_t *rowptr, const int32_t *c
   }
   out10[4] = hb[0].nb; out10[5] = hb[1].nb; out10[6] = std::max(hb[0].max_ext, hb[1].max_ext); out10[7] = hb[0].rec_ok;
   out10[8] = std::max(hb[0].max_row_ent, hb[1].max_row_ent); out10[9] = hb[0].rows_cap;
+  if (paths48 && paths48[40]) {
+    IluPathPlan plan[2];
+    for (int up = 0; up < 2; ++up) plan[up] = plan_paths(hb[up], up != 0, ilu_blocks);
+    if (!plan[0].fits || !plan[1].fits) {
+      paths48[39] = kIluFallbackLds;
+      paths48[kPathLds] = (int64_t)plan[0].lds;                       // what did not fit
+      paths48[16 + kPathLds] = (int64_t)plan[1].lds;
+      for (int k = 0; k < 3; ++k) out10[k] = 0;
+    } else {
+      for (int up = 0; up < 2; ++up) count_paths(hb[up], plan[up], paths48 + 16 * up);
+      paths48[38] = 1;
+    }
+  }
+  return KHIP_OK;
+}
+
+int khip_test_ilu_blocks_host(int64_t n, const int64_t *rowptr, const int32_t *colidx, int mode, int64_t *out10) {
+  return ilu_host_analysis(n, rowptr, colidx, mode, 1, out10, nullptr);
+}
+
+int khip_test_ilu_paths_host(int64_t n, const int64_t *rowptr, const int32_t *colidx, int mode, int ilu_blocks, int64_t *out10,
+                             int64_t *paths48) {
+  KHIP_REQUIRE(paths48, "test_ilu_paths_host: bad arguments");
+  return ilu_host_analysis(n, rowptr, colidx, ilu_blocks == 3 ? 3 : mode, ilu_blocks, out10, paths48);
+}
+
+// Which row path the blocks of a live operator take and how its level schedule is launched.  paths48: [0..15] lower triangle,
+// [16..31] upper triangle (kPath... above: blocks on the fast / wide / packed path, packed ones inside a handle with records,
+// blocks with a row > 16 entries, with > 1024 face rows, largest face list / row / local level count / local level, rows_cap,
+// dynamic LDS bytes, workgroups launched, blocks), [32..37] batched and single-level launches of the factorisation, the lower
+// and the upper level solve, [38] 1 = the block schedule is in use, [39] why an attempted one is not (1 LDS, 2 slot range),
+// [40] 1 = the create path attempted one, [41] [42] levels lower / upper.
+int khip_test_ilu0_paths(const khip_operator *op, int64_t *paths48) {
+  KHIP_REQUIRE(op && op->apply == ilu0_apply && op->self && paths48, "test_ilu0_paths: not an ILU(0) operator");
+  const khip_ilu0 *P = static_cast<const khip_ilu0 *>(op->self);
+  for (int k = 0; k < 48; ++k) paths48[k] = 0;
+  if (P->use_blocks)
+    for (int k = 0; k < kIluPathFields; ++k) { paths48[k] = P->blk_lo.paths[k]; paths48[16 + k] = P->blk_up.paths[k]; }
+  count_level_launches(P->lvl_lo, paths48 + 32);
+  count_level_launches(P->lvl_lo, paths48 + 34);
+  count_level_launches(P->lvl_up, paths48 + 36);
+  paths48[38] = P->use_blocks;
+  paths48[39] = P->use_blocks ? 0 : P->blk_fallback;
+  if (paths48[39] == kIluFallbackLds) { paths48[kPathLds] = P->blk_fallback_lds[0]; paths48[16 + kPathLds] = P->blk_fallback_lds[1]; }
+  paths48[40] = P->blk_attempted;
+  paths48[41] = (int64_t)P->lvl_lo.size() - 1;
+  paths48[42] = (int64_t)P->lvl_up.size() - 1;
   return KHIP_OK;
 }
 

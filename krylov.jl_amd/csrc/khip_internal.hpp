@@ -109,6 +109,7 @@ struct Tuning {
   int hist_window = 1 << 14;   // device-resident loops: residual-history entries kept on the device between drains
   int red_u = 0;            // reductions: 16-byte accesses per lane (0 auto: 4 for long vectors, else 1)
   int ilu_blocks = 1;        // ILU(0) solves: block schedule where the pattern is a structured grid (0: level scheduling always; 2: block schedule on packed entry lists only, no row records; 3: blocks from the level-sorted row sequence even where a grid is recognised)
+  int ilu_grid = 0;          // ILU(0) block solves: > 0 caps the workgroups of a launch (tests: few workgroups, each takes many blocks in sequence); read at create
   int panel_multi_tiles = 2; // X += sum V_i Y_i: factor blocks in LDS, this many 16-row tiles per wave (0 = the one-tile kernel that re-reads the factors per tile)
   int gmres_sstep = 4;      // gmres! variant 2: inner iterations per block of the s-step form (1..8)
   int panel_nt = 0;         // fused Gram-Schmidt kernel: non-temporal accesses to the panels (1: panels of at least nt_min_elems doubles, 2: always); measured no effect (3.263 vs 3.263 ms per three-panel sweep), off

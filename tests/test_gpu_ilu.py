@@ -181,7 +181,9 @@ def test_ilu0_block_schedule_bit_identical(K, ctx, oracle, gen, args):
     """Structured grids (>= 4096 rows) take the block schedule (csrc/ilu.hip: ilu_block_solve_kernel): same y, bit for bit,
     as the level-scheduled kernels and as the oracle's serial loops -- whole and partial 8 x 8 x 8 blocks, a 2-D grid, an
     unsymmetric pattern, and the 27-point stencil, whose lower triangle reaches (x + 1, y - 1, z) and (x + 1, y + 1, z - 1): its
-    blocks are cubes in the skewed basis (x + y + 2 z, y + z, z) and run the general path (13 entries per row)."""
+    blocks are cubes in the skewed basis (x + y + 2 z, y + z, z) and run on the wide (176-byte) row records (13 entries per row,
+    22 local levels of at most 48 rows per cube: path_info() shows every block on the wide path, none on the packed lists); the
+    5- / 7-point operators run on the 48-byte records.  Option ilu_blocks = 2 puts every block on the packed lists."""
     A = getattr(oracle, gen)(*args)
     ref = oracle.Ilu0(A)
     dA = _upload(K, ctx, A)
@@ -191,6 +193,14 @@ def test_ilu0_block_schedule_bit_identical(K, ctx, oracle, gen, args):
     if gen == "poisson3d":
         want = tuple(args) if len(args) == 3 else (args[0],) * 3
         assert dims == want
+    paths = P.path_info()
+    for tri in ("lower", "upper"):
+        t = paths[tri]
+        assert t["blocks"] == nb and t["packed"] == 0 and t["packed_pad0"] == 0, t
+        if gen == "stencil27_unsym":
+            assert t["wide"] == nb and t["max_row"] == 13 and t["max_levels"] < 64 and t["max_width"] <= 64, t
+        else:
+            assert t["fast"] == nb and t["max_row"] <= 3 and t["max_faces"] <= 254, t
     ctx.set_option("ilu_blocks", 0)
     try:
         Pl = K.Ilu0(dA)                      # level scheduling on the same handle
@@ -219,13 +229,14 @@ def test_ilu0_block_schedule_bit_identical(K, ctx, oracle, gen, args):
         Pp(dx, dy)
         assert np.array_equal(dy.to_host(), ref.solve(x))
         assert Pp.block_info()[1] > 0 and Pp.block_info()[2] == 0
+        assert all(Pp.path_info()[tri]["packed"] == Pp.block_info()[1] for tri in ("lower", "upper"))
 
 
 @pytest.mark.parametrize("blocks", [1, 2])
 def test_ilu0_block_schedule_without_a_grid(K, ctx, oracle, blocks):
     """A pattern that is no grid in natural ordering (a random symmetric permutation of one): the blocks are pieces of the
-    level-sorted row sequence (dims 0, 0, 0 but blocks > 0) -- on row records and on the packed lists -- and y is still the
-    oracle's, bit for bit.  A chain (levels of one row) keeps level scheduling: see the next test."""
+    level-sorted row sequence (dims 0, 0, 0 but blocks > 0) -- on the wide (176-byte) row records, since the permutation leaves up
+    to 6 of a row's entries in one triangle, and on the packed lists -- and y is still the oracle's, bit for bit.  A chain (levels of one row) keeps level scheduling: see the next test."""
     import scipy.sparse as sp
     A = oracle.poisson3d(16)
     S = A.to_scipy().tocsr()
@@ -240,6 +251,9 @@ def test_ilu0_block_schedule_without_a_grid(K, ctx, oracle, blocks):
         ctx.set_option("ilu_blocks", 1)
     dims, nb, failed = P.block_info()
     assert dims == (0, 0, 0) and nb > 0 and failed == 0, (dims, nb, failed)
+    for tri in ("lower", "upper"):                   # path_info(): every block on the 176-byte records / on the packed lists
+        t = P.path_info()[tri]
+        assert t["wide" if blocks == 1 else "packed"] == t["blocks"] > 0 and t["max_row"] == 6, t
     ref = oracle.Ilu0(Ap)
     assert np.array_equal(P.values(), ref.lu)
     for seed in range(3):
@@ -280,6 +294,9 @@ def test_ilu0_block_schedule_general_rows(K, ctx, oracle, dims, records):
         ctx.set_option("ilu_blocks", 1)
     got_dims, nb, failed = P.block_info()
     assert got_dims == dims and nb > 0 and failed == 0, (got_dims, nb, failed)
+    for tri in ("lower", "upper"):                   # path_info(): the wide records (rows of 6 / 4 entries) or the packed lists
+        t = P.path_info()[tri]
+        assert t["wide" if records == 1 else "packed"] == nb and t["max_row"] == (6 if n3 > 1 else 4), t
     assert np.array_equal(P.values(), ref.lu)
     rng = np.random.default_rng(n1)
     for _ in range(2):
