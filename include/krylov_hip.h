@@ -55,7 +55,12 @@ int   khip_ctx_destroy(khip_ctx *ctx);
 int   khip_ctx_sync(khip_ctx *ctx);
 void *khip_ctx_stream(khip_ctx *ctx);
 /* tuning / behaviour knobs, see DESIGN.md ("spmv_rows", "spmv_vec", "spmv_nt", "spmv_xcd",
- * "compensated", "blas1_blocks", ...).  Unknown key -> KHIP_ERR_INVALID. */
+ * "compensated", "blas1_blocks", ...).  Unknown key -> KHIP_ERR_INVALID.
+ * "cg_defer_x" (default 1): the device-resident loop of khip_cg_solve (fused = 2, variant 0) updates x every second
+ * iteration through a second direction buffer of n doubles that the workspace allocates on first use (adopted workspaces
+ * too; it is not one of the workspace's named vectors and khip_cg_workspace_bytes does not count it) -- 4n fewer bytes
+ * per iteration, every vector, the history and the stats bit-identical.  0: x every iteration, no extra buffer.  When the
+ * buffer cannot be allocated the solve runs as with 0. */
 int   khip_ctx_set_option(khip_ctx *ctx, const char *key, int value);
 int   khip_ctx_get_option(khip_ctx *ctx, const char *key, int *value);
 

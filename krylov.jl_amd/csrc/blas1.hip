@@ -519,6 +519,82 @@ int launch_cg_update_dev(khip_ctx *ctx, int64_t n, const void *cg_state_dev, lon
   return KHIP_OK;
 }
 
+// The same update with x touched every SECOND iteration (cg_device_loop, ctx option cg_defer_x): p2 holds the direction the
+// light iteration formed, p the one before it.  Every expression is the one cg_update_dev_kernel evaluates, on the same
+// operands in the same order, so x and the directions keep their bits.
+//   LIGHT  p2 = fma(1, r, beta p)                                       2R + 1W = 24n   (solved: x = fma(alpha, p, x) instead)
+//   HEAVY  x = fma(alpha, p2, fma(alpha_prev, p, x)) ; p = fma(1, r, beta p2)   4R + 2W = 48n   (solved: p = p2, the direction
+//          cg_update_dev_kernel would have left in p)
+//   FLUSH  x = fma(a, p, x) ; p = p2 with a = alpha_prev or alpha (`prev`): once, after a loop that ended on a light iteration
+template <int MODE>
+__device__ __forceinline__ void cg_defer_elem(bool solved, double a0, double a, double b, double rv, double pv, double qv,
+                                              double xv, double &xo, double &po) {
+  if (MODE == CGD_LIGHT) { xo = fma(a, pv, xv); po = fma(1.0, rv, b * pv); }
+  else if (MODE == CGD_HEAVY) { xo = fma(a, qv, fma(a0, pv, xv)); po = solved ? qv : fma(1.0, rv, b * qv); }
+  else { xo = fma(a, pv, xv); po = qv; }
+}
+
+template <int MODE, int VEC, bool NT>
+__global__ __launch_bounds__(kBlock) void cg_defer_kernel(int64_t n, const CgDevState *st, long long seq, int prev,
+                                                          const double *r, double *p, double *p2, double *x) {
+  using T = typename VecT<VEC>::type;
+  if (MODE != CGD_FLUSH && seq >= st->stop_seq) return;
+  const double a0 = st->alpha_prev, a = (MODE == CGD_FLUSH && prev) ? a0 : st->alpha, b = st->beta;
+  const bool solved = MODE != CGD_FLUSH && st->solved != 0;
+  const bool rd_q = MODE != CGD_LIGHT, rd_x = MODE != CGD_LIGHT || solved, rd_r = MODE != CGD_FLUSH && !solved;
+  const bool wr_p = MODE != CGD_LIGHT, wr_p2 = MODE == CGD_LIGHT && !solved;
+  const int64_t nvec = n / VEC;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < nvec) {
+    const T pv = ldg<NT>(reinterpret_cast<T *>(p) + i);
+    T qv = {}, xv = {}, rv = {};
+    if (rd_q) qv = ldg<NT>(reinterpret_cast<T *>(p2) + i);
+    if (rd_x) xv = ldg<NT>(reinterpret_cast<T *>(x) + i);
+    if (rd_r) rv = ldg<NT>(reinterpret_cast<const T *>(r) + i);
+    T xo, po;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      double sx, sp;
+      cg_defer_elem<MODE>(solved, a0, a, b, vget(rv, e), vget(pv, e), vget(qv, e), vget(xv, e), sx, sp);
+      vset(xo, e, sx);
+      vset(po, e, sp);
+    }
+    if (rd_x) stg<NT>(xo, reinterpret_cast<T *>(x) + i);
+    if (wr_p) stg<NT>(po, reinterpret_cast<T *>(p) + i);
+    if (wr_p2) stg<NT>(po, reinterpret_cast<T *>(p2) + i);
+  }
+  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    const int64_t t = n - 1;
+    double sx, sp;
+    cg_defer_elem<MODE>(solved, a0, a, b, rd_r ? r[t] : 0.0, p[t], rd_q ? p2[t] : 0.0, rd_x ? x[t] : 0.0, sx, sp);
+    if (rd_x) x[t] = sx;
+    if (wr_p) p[t] = sp;
+    if (wr_p2) p2[t] = sp;
+  }
+}
+
+int launch_cg_defer(khip_ctx *ctx, int64_t n, int mode, const void *cg_state_dev, long long seq, int flush_prev, const double *r,
+                    double *p, double *p2, double *x) {
+  if (n <= 0) return KHIP_OK;
+  const CgDevState *st = static_cast<const CgDevState *>(cg_state_dev);
+  const bool v2 = n >= 2 && aligned16(r) && aligned16(p) && aligned16(p2) && aligned16(x);
+  const bool nt = use_nt(ctx, n);
+  const int64_t g = tiles_for(v2 ? n / 2 : n, 1);
+  if (g > 0x7fffffffLL) { set_error("vector too long for one launch"); return KHIP_ERR_INVALID; }
+#define KHIP_CGD(MODE, VEC, NT) \
+  hipLaunchKernelGGL((cg_defer_kernel<MODE, VEC, NT>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, st, seq, flush_prev, r, p, p2, x)
+#define KHIP_CGD_M(MODE) do { if (v2) { if (nt) KHIP_CGD(MODE, 2, true); else KHIP_CGD(MODE, 2, false); } \
+                              else    { if (nt) KHIP_CGD(MODE, 1, true); else KHIP_CGD(MODE, 1, false); } } while (0)
+  if (mode == CGD_LIGHT) KHIP_CGD_M(CGD_LIGHT);
+  else if (mode == CGD_HEAVY) KHIP_CGD_M(CGD_HEAVY);
+  else if (mode == CGD_FLUSH) KHIP_CGD_M(CGD_FLUSH);
+  else { set_error("launch_cg_defer: unknown mode %d", mode); return KHIP_ERR_INVALID; }
+#undef KHIP_CGD_M
+#undef KHIP_CGD
+  KHIP_CHECK_HIP(hipGetLastError());
+  return KHIP_OK;
+}
+
 // Scalar epilogue on its own (the reduction value was written to results[slot] by other means).
 __global__ void epilogue_kernel(RedArgs ra) {
   if (seq_skip(ra.stop_seq, ra.seq)) return;

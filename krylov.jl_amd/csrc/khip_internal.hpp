@@ -93,6 +93,7 @@ struct Tuning {
   int spmv_template = 1;    // use the row-template kernel on handles that khip_csr_compress compressed
   int spmv_tmpl_rows = 8;   // template kernel: rows per lane (amortises the per-workgroup table load; 1.02 -> 0.86 ms at 512^3)
   int spmv_cap = 0;         // staged kernel LDS window in entries (0 = sized to the widest row block)
+  int cg_defer_x = 1;       // device-resident cg! loop: x is updated every second iteration through a second direction buffer of n doubles (140n instead of 144n bytes per iteration, same bits); 0: x every iteration, no extra buffer
   int cg_setup_fused = 1;   // cg! (fused paths, M = I, no warm start): x = 0, r = p = b, gamma = b.b in one pass (khip_cg_setup) instead of four primitives
   int spmv_sell = 2;        // coded operators with 8-bit codes: the sliced (64-row transposed) form -- every lane loads its own row's entries with coalesced 8-byte loads, no LDS window, no barrier in the row walk (1: default load policy, 2: non-temporal loads of the matrix words, 0: off = spmv_code_kernel); 512^3: 2.21 -> 1.97-2.00 ms fused, CG 275 -> 290-297 it/s (profiles/r06ap, r06aq)
   int spmv_sell_pair = 1;   // sliced form of a coded operator: the row's words in 16-byte pairs (half the vector-memory instructions of the matrix stream): 7-point 512^3 fused 1.92-2.00 -> 1.77-1.84 ms, 27-point 216^3 plain 0.53 -> 0.49 ms; 2 = for the int32 form too (96 instead of 88 B per 7-point row: no gain, off)
@@ -315,6 +316,12 @@ int launch_cg_update(khip_ctx *ctx, int64_t n, double a, double b, const double 
 // same with alpha / beta / solved read from a CgDevState in device memory (solver_device.hpp)
 int launch_cg_update_dev(khip_ctx *ctx, int64_t n, const void *cg_state_dev, long long seq, const double *r, double *p,
                          double *x);
+// the same with x updated every second iteration (cg_device_loop, solvers.cpp).  LIGHT: p2 = r + beta p (solved: x += alpha p
+// instead); HEAVY: x += alpha_prev p + alpha p2 ; p = r + beta p2 (solved: p = p2); FLUSH, after the loop: x += a p ; p = p2
+// with a = alpha_prev when flush_prev is set, else alpha
+enum CgDeferMode { CGD_LIGHT = 0, CGD_HEAVY = 1, CGD_FLUSH = 2 };
+int launch_cg_defer(khip_ctx *ctx, int64_t n, int mode, const void *cg_state_dev, long long seq, int flush_prev, const double *r,
+                    double *p, double *p2, double *x);
 // run the scalar epilogue in ctx->ctl on results[slot..] (1-thread kernel; used when the reduction result was
 // produced outside a finish kernel) / fold nranks gathered (hi, lo) partials per scalar and run it
 int launch_epilogue_only(khip_ctx *ctx, int slot);

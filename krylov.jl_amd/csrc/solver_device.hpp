@@ -21,6 +21,7 @@ struct CgDevState {
   double gamma;        // r.z of the current iterate              (src/cg.jl:162, 257)
   double pAp;          //                                          (:197)
   double alpha;        // gamma / pAp                              (:213)
+  double alpha_prev;   // alpha of the iteration before: the x update a light iteration left pending (cg_defer_x, solvers.cpp)
   double beta;         // gamma_next / gamma                       (:256)
   double pNorm2;       //                                          (:257)
   double rNorm;        // sqrt(gamma_next)                         (:243)
@@ -278,6 +279,7 @@ __device__ inline void solver_epilogue(int epi, void *state, const double *v, lo
         return;
       }
     }
+    st->alpha_prev = st->alpha;
     st->alpha = st->gamma / pAp;
   } else if (epi == EPI_CG_STEP2) {                // v[0] = r.r after r -= alpha Ap     src/cg.jl:242-262
     CgDevState *st = static_cast<CgDevState *>(state);

@@ -37,6 +37,7 @@ struct khip_cg_workspace {
   Borrowed borrowed;                   // vectors of a caller's CgWorkspace (khip_cg_workspace_adopt)
   StatsBox box;
   double *pz = nullptr, *pq = nullptr;                        // pipelined variant: z = A s, q = A w (allocated on first use)
+  double *p2 = nullptr;                                       // device-resident cg! loop: second direction buffer (cg_defer_x; allocated on first use)
   DeviceLoop<CgDevState> loop;                                // device-resident loops (fused = 2): cg! ...
   DeviceLoop<CgcgDevState> cgcg_loop;                         // ... and the single-reduction and pipelined variants
 };
@@ -46,16 +47,32 @@ namespace {
 // The loop of src/cg.jl:195-268 with scalars and stopping tests on the device.  Preconditions (checked by
 // the caller): CSR operator, M = I, radius = 0, no linesearch, no callback.  On return the vectors are in
 // the state the reference's loop leaves them in and `out` holds the final scalar state.
+//
+// Nothing reads x before the solve returns, so (ctx option cg_defer_x, default on) x is updated every SECOND iteration: an even
+// ("light") iteration j only forms p_{j+1} = r + beta p_j in the second direction buffer p2 and leaves x += alpha_j p_j pending;
+// the odd ("heavy") iteration after it applies both x updates in one read and one write of x and forms p_{j+2} in p, over
+// p_j.  24n + 48n instead of 2 x 40n bytes per pair of iterations; the same operations on the same operands in the same order,
+// so every vector keeps its bits.  A loop that ends with an update pending (an odd number of iterations done and not solved:
+// itmax, timemax, the curvature test or r.r < 0 right after a light iteration) is completed by one flush pass.
 int cg_device_loop(khip_cg_workspace *ws, const khip_csr *A, double gamma, double eps_tol, const DeviceLoopArgs &a,
                    CgDevState *out, bool *overtimed) {
   khip_ctx *ctx = ws->ctx;
   const int64_t n = ws->n;
   CgDevState h{};
   h.gamma = gamma; h.pNorm2 = gamma; h.eps_tol = eps_tol; h.keps = kEps; h.rNorm = std::sqrt(gamma);
+  // allocated on first use; without it the solve runs the loop that needs none.  Not one of the workspace's vectors: its
+  // allocation is not charged to stats.allocation_timer, which counts those (src/krylov_workspaces.jl:288-289)
+  if (ctx->tune.cg_defer_x && !ws->p2 && n > 0) {
+    void *q = nullptr;
+    if (hipSetDevice(ctx->device) == hipSuccess && hipMalloc(&q, sizeof(double) * (size_t)padded(n)) == hipSuccess) ws->p2 = static_cast<double *>(q);
+    else (void)hipGetLastError();
+  }
+  double *p2 = ctx->tune.cg_defer_x ? ws->p2 : nullptr;
   auto step = [&](CgDevState *dev, long long j) {
+    const bool heavy = p2 && (j & 1);
     ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j, EPI_CG_STEP1, dev};
     const int s1 = take_slots(ctx, 1);
-    int rc = spmv_any(ctx, A, ws->p, ws->Ap, s1);                                     // :196-197, epilogue :198-213
+    int rc = spmv_any(ctx, A, heavy ? p2 : ws->p, ws->Ap, s1);                        // :196-197, epilogue :198-213
     if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, s1, 1);
     if (rc != KHIP_OK) return rc;
     ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j + 1, EPI_CG_STEP2, dev};
@@ -64,9 +81,15 @@ int cg_device_loop(khip_cg_workspace *ws, const khip_csr *A, double gamma, doubl
     if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, s2, 1);
     ctx->ctl = SeqCtl{};
     if (rc != KHIP_OK) return rc;
-    return launch_cg_update_dev(ctx, n, dev, 3 * j + 2, ws->r, ws->p, ws->x);         // :239 and :259
+    if (!p2) return launch_cg_update_dev(ctx, n, dev, 3 * j + 2, ws->r, ws->p, ws->x);   // :239 and :259
+    return launch_cg_defer(ctx, n, heavy ? CGD_HEAVY : CGD_LIGHT, dev, 3 * j + 2, 0, ws->r, ws->p, p2, ws->x);
   };
-  return ws->loop.run(ctx, h, a, step, out, overtimed);
+  KHIP_TRY(ws->loop.run(ctx, h, a, step, out, overtimed));
+  // pending: the last completed iteration was a light one and did not solve.  The iteration that stopped the loop, if any,
+  // left alpha alone (curvature test: step 1 returned first) or had already replaced it (r.r < 0 in step 2)
+  if (p2 && !out->solved && (out->iter & 1))
+    KHIP_TRY(launch_cg_defer(ctx, n, CGD_FLUSH, ws->loop.dev, 0, out->not_spd ? 1 : 0, ws->r, ws->p, p2, ws->x));
+  return KHIP_OK;
 }
 
 // the initial state of the single-reduction and pipelined variants
@@ -191,7 +214,7 @@ int khip_cg_workspace_adopt_vector(khip_cg_workspace *ws, const char *name, doub
 
 int khip_cg_workspace_destroy(khip_cg_workspace *ws) {
   if (!ws) return KHIP_OK;
-  for (double *v : {ws->dx, ws->x, ws->r, ws->npc_dir, ws->p, ws->Ap, ws->z, ws->pz, ws->pq}) free_unless_borrowed(ws->ctx, ws->borrowed, v);
+  for (double *v : {ws->dx, ws->x, ws->r, ws->npc_dir, ws->p, ws->Ap, ws->z, ws->pz, ws->pq, ws->p2}) free_unless_borrowed(ws->ctx, ws->borrowed, v);
   ws->loop.release();
   ws->cgcg_loop.release();
   delete ws;

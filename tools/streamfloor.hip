@@ -659,6 +659,61 @@ static void cgfold_main(int n1) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------ cg! x update every second iteration?
+// Today's device-loop update (cg_update_dev_kernel: x += a p ; p = r + b p, 3R + 2W in place, 40n bytes) against the pair that
+// touches x only every second iteration: a light pass p2 = r + b p (2R + 1W out of place, 24n) and a heavy pass
+// x += a1 p + a2 p2 ; p = r + b p2 (4R + 2W, 48n) -- 72n instead of 80n per two iterations, IF the 4R + 2W mix streams at the rate
+// of the 3R + 2W one.  Access style of csrc/blas1.hip: one 16-byte element per thread, non-temporal loads and stores.
+// MIX 0: 3R + 2W in place; 1: 2R + 1W out of place; 2: 4R + 2W.
+template <int MIX>
+__global__ __launch_bounds__(256) void k_cgdefer(long nv, double a, double b, const dbl2 *r, dbl2 *p, dbl2 *p2, dbl2 *x) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nv) return;
+  const dbl2 rv = __builtin_nontemporal_load(r + i), pv = __builtin_nontemporal_load(p + i);
+  if (MIX == 1) {
+    dbl2 o; o.x = fma(1.0, rv.x, b * pv.x); o.y = fma(1.0, rv.y, b * pv.y);
+    __builtin_nontemporal_store(o, p2 + i);
+    return;
+  }
+  const dbl2 xv = __builtin_nontemporal_load(x + i);
+  dbl2 xo, po;
+  if (MIX == 0) {
+    xo.x = fma(a, pv.x, xv.x); xo.y = fma(a, pv.y, xv.y);
+    po.x = fma(1.0, rv.x, b * pv.x); po.y = fma(1.0, rv.y, b * pv.y);
+  } else {
+    const dbl2 qv = __builtin_nontemporal_load(p2 + i);
+    xo.x = fma(a, qv.x, fma(b, pv.x, xv.x)); xo.y = fma(a, qv.y, fma(b, pv.y, xv.y));
+    po.x = fma(1.0, rv.x, b * qv.x); po.y = fma(1.0, rv.y, b * qv.y);
+  }
+  __builtin_nontemporal_store(xo, x + i);
+  __builtin_nontemporal_store(po, p + i);
+}
+
+static void cgdefer_main(int n1) {
+  const long n = (long)n1 * n1 * n1, nv = n / 2;
+  double *v[4];
+  for (auto &q : v) { CK(hipMalloc(&q, n * 8)); CK(hipMemset(q, 0, n * 8)); }
+  const dbl2 *r = (const dbl2 *)v[0]; dbl2 *p = (dbl2 *)v[1], *p2 = (dbl2 *)v[2], *x = (dbl2 *)v[3];
+  const unsigned G = (unsigned)((nv + 255) / 256);
+  printf("cg! x update every second iteration? streams of %ld doubles (%.2f GB each), 16 B per thread, non-temporal loads and stores, 20 launches per figure\n", n, n * 8 / 1e9);
+  const int rounds = 7;
+  float t[3][rounds];
+  for (int k = 0; k < rounds; ++k) {
+    t[0][k] = timeit([&] { hipLaunchKernelGGL(k_cgdefer<0>, dim3(G), dim3(256), 0, 0, nv, 0.25, 0.5, r, p, p2, x); }, 20);
+    t[1][k] = timeit([&] { hipLaunchKernelGGL(k_cgdefer<1>, dim3(G), dim3(256), 0, 0, nv, 0.25, 0.5, r, p, p2, x); }, 20);
+    t[2][k] = timeit([&] { hipLaunchKernelGGL(k_cgdefer<2>, dim3(G), dim3(256), 0, 0, nv, 0.25, 0.5, r, p, p2, x); }, 20);
+    printf("round %d  3R+2W in place %.4f ms (%5.0f GB/s)   2R+1W out of place %.4f ms (%5.0f GB/s)   4R+2W %.4f ms (%5.0f GB/s)   light + heavy - 2 x today = %+.4f ms\n", k,
+           t[0][k], 40.0 * n / t[0][k] / 1e6, t[1][k], 24.0 * n / t[1][k] / 1e6, t[2][k], 48.0 * n / t[2][k] / 1e6, t[1][k] + t[2][k] - 2 * t[0][k]);
+    fflush(stdout);
+  }
+  float lo[3], hi[3];
+  for (int m = 0; m < 3; ++m) { lo[m] = hi[m] = t[m][0]; for (int k = 1; k < rounds; ++k) { lo[m] = t[m][k] < lo[m] ? t[m][k] : lo[m]; hi[m] = t[m][k] > hi[m] ? t[m][k] : hi[m]; } }
+  printf("ranges over %d rounds: 3R+2W %.4f-%.4f   2R+1W %.4f-%.4f   4R+2W %.4f-%.4f ms\n", rounds, lo[0], hi[0], lo[1], hi[1], lo[2], hi[2]);
+  printf("pair of iterations: today 2 x (3R+2W) = %.4f-%.4f ms ; light + heavy = %.4f-%.4f ms ; slowest pair against fastest today: %+.4f ms per pair\n",
+         2 * lo[0], 2 * hi[0], lo[1] + lo[2], hi[1] + hi[2], hi[1] + hi[2] - 2 * lo[0]);
+  for (auto &q : v) CK(hipFree(q));
+}
+
 int main(int argc, char **argv) {
   const char *mode = argc > 1 ? argv[1] : "panel";
   if (strcmp(mode, "panel") == 0) panel_main(argc > 2 ? atol(argv[2]) : 10077696L, 16);
@@ -667,6 +722,7 @@ int main(int argc, char **argv) {
   else if (strcmp(mode, "spmmirr") == 0) spmmirr_main();
   else if (strcmp(mode, "spmmslide") == 0) spmmslide_main(argc > 2 ? atoi(argv[2]) : 216);
   else if (strcmp(mode, "cgfold") == 0) cgfold_main(argc > 2 ? atoi(argv[2]) : 512);
-  else { printf("usage: streamfloor panel [rows] | multi [rows] | spmm [n1] | spmmslide [n1] | spmmirr | cgfold [n1]\n"); return 2; }
+  else if (strcmp(mode, "cgdefer") == 0) cgdefer_main(argc > 2 ? atoi(argv[2]) : 512);
+  else { printf("usage: streamfloor panel [rows] | multi [rows] | spmm [n1] | spmmslide [n1] | spmmirr | cgfold [n1] | cgdefer [n1]\n"); return 2; }
   return 0;
 }
