@@ -72,6 +72,11 @@ int khip_test_small_dense(int which, int m, int n, int nc, double *A, double *ta
  * right) and is a defect of the builder; the GPU test session asserts 0 (tests/conftest.py). */
 int khip_test_optional_build_failures(int *count);
 
+/* test-only: the CSR arrays a handle holds (for a transposed handle: what khip_csr_transpose built), copied to the host:
+ * rowptr_out has m + 1 entries, col_out / val_out nnz (tests/test_gpu_operator_forms_exact.py compares the rows of A' with the
+ * stable column-major order of A, entry by entry). */
+int khip_test_csr_arrays(const khip_csr *A, int32_t *rowptr_out, int32_t *col_out, double *val_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -249,6 +249,7 @@ SIGNATURES = {
     "khip_test_householder_r": (_int, [_int, _int, c_double_p, c_double_p]),
     "khip_test_householder_signs": (_int, [_int, _i64, c_double_p, c_double_p, c_double_p]),
     "khip_test_optional_build_failures": (_int, [C.POINTER(_int)]),
+    "khip_test_csr_arrays": (_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_double_p]),
     "khip_test_set_halo_self": (_int, [_vp, _int]),
     "khip_test_sym_givens": (_int, [C.c_double, C.c_double, c_double_p, c_double_p, c_double_p]),
     "khip_test_roots_quadratic": (_int, [C.c_double, C.c_double, C.c_double, _int, c_double_p, c_double_p]),
@@ -802,6 +803,15 @@ class CsrMatrix:
         h = C.c_void_p()
         _ck(lib().khip_csr_transpose(self.ctx._h, self._h, C.byref(h)))
         return CsrMatrix(self.ctx, h)
+
+    def to_host_arrays(self):
+        """(rowptr, col, val) as the handle holds them, copied to the host (test export khip_test_csr_arrays)."""
+        rp = np.empty(self.m + 1, dtype=np.int32)
+        cl = np.empty(self.nnz, dtype=np.int32)
+        vl = np.empty(self.nnz, dtype=np.float64)
+        _ck(lib().khip_test_csr_arrays(self._h, rp.ctypes.data_as(C.POINTER(C.c_int32)), cl.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       vl.ctypes.data_as(c_double_p)))
+        return rp, cl, vl
 
     def compress(self) -> int:
         """Re-encode as row templates when the operator repeats few (column - row, value) rows (stencils);

@@ -41,6 +41,18 @@ int khip_test_optional_build_failures(int *count) {
   return KHIP_OK;
 }
 
+// test-only (include/krylov_hip_test.h): the CSR arrays a handle holds, copied to the host
+int khip_test_csr_arrays(const khip_csr *A, int32_t *rowptr_out, int32_t *col_out, double *val_out) {
+  KHIP_REQUIRE(A && A->ctx && rowptr_out && (A->nnz == 0 || (col_out && val_out)), "test_csr_arrays: null argument");
+  KHIP_CHECK_HIP(hipStreamSynchronize(A->ctx->stream));
+  KHIP_CHECK_HIP(hipMemcpy(rowptr_out, A->rowptr, sizeof(int32_t) * (size_t)(A->m + 1), hipMemcpyDeviceToHost));
+  if (A->nnz > 0) {
+    KHIP_CHECK_HIP(hipMemcpy(col_out, A->col, sizeof(int32_t) * (size_t)A->nnz, hipMemcpyDeviceToHost));
+    KHIP_CHECK_HIP(hipMemcpy(val_out, A->val, sizeof(double) * (size_t)A->nnz, hipMemcpyDeviceToHost));
+  }
+  return KHIP_OK;
+}
+
 void khip_version(int *major, int *minor) {
   if (major) *major = KHIP_VERSION_MAJOR;
   if (minor) *minor = KHIP_VERSION_MINOR;

@@ -755,7 +755,9 @@ __global__ __launch_bounds__(kBlock) void band_kernel(const int32_t *rowptr, con
   int mx = 0;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < m; i += (int64_t)gridDim.x * kBlock) {
     const int32_t s = rowptr[i], e = rowptr[i + 1];
-    if (e > s) {                                   // sorted rows: the extremes are the first and last entry; unsorted: scan
+    if (e > s) {                                   // the first and last entry: the extremes of a row with sorted columns.  Unsorted rows
+                                                   // (khip_csr_create admits them) are NOT scanned: `band` only sizes the SpMM sweeps, a
+                                                   // too-small value costs speed there and never a bit of a result
       int d0 = (int)i - col[s], d1 = col[e - 1] - (int)i;
       d0 = d0 < 0 ? -d0 : d0; d1 = d1 < 0 ? -d1 : d1;
       mx = d0 > mx ? d0 : mx; mx = d1 > mx ? d1 : mx;
@@ -799,7 +801,8 @@ __global__ __launch_bounds__(kBlock) void blockptr_kernel(const int32_t *rowptr,
 
 // Structural validation of user arrays (they are trusted by every kernel afterwards: window loads through buffer
 // descriptors, x gathers, the ghost remap): row pointers start at 0, never decrease, end at nnz; columns lie in [0, n).
-// bad[0] = smallest offending row (m + 1 = none), bad[1] = kind (1 row pointer, 2 column).
+// bad[0] = 4 * (smallest offending row) + its kind (1 row pointer, 2 column): ONE key and one atomicMin, so the kind reported is
+// that row's own whichever workgroup finishes last (4 * (m + 1) = none).
 __global__ __launch_bounds__(kBlock) void csr_validate_kernel(const int32_t *rowptr, const int32_t *col, int64_t m, int64_t n,
                                                                int64_t nnz, unsigned long long *bad) {
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < m; i += (int64_t)gridDim.x * kBlock) {
@@ -811,10 +814,7 @@ __global__ __launch_bounds__(kBlock) void csr_validate_kernel(const int32_t *row
         const int32_t c = col[q];
         if (c < 0 || (int64_t)c >= n) { kind = 2; break; }
       }
-    if (kind) {
-      const unsigned long long old = atomicMin(&bad[0], (unsigned long long)i);
-      if ((unsigned long long)i < old) bad[1] = (unsigned long long)kind;
-    }
+    if (kind) atomicMin(&bad[0], (unsigned long long)i * 4 + (unsigned long long)kind);
   }
 }
 
@@ -846,8 +846,8 @@ int csr_finalize(khip_ctx *ctx, khip_csr *A) {
   }
   {
     unsigned long long *d_bad = nullptr;
-    KHIP_CHECK_HIP(hipMalloc(&d_bad, 2 * sizeof(unsigned long long)));
-    unsigned long long h_bad[2] = {(unsigned long long)A->m + 1, 0ull};
+    KHIP_CHECK_HIP(hipMalloc(&d_bad, sizeof(unsigned long long)));
+    unsigned long long h_bad[1] = {((unsigned long long)A->m + 1) * 4};
     hipError_t e = hipMemcpyAsync(d_bad, h_bad, sizeof(h_bad), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
       int64_t wantv = (A->m + kBlock - 1) / kBlock;
@@ -859,10 +859,10 @@ int csr_finalize(khip_ctx *ctx, khip_csr *A) {
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     (void)hipFree(d_bad);
     if (e != hipSuccess) { set_error("csr validation: %s", hipGetErrorString(e)); return KHIP_ERR_HIP; }
-    if (h_bad[0] <= (unsigned long long)A->m) {
-      set_error(h_bad[1] == 2 ? "csr: row %llu has a column index outside [0, %lld) (wrong index_base?)"
-                              : "csr: row pointers are not a monotone sequence from 0 to nnz at row %llu (n = %lld; wrong index_base?)",
-                h_bad[0], (long long)A->n);
+    if (h_bad[0] / 4 <= (unsigned long long)A->m) {
+      set_error(h_bad[0] % 4 == 2 ? "csr: row %llu has a column index outside [0, %lld) (wrong index_base?)"
+                                  : "csr: row pointers are not a monotone sequence from 0 to nnz at row %llu (n = %lld; wrong index_base?)",
+                h_bad[0] / 4, (long long)A->n);
       return KHIP_ERR_INVALID;
     }
   }

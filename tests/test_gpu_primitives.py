@@ -1046,3 +1046,21 @@ def test_csr_create_rejects_malformed_arrays(K, ctx):
         with pytest.raises(K.KhipError) as ei:
             K.CsrMatrix.from_host(ctx, bad_rp, bad_cl, vl, (3, 3))
         assert why in str(ei.value), (why, str(ei.value))
+    # Two kinds of fault at once, in different workgroups: the message names the SMALLEST bad row with that row's OWN kind
+    # (csr_validate_kernel reports row and kind through one atomicMin on the key 4 * row + kind).  This states the property: with
+    # two separate words the wrong kind appeared only when the later rows' workgroups wrote last.
+    m = 6000
+    rp = 2 * np.arange(m + 1, dtype=np.int64)
+    cl = np.tile(np.array([0, 1], dtype=np.int32), m)
+    vl = np.ones(2 * m)
+    K.CsrMatrix.from_host(ctx, rp, cl, vl, (m, m))                                   # well-formed
+    rp_low, cl_late = rp.copy(), cl.copy()
+    rp_low[4] = rp_low[3] - 1                                                        # row 3: its end lies before its start
+    cl_late[2 * 2000::2] = m + 5                                                     # rows 2000 ..: a column >= n
+    rp_late, cl_low = rp.copy(), cl.copy()
+    rp_late[2001:m:2] -= 3                                                           # rows 2000, 2002, ...: end before start
+    cl_low[2 * 3 + 1] = -7                                                           # row 3: a negative column
+    for bad_rp, bad_cl, why, where in [(rp_low, cl_late, "row pointers", "at row 3 "), (rp_late, cl_low, "column index", "row 3 has")]:
+        with pytest.raises(K.KhipError) as ei:
+            K.CsrMatrix.from_host(ctx, bad_rp, bad_cl, vl, (m, m))
+        assert why in str(ei.value) and where in str(ei.value), (why, where, str(ei.value))
