@@ -558,6 +558,39 @@ int khip_cg_lanczos_shift_last_path(khip_cg_lanczos_shift_workspace *ws);
 double           *khip_cg_lanczos_shift_vector(khip_cg_lanczos_shift_workspace *ws, const char *name);
 size_t            khip_cg_lanczos_shift_workspace_bytes(khip_cg_lanczos_shift_workspace *ws);   /* (2 nshifts + 3) n doubles without M */
 
+/* ---- bilq! (src/bilq.jl:118-407), real Float64: square nonsymmetric systems by the two-sided Lanczos process on A and A', with the
+ * transfer to the BiCG point.  BilqWorkspace (src/krylov_workspaces.jl): uₖ₋₁, uₖ, q, vₖ₋₁, vₖ, p, x, d̅ (8 vectors of n doubles), + Δx
+ * with a warm start, + t with M, + s with N (allocated lazily, counted by stats.allocation_timer).  The adjoint travels as its own
+ * operator: khip_csr_transpose builds it for a CSR handle (row-partitioned handles included).  options.radius, linesearch, restart,
+ * reorthogonalization and variant are ignored.  After a solve only x and the stats are defined: the fused loops rotate the roles of
+ * (vₖ₋₁, vₖ) and (uₖ₋₁, uₖ) instead of copying, and khip_bilq_vector returns a name's pointer by its current role. */
+typedef struct khip_bilq_workspace khip_bilq_workspace;
+typedef struct {
+  int transfer_to_bicg;        /* also test and return the BiCG point xᶜ; default 1        (src/bilq.jl:98) */
+  const khip_operator *Mt, *Nt; /* adjoints of M, N; NULL = the operator is applied as its own adjoint: right for a diagonal (Jacobi) one only, the caller's duty otherwise */
+} khip_bilq_params;
+khip_bilq_params khip_bilq_default_params(void);   /* transfer_to_bicg = 1, Mt = Nt = NULL */
+int khip_bilq_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_bilq_workspace **out);   /* m != n: KHIP_ERR_INVALID "System must be square" */
+/* BilqWorkspace on the caller's eight vectors; every pointer must be distinct.  adopt_vector names: "dx" (Δx: warm_start! fills it on
+ * the caller's side and hands it over, then khip_bilq_warm_start(ws, dx) only sets the flag), "t" (needed with M), "s" (needed with N) */
+int khip_bilq_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *u_prev, double *u, double *q, double *v_prev, double *v,
+                              double *p, double *x, double *dbar, khip_bilq_workspace **out);
+int khip_bilq_workspace_adopt_vector(khip_bilq_workspace *ws, const char *name, double *ptr);
+int khip_bilq_workspace_destroy(khip_bilq_workspace *ws);
+int khip_bilq_warm_start(khip_bilq_workspace *ws, const double *x0);
+/* bilq!(ws, A, b; c, transfer_to_bicg, M, N, atol, rtol, itmax, timemax, verbose, history, callback).  At = A' is required (NULL:
+ * KHIP_ERR_INVALID); c == NULL means c = b; M / N == NULL mean the identity, otherwise q <- M A N v and p <- Nt At Mt u.
+ * Loops (khip_bilq_last_path): 2 = device-resident (A and At CSR handles, M = N = I, no callback, verbose = 0), 1 = host-driven on the
+ * same kernels (same bits as 2), 0 = one launch per primitive (options.fused = 0). */
+int khip_bilq_solve(khip_bilq_workspace *ws, const khip_operator *A, const khip_operator *At, const khip_operator *M,
+                    const khip_operator *N, const double *b, const double *c, const khip_options *opts, const khip_bilq_params *params);
+double           *khip_bilq_solution(khip_bilq_workspace *ws);
+const khip_stats *khip_bilq_stats(khip_bilq_workspace *ws);
+int khip_bilq_last_path(khip_bilq_workspace *ws);
+/* named work vectors: "u_prev", "u", "q", "v_prev", "v", "p", "x", "dbar", "dx", "t", "s" (NULL while not allocated) */
+double           *khip_bilq_vector(khip_bilq_workspace *ws, const char *name);
+size_t            khip_bilq_workspace_bytes(khip_bilq_workspace *ws);   /* 8n doubles without M, N and warm start */
+
 int khip_gmres_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, int memory, khip_gmres_workspace **out);
 /* GmresWorkspace on the caller's x, w and basis V_host[0 .. memory) (device pointers in a HOST array; `V::Vector{S}`,
  * src/krylov_workspaces.jl:2857-2873).  adopt_vector names: "x", "w", "p", "q", "dx".  adopt_basis replaces the whole list

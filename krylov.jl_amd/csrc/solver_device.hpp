@@ -15,7 +15,8 @@
 namespace khip {
 
 enum Epilogue { EPI_NONE = 0, EPI_CG_STEP1 = 1, EPI_CG_STEP2 = 2, EPI_BICG_A = 3, EPI_BICG_B = 4, EPI_BICG_C = 5, EPI_CGCG = 6,
-               EPI_MINRES_A = 7, EPI_MINRES_B = 8, EPI_MINRES_C = 9, EPI_LZSHIFT_A = 10, EPI_LZSHIFT_B = 11 };
+               EPI_MINRES_A = 7, EPI_MINRES_B = 8, EPI_MINRES_C = 9, EPI_LZSHIFT_A = 10, EPI_LZSHIFT_B = 11,
+               EPI_BILQ_A = 12, EPI_BILQ_B = 13, EPI_BILQ_C = 14 };
 
 struct CgDevState {
   double gamma;        // r.z of the current iterate              (src/cg.jl:162, 257)
@@ -261,6 +262,126 @@ __host__ __device__ inline bool lzshift_step(LanczosShiftDevState &s, const LzSh
   return !any;
 }
 
+// sym_givens(a, b) for reals, src/krylov_utils.jl:21-51: one source for the host code of gmres! and for the epilogues below
+__host__ __device__ inline double sym_givens_sign(double v) { return v > 0 ? 1.0 : (v < 0 ? -1.0 : 0.0); }
+__host__ __device__ inline void sym_givens(double a, double b, double &c, double &s, double &rho) {
+  if (b == 0.0) {
+    c = sym_givens_sign(a) + (a == 0.0 ? 1.0 : 0.0);
+    s = 0.0;
+    rho = fabs(a);
+  } else if (a == 0.0) {
+    c = 0.0;
+    s = sym_givens_sign(b);
+    rho = fabs(b);
+  } else if (fabs(b) > fabs(a)) {
+    const double t = a / b;
+    s = sym_givens_sign(b) / sqrt(1.0 + t * t);
+    c = s * t;
+    rho = b / s;
+  } else {
+    const double t = b / a;
+    c = sym_givens_sign(a) / sqrt(1.0 + t * t);
+    s = c * t;
+    rho = a / c;
+  }
+}
+
+// bilq! (src/bilq.jl:118-407), real Float64: the scalars of the two-sided Lanczos process, of the LQ factorisation of Tₖ, the
+// residual estimates of the LQ and CG points and the stopping tests.  The same three steps run on the host (loops 0 and 1) and as
+// the epilogues of the three reductions of an iteration (device-resident loop): one source, the reference's IEEE operations in its
+// order, so loops 1 and 2 produce the same bits.  Field names follow the reference.
+struct BilqDevState {
+  // coefficients the vector kernels read
+  double gamma, beta;            // γₖ, βₖ: P1                                   (:244-245)
+  double alpha;                  // αₖ: P2                                       (:247-250)
+  double beta_next, gamma_next;  // βₖ₊₁, γₖ₊₁: the divisors of P3               (:253-254, :329-330)
+  double pq;                     // pᴴq                                          (:252)
+  double zc, zs, neg_c, sn;      // ζₖ₋₁cₖ, ζₖ₋₁sₖ, -cₖ, sₖ: the x and d̅ updates (:316-321)
+  // constants of the solve
+  double bNorm, eps_tol;         // ‖r₀‖, ε = atol + rtol ‖r₀‖                   (:169, :199)
+  // recurrences
+  double cs, cs_prev, sn_prev;   // cₖ, cₖ₋₁, sₖ₋₁
+  double delta, lambda, epsilon; // δₖ₋₁, λₖ₋₁, ϵₖ₋₂
+  double dbar, dbar_prev;        // δbarₖ, δbarₖ₋₁
+  double zeta_m1, zeta_m2, zbar; // ζₖ₋₁, ζₖ₋₂, ζbarₖ
+  double eta, eta_prev;          // ηₖ, ηₖ₋₁
+  double norm_v;                 // ‖vₖ‖
+  double rNorm_lq, rNorm_cg;
+  long long stop_seq, iter, hist_base, hist_cap;
+  double *hist;                  // device history window (null: no history)
+  int transfer_to_bicg, solved_lq, solved_cg, breakdown;
+};
+
+// after αₖ = ⟨uₖ, q⟩ (:247)
+__host__ __device__ inline void bilq_step_a(BilqDevState &s, double uq) { s.alpha = uq; }
+
+// after pᴴq = ⟨p, q⟩: βₖ₊₁, γₖ₊₁ and the LQ update (:252-305); k = iter
+__host__ __device__ inline void bilq_step_b(BilqDevState &s, double pq, long long k) {
+  s.pq = pq;
+  s.beta_next = sqrt(fabs(pq));
+  s.gamma_next = pq / s.beta_next;
+  if (k == 1) {
+    s.dbar = s.alpha;
+  } else if (k == 2) {
+    sym_givens(s.dbar_prev, s.gamma, s.cs, s.sn, s.delta);
+    s.lambda = s.cs * s.beta + s.sn * s.alpha;
+    s.dbar = s.sn * s.beta - s.cs * s.alpha;
+  } else {
+    sym_givens(s.dbar_prev, s.gamma, s.cs, s.sn, s.delta);
+    s.epsilon = s.sn_prev * s.beta;
+    s.lambda = -s.cs_prev * s.cs * s.beta + s.sn * s.alpha;
+    s.dbar = -s.cs_prev * s.sn * s.beta - s.cs * s.alpha;
+  }
+  if (k == 1) s.eta = s.beta;
+  if (k == 2) {
+    s.zeta_m1 = s.eta_prev / s.delta;
+    s.eta = -s.lambda * s.zeta_m1;
+  }
+  if (k >= 3) {
+    s.zeta_m2 = s.zeta_m1;
+    s.zeta_m1 = s.eta_prev / s.delta;
+    s.eta = -s.epsilon * s.zeta_m2 - s.lambda * s.zeta_m1;
+  }
+  s.zc = s.zeta_m1 * s.cs;
+  s.zs = s.zeta_m1 * s.sn;
+  s.neg_c = -s.cs;
+}
+
+// after ⟨vₖ, vₖ₊₁⟩ and ‖vₖ₊₁‖ (:334-371): the residual estimates, the history entry, the shifts and the tests; true when the loop
+// stops (tired / overtimed / the callback are the driver's)
+__host__ __device__ inline bool bilq_step_c(BilqDevState &s, double vv_next, double norm_next, long long k) {
+  if (k == 1) {
+    s.rNorm_lq = s.bNorm;
+  } else {
+    const double mu = s.beta * (s.sn_prev * s.zeta_m2 - s.cs_prev * s.cs * s.zeta_m1) + s.alpha * s.sn * s.zeta_m1;
+    const double omega = s.beta_next * s.sn * s.zeta_m1;
+    const double theta = mu * omega * vv_next;
+    s.rNorm_lq = sqrt(mu * mu * (s.norm_v * s.norm_v) + omega * omega * (norm_next * norm_next) + 2 * theta);
+  }
+  if (s.hist) {
+    const long long idx = k - 1 - s.hist_base;
+    if (idx >= 0 && idx < s.hist_cap) s.hist[idx] = s.rNorm_lq;
+  }
+  const bool cg_point = s.transfer_to_bicg && (fabs(s.dbar) > 2.220446049250313e-16);
+  if (cg_point) {
+    s.zbar = s.eta / s.dbar;
+    const double rho = s.beta_next * (s.sn * s.zeta_m1 - s.cs * s.zbar);
+    s.rNorm_cg = fabs(rho) * norm_next;
+  }
+  s.sn_prev = s.sn;
+  s.cs_prev = s.cs;
+  s.eta_prev = s.eta;
+  s.gamma = s.gamma_next;
+  s.beta = s.beta_next;
+  s.dbar_prev = s.dbar;
+  s.norm_v = norm_next;
+  s.solved_lq = (s.rNorm_lq <= s.eps_tol) ? 1 : 0;
+  s.solved_cg = (cg_point && s.rNorm_cg <= s.eps_tol) ? 1 : 0;
+  s.breakdown = (!s.solved_lq && !s.solved_cg && s.pq == 0.0) ? 1 : 0;
+  s.iter = k;
+  return s.solved_lq || s.solved_cg || s.breakdown;
+}
+
 __device__ __forceinline__ bool seq_skip(const long long *stop_seq, long long seq) {
   return stop_seq != nullptr && seq >= *stop_seq;
 }
@@ -347,6 +468,14 @@ __device__ inline void solver_epilogue(int epi, void *state, const double *v, lo
       if (idx >= 0 && idx < st->hist_cap) row = st->hist + idx * st->nshifts;
     }
     if (lzshift_step(*st, lzshift_arrays(*st), k, row)) st->stop_seq = seq + 2;   // this iteration's P2 (seq + 1) still runs
+  } else if (epi == EPI_BILQ_A) {                  // v[0] = u.q                 src/bilq.jl:247
+    bilq_step_a(*static_cast<BilqDevState *>(state), v[0]);
+  } else if (epi == EPI_BILQ_B) {                  // v[0] = p.q                 :252-305
+    BilqDevState *st = static_cast<BilqDevState *>(state);
+    bilq_step_b(*st, v[0], st->iter + 1);
+  } else if (epi == EPI_BILQ_C) {                  // v = (v_k.v_k+1, v_k+1.v_k+1)   :334-371
+    BilqDevState *st = static_cast<BilqDevState *>(state);
+    if (bilq_step_c(*st, v[0], sqrt(v[1]), st->iter + 1)) st->stop_seq = seq + 1;
   } else if (epi == EPI_BICG_A) {                  // v[0] = c.v                 src/bicgstab.jl:223
     BicgDevState *st = static_cast<BicgDevState *>(state);
     st->alpha = st->rho / v[0];

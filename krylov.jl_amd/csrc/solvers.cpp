@@ -635,29 +635,7 @@ static int gmres_grow_basis(khip_gmres_workspace *ws, int count) {   // push!(V,
   return KHIP_OK;
 }
 
-// sym_givens(a, b) for reals, src/krylov_utils.jl:21-51
-static void sym_givens(double a, double b, double &c, double &s, double &rho) {
-  auto sgn = [](double v) { return v > 0 ? 1.0 : (v < 0 ? -1.0 : 0.0); };
-  if (b == 0.0) {
-    c = sgn(a) + (a == 0.0 ? 1.0 : 0.0);
-    s = 0.0;
-    rho = std::fabs(a);
-  } else if (a == 0.0) {
-    c = 0.0;
-    s = sgn(b);
-    rho = std::fabs(b);
-  } else if (std::fabs(b) > std::fabs(a)) {
-    const double t = a / b;
-    s = sgn(b) / std::sqrt(1.0 + t * t);
-    c = s * t;
-    rho = b / s;
-  } else {
-    const double t = b / a;
-    c = sgn(a) / std::sqrt(1.0 + t * t);
-    s = c * t;
-    rho = a / c;
-  }
-}
+// sym_givens(a, b): solver_device.hpp (shared with the device epilogues)
 
 extern "C" {
 
