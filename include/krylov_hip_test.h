@@ -77,6 +77,26 @@ int khip_test_optional_build_failures(int *count);
  * stable column-major order of A, entry by entry). */
 int khip_test_csr_arrays(const khip_csr *A, int32_t *rowptr_out, int32_t *col_out, double *val_out);
 
+/* test-only: the SpMM pin (tests/spmm_model.py, tests/test_gpu_spmm_exact.py).
+ * khip_test_csr_tile_records: what spmm_tile_build left on the handle.  out16 = state (0 not tried, 1 built, -1 refused), window
+ * slots (cap), bytes per record, groups, run_len, runs, look-ahead flag, 1 = grid tiles, groups on the direct path (all 0 unless
+ * state == 1), then line_rows, plane_rows, m, n, nnz, n_ghost, band of the handle.  *reuse = the builder's score (references per
+ * distinct column).  meta_out (groups x stride bytes) / direct_out (direct-path groups) may be null: a first call reads the sizes.
+ * A record: int32 {row, first entry, length, aux}[32] | int32 list[cap] | uint8 slot[32][32]; aux of row slot 0 = distinct
+ * columns, 1 = direct-path flag, 2 = octets of window slots to copy, 3 = look-ahead flag.
+ * khip_test_csr_window_info: *win_L = lanes per row the window metadata was built for (-L: refused for L, 0: not tried), its row
+ * groups and how many of them are flagged for the direct path.
+ * khip_test_spmm_last_launch: what the last khip_spmm on ctx launched, written from the variables of the launch itself where it is
+ * decided (it changes no decision).  out24 = family (0 none yet, 1 spmm_kernel, 2 spmm2_kernel, 3 spmm_window_kernel, 4 spmm_tile_kernel,
+ * 5 spmm_tile2_kernel), L (spmm_kernel: P), NL, dbuf, ahead, run_len passed to the kernel, workgroups, XCD-order bits (8 round-robin,
+ * 128 chunked front, 0 eighths), tile launches (column slices), workgroups of the direct-path kernel, sweep S, W, K, columns per
+ * XCD, non-temporal instantiation, DIST instantiation, p, POW2 arm of the window kernel, threads per workgroup, dynamic LDS bytes,
+ * CUs of the device; the rest 0. */
+int khip_test_csr_tile_records(const khip_csr *A, int64_t *out16, double *reuse, char *meta_out, int64_t meta_bytes,
+                               int32_t *direct_out, int64_t direct_cap);
+int khip_test_csr_window_info(const khip_csr *A, int *win_L, int64_t *groups, int64_t *flagged);
+int khip_test_spmm_last_launch(const khip_ctx *ctx, int64_t *out24);
+
 #ifdef __cplusplus
 }
 #endif

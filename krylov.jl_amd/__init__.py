@@ -267,6 +267,9 @@ SIGNATURES = {
     "khip_test_householder_signs": (_int, [_int, _i64, c_double_p, c_double_p, c_double_p]),
     "khip_test_optional_build_failures": (_int, [C.POINTER(_int)]),
     "khip_test_csr_arrays": (_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_double_p]),
+    "khip_test_csr_tile_records": (_int, [_vp, C.POINTER(_i64), c_double_p, _vp, _i64, C.POINTER(C.c_int32), _i64]),
+    "khip_test_csr_window_info": (_int, [_vp, C.POINTER(_int), C.POINTER(_i64), C.POINTER(_i64)]),
+    "khip_test_spmm_last_launch": (_int, [_vp, C.POINTER(_i64)]),
     "khip_test_set_halo_self": (_int, [_vp, _int]),
     "khip_test_sym_givens": (_int, [C.c_double, C.c_double, c_double_p, c_double_p, c_double_p]),
     "khip_test_roots_quadratic": (_int, [C.c_double, C.c_double, C.c_double, _int, c_double_p, c_double_p]),
@@ -381,6 +384,18 @@ class Context:
     def test_set_halo_self(self, enable: int = 1):
         """TEST-ONLY measurement hook (include/krylov_hip_test.h): a one-rank RCCL communicator exchanges its halo with itself."""
         _ck(lib().khip_test_set_halo_self(self._h, int(enable)))
+
+    SPMM_LAUNCH_FIELDS = ("family", "L", "NL", "dbuf", "ahead", "run_len", "grid", "xcd", "launches", "direct", "sweep_S", "sweep_W",
+                          "sweep_K", "sweep_cols", "nt", "dist", "p", "pow2", "block", "lds", "num_cu")
+    SPMM_FAMILIES = ("none", "spmm_kernel", "spmm2_kernel", "window", "tile1", "tile2")
+
+    def spmm_last_launch(self) -> dict:
+        """TEST-ONLY (khip_test_spmm_last_launch): what the last spmm_ on this context launched, family by name."""
+        out = (_i64 * 24)()
+        _ck(lib().khip_test_spmm_last_launch(self._h, out))
+        d = {k: int(out[i]) for i, k in enumerate(self.SPMM_LAUNCH_FIELDS)}
+        d["family"] = self.SPMM_FAMILIES[d["family"]]
+        return d
 
     def get_option(self, key: str) -> int:
         v = C.c_int()
@@ -807,6 +822,31 @@ class CsrMatrix:
         g, d, r = C.c_int64(), C.c_int64(), C.c_double()
         _ck(lib().khip_csr_tile_info(self._h, C.byref(st), C.byref(w), C.byref(gt), C.byref(g), C.byref(d), C.byref(r)))
         return dict(state=st.value, window=w.value, grid_tiles=gt.value, groups=g.value, direct_groups=d.value, reuse=r.value)
+
+    TILE_RECORD_FIELDS = ("state", "cap", "stride", "groups", "run_len", "runs", "ahead", "grid_tiles", "direct", "line_rows",
+                          "plane_rows", "m", "n", "nnz", "n_ghost", "band")
+
+    def tile_records(self) -> dict:
+        """TEST-ONLY (khip_test_csr_tile_records): the build outcome of the tile SpMM, the raw group records ("meta": uint8
+        [groups, stride]) and the list of the groups on the direct path ("direct_list")."""
+        out, reuse = (_i64 * 16)(), C.c_double()
+        _ck(lib().khip_test_csr_tile_records(self._h, out, C.byref(reuse), None, 0, None, 0))
+        d = {k: int(out[i]) for i, k in enumerate(self.TILE_RECORD_FIELDS)}
+        d["reuse"] = reuse.value
+        meta = np.zeros((d["groups"], d["stride"]), dtype=np.uint8)
+        dl = np.zeros(d["direct"], dtype=np.int32)
+        if d["state"] == 1:
+            _ck(lib().khip_test_csr_tile_records(self._h, out, C.byref(reuse), meta.ctypes.data, meta.size,
+                                                 dl.ctypes.data_as(C.POINTER(C.c_int32)), dl.size))
+        d["meta"], d["direct_list"] = meta, dl
+        return d
+
+    @property
+    def window_info(self):
+        """TEST-ONLY (khip_test_csr_window_info): (win_L, groups, flagged groups) of the window SpMM's metadata."""
+        wl, g, f = C.c_int(), _i64(), _i64()
+        _ck(lib().khip_test_csr_window_info(self._h, C.byref(wl), C.byref(g), C.byref(f)))
+        return wl.value, g.value, f.value
 
     @property
     def halo_info(self):
@@ -1999,6 +2039,18 @@ class Panel:
         col = ctx.array(np.asfortranarray(M).ravel(order="F"))
         _ck(lib().khip_panel_from_colmajor(ctx._h, P.n, P.p, col.ptr, P.buf.ptr))
         ctx.sync()
+        return P
+
+    @classmethod
+    def from_raw_buffer(cls, ctx, n, buf):
+        """A panel of n rows whose WHOLE row-major buffer, padding rows included, is the host array buf (panel_rows(n) x p):
+        for tests that place values in the padding rows and read `buf` back raw."""
+        buf = np.ascontiguousarray(buf, dtype=np.float64)
+        if buf.ndim != 2 or buf.shape[0] != panel_rows(n):
+            raise ValueError(f"from_raw_buffer: {buf.shape} is not ({panel_rows(n)}, p) for n = {n}")
+        P = cls.__new__(cls)
+        P.ctx, P.n, P.p, P.n_pad = ctx, n, buf.shape[1], buf.shape[0]
+        P.buf = ctx.array(buf.ravel())
         return P
 
     def to_host(self) -> np.ndarray:

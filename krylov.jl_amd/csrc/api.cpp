@@ -53,6 +53,22 @@ int khip_test_csr_arrays(const khip_csr *A, int32_t *rowptr_out, int32_t *col_ou
   return KHIP_OK;
 }
 
+// test-only (include/krylov_hip_test.h): the SpMM pin -- tile records, window metadata, what the last product launched
+int khip_test_csr_tile_records(const khip_csr *A, int64_t *out16, double *reuse, char *meta_out, int64_t meta_bytes, int32_t *direct_out,
+                               int64_t direct_cap) {
+  KHIP_REQUIRE(A && out16, "test_csr_tile_records: null argument");
+  return khip::tile_records_host(A, out16, reuse, meta_out, meta_bytes, direct_out, direct_cap);
+}
+int khip_test_csr_window_info(const khip_csr *A, int *win_L, int64_t *groups, int64_t *flagged) {
+  KHIP_REQUIRE(A && win_L && groups && flagged, "test_csr_window_info: null argument");
+  return khip::window_info_host(A, win_L, groups, flagged);
+}
+int khip_test_spmm_last_launch(const khip_ctx *ctx, int64_t *out24) {
+  KHIP_REQUIRE(ctx && out24, "test_spmm_last_launch: null argument");
+  for (int i = 0; i < khip::kSpmmLastWords; ++i) out24[i] = ctx->spmm_last[i];
+  return KHIP_OK;
+}
+
 void khip_version(int *major, int *minor) {
   if (major) *major = KHIP_VERSION_MAJOR;
   if (minor) *minor = KHIP_VERSION_MINOR;

@@ -613,6 +613,12 @@ static void launch_window(khip_ctx *ctx, const khip_csr *A, const SpmvArgs &a, i
   }
   const bool dist = a.ghost != a.x, pow2 = p == 2 * L;
   const dim3 gd((unsigned)grid), bd(kBlock);
+  {                                      // test-only record (khip_test_spmm_last_launch)
+    int64_t *r = ctx->spmm_last;
+    r[kSlFamily] = 3; r[kSlL] = L; r[kSlGrid] = grid; r[kSlLaunches] = 1; r[kSlSweepS] = w.sweep_S; r[kSlSweepW] = w.sweep_W;
+    r[kSlSweepK] = w.sweep_K; r[kSlSweepCols] = w.sweep_cols; r[kSlDist] = dist ? 1 : 0; r[kSlPow2] = pow2 ? 1 : 0; r[kSlBlock] = kBlock;
+    r[kSlLds] = (int64_t)lds;
+  }
   if (lds > 64 * 1024) {                 // beyond the default dynamic-LDS limit: raise it for the instantiation about to run
     const void *fn = dist ? (pow2 ? (const void *)spmm_window_kernel<L, true, true> : (const void *)spmm_window_kernel<L, true, false>)
                           : (pow2 ? (const void *)spmm_window_kernel<L, false, true> : (const void *)spmm_window_kernel<L, false, false>);
@@ -626,6 +632,8 @@ static void launch_window(khip_ctx *ctx, const khip_csr *A, const SpmvArgs &a, i
 
 int launch_spmm(khip_ctx *ctx, const khip_csr *A, const double *X, double *Y, int p) {
   if (p < 1 || p > 64) { set_error("spmm: 1 <= p <= 64 required (got %d)", p); return KHIP_ERR_INVALID; }
+  for (int i = 0; i < kSpmmLastWords; ++i) ctx->spmm_last[i] = 0;       // test-only record of this product's launches
+  ctx->spmm_last[kSlP] = p; ctx->spmm_last[kSlNumCu] = ctx->num_cu;
   SpmvArgs a;
   a.hole_lo = INT64_MAX; a.hole_len = 0;
   a.rowptr = A->rowptr; a.blockptr = nullptr; a.col = A->col; a.val = A->val; a.x = X; a.ghost = X; a.y = Y;
@@ -714,6 +722,11 @@ int launch_spmm(khip_ctx *ctx, const khip_csr *A, const double *X, double *Y, in
         return KHIP_OK;
       }
     }
+    {
+      int64_t *r = ctx->spmm_last;
+      r[kSlFamily] = 2; r[kSlL] = L; r[kSlGrid] = grid2; r[kSlLaunches] = 1; r[kSlSweepS] = a.sweep_s; r[kSlSweepW] = a.sweep_s > 0 ? a.sweep_w : 0;
+      r[kSlDist] = a.ghost != a.x ? 1 : 0; r[kSlBlock] = kBlock;
+    }
     switch (L) {
       case 2: hipLaunchKernelGGL((spmm2_kernel<2>), dim3(grid2), dim3(kBlock), 0, ctx->stream, a, p); break;
       case 4: hipLaunchKernelGGL((spmm2_kernel<4>), dim3(grid2), dim3(kBlock), 0, ctx->stream, a, p); break;
@@ -723,6 +736,11 @@ int launch_spmm(khip_ctx *ctx, const khip_csr *A, const double *X, double *Y, in
     }
     KHIP_CHECK_HIP(hipGetLastError());
     return KHIP_OK;
+  }
+  {
+    int64_t *r = ctx->spmm_last;
+    r[kSlFamily] = 1; r[kSlL] = P; r[kSlGrid] = grid; r[kSlLaunches] = 1; r[kSlSweepS] = a.sweep_s; r[kSlSweepW] = a.sweep_s > 0 ? a.sweep_w : 0;
+    r[kSlDist] = a.ghost != a.x ? 1 : 0; r[kSlBlock] = kBlock;
   }
   switch (P) {
     case 4: hipLaunchKernelGGL((spmm_kernel<4>), dim3(grid), dim3(kBlock), 0, ctx->stream, a, p); break;
@@ -1500,6 +1518,19 @@ int spmm_window_build(khip_ctx *ctx, khip_csr *A, int L) {
     csr_free_window(A);
     A->win_L = -L;
   }
+  return KHIP_OK;
+}
+
+// test-only (khip_test_csr_window_info): lane count the window metadata was built for, its row groups and the flagged ones
+int window_info_host(const khip_csr *A, int *win_L, int64_t *groups, int64_t *flagged) {
+  *win_L = A->win_L; *groups = 0; *flagged = 0;
+  if (A->win_L <= 0) return KHIP_OK;
+  const int rpb = kBlock / A->win_L;
+  *groups = (A->m + rpb - 1) / rpb;
+  std::vector<int32_t> fl((size_t)*groups);
+  if (A->ctx) KHIP_CHECK_HIP(hipStreamSynchronize(A->ctx->stream));
+  KHIP_CHECK_HIP(hipMemcpy(fl.data(), A->win_flag, sizeof(int32_t) * fl.size(), hipMemcpyDeviceToHost));
+  for (int32_t f : fl) *flagged += f != 0 ? 1 : 0;
   return KHIP_OK;
 }
 

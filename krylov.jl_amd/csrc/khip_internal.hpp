@@ -163,6 +163,16 @@ struct LanczosEpi {
 
 }  // namespace khip
 
+namespace khip {
+// words of khip_ctx::spmm_last
+enum SpmmLast {
+  kSlFamily = 0,   // 0 nothing yet, 1 spmm_kernel, 2 spmm2_kernel, 3 spmm_window_kernel, 4 spmm_tile_kernel, 5 spmm_tile2_kernel
+  kSlL, kSlNL, kSlDbuf, kSlAhead, kSlRunLen, kSlGrid, kSlXcd, kSlLaunches, kSlDirect,
+  kSlSweepS, kSlSweepW, kSlSweepK, kSlSweepCols, kSlNt, kSlDist, kSlP, kSlPow2, kSlBlock, kSlLds, kSlNumCu,
+  kSpmmLastWords = 24
+};
+}  // namespace khip
+
 struct khip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -179,6 +189,9 @@ struct khip_ctx {
   hipEvent_t ev_red = nullptr;         // comm_allreduce_dd_device_begin / _end (all-reduce on the communication stream)
   bool allreduce_pending = false;      // a _begin on this context still waits for its _end
   int num_cu = 256;
+  // test-only record of what the last khip_spmm on this context launched (khip_test_spmm_last_launch, include/krylov_hip_test.h):
+  // written from the variables the launch itself uses, read by nothing but the export
+  int64_t spmm_last[khip::kSpmmLastWords] = {};
   // reduction scratch (grown on demand by ensure_reduction_scratch)
   khip::dd *partials = nullptr;        // [kMaxNout][red_cap1]  one per wave of the streaming kernel
   khip::dd *partials2 = nullptr;       // [kMaxNout][256]       one per workgroup of the finish kernel
@@ -395,6 +408,9 @@ int launch_diagonal(khip_ctx *ctx, const khip_csr *A, double *diag);
 void csr_free_templates(khip_csr *A);
 void csr_free_window(khip_csr *A);
 void csr_free_tiles(khip_csr *A);                  // spmm_tile.hip
+int tile_records_host(const khip_csr *A, int64_t *out16, double *reuse, char *meta_out, int64_t meta_bytes, int32_t *direct_out,
+                      int64_t direct_cap);              // spmm_tile.hip (test-only export)
+int window_info_host(const khip_csr *A, int *win_L, int64_t *groups, int64_t *flagged);   // csr_aux.hip (test-only export)
 int spmm_tile_build(khip_ctx *ctx, khip_csr *A);   // spmm_tile.hip: sets A->tile_state to 1 or -1
 void csr_free_delta(khip_csr *A);                  // coldelta.hip
 int csr_build_delta(khip_ctx *ctx, khip_csr *A, int rows);   // coldelta.hip: sets A->delta_state to 1 or -1

@@ -1139,6 +1139,8 @@ int spmm_tile_build(khip_ctx *ctx, khip_csr *A) {
   struct Scratch { int32_t *&c; unsigned long long *&s; ~Scratch() { (void)hipFree(c); (void)hipFree(s); } } scratch{cnt, stat};
   KHIP_CHECK_HIP(hipMalloc(&stat, NSTAT * sizeof(unsigned long long)));
   // candidate orders: identity, and the grid tiles when csr_finalize saw a line / plane structure
+  // (line_rows >= 4 never decides: csr_finalize takes the line distance from the SECOND cluster of offsets, which starts past
+  // 2 x 1 + 2, so a handle reports 0 or at least 5 -- tests/spmm_model.py holds the 3 / 4 edge on the rule alone)
   const bool grid_ok = A->line_rows >= 4 && A->line_rows < A->m &&
                        (A->plane_rows <= A->line_rows || (A->plane_rows % A->line_rows == 0 && A->plane_rows / A->line_rows >= 4));
   TileOrder best{};
@@ -1219,6 +1221,38 @@ int spmm_tile_build(khip_ctx *ctx, khip_csr *A) {
   A->tile_grid = best.s1 != 0 ? 1 : 0;
   A->tile_direct = n_direct;
   A->tile_reuse = best_score;
+  return KHIP_OK;
+}
+
+// test-only record (khip_test_spmm_last_launch): the variables of the launch about to be issued
+static void tile_record_launch(khip_ctx *ctx, const khip_csr *A, const TileArgs &w, int family, int L, int NL, int64_t grid, int block,
+                               size_t lds, bool nt, bool dist) {
+  int64_t *r = ctx->spmm_last;
+  r[kSlFamily] = family; r[kSlL] = L; r[kSlNL] = NL; r[kSlDbuf] = w.dbuf; r[kSlAhead] = w.ahead; r[kSlRunLen] = w.run_len;
+  r[kSlGrid] = grid; r[kSlXcd] = w.exp & (8 | 128); r[kSlLaunches] += 1; r[kSlDirect] = A->tile_direct;
+  r[kSlNt] = nt ? 1 : 0; r[kSlDist] = dist ? 1 : 0; r[kSlBlock] = block; r[kSlLds] = (int64_t)lds;
+}
+
+// test-only (khip_test_csr_tile_records): what spmm_tile_build left on the handle
+int tile_records_host(const khip_csr *A, int64_t *out16, double *reuse, char *meta_out, int64_t meta_bytes, int32_t *direct_out,
+                      int64_t direct_cap) {
+  const bool on = A->tile_state == 1;
+  const int64_t v[16] = {A->tile_state, on ? A->tile_cap : 0, on ? A->tile_stride : 0, on ? A->tile_groups : 0, on ? A->tile_run_len : 0,
+                         on ? A->tile_runs : 0, on ? A->tile_ahead : 0, on ? A->tile_grid : 0, on ? A->tile_direct : 0, A->line_rows,
+                         A->plane_rows, A->m, A->n, A->nnz, A->n_ghost, A->band};
+  for (int i = 0; i < 16; ++i) out16[i] = v[i];
+  if (reuse) *reuse = on ? A->tile_reuse : 0.0;
+  if (!on) return KHIP_OK;
+  if (A->ctx) KHIP_CHECK_HIP(hipStreamSynchronize(A->ctx->stream));
+  if (meta_out) {
+    const int64_t need = A->tile_groups * (int64_t)A->tile_stride;
+    if (meta_bytes < need) { set_error("test_csr_tile_records: %lld bytes of records, room for %lld", (long long)need, (long long)meta_bytes); return KHIP_ERR_INVALID; }
+    KHIP_CHECK_HIP(hipMemcpy(meta_out, A->tile_meta, (size_t)need, hipMemcpyDeviceToHost));
+  }
+  if (direct_out && A->tile_direct > 0) {
+    if (direct_cap < A->tile_direct) { set_error("test_csr_tile_records: %lld flagged groups, room for %lld", (long long)A->tile_direct, (long long)direct_cap); return KHIP_ERR_INVALID; }
+    KHIP_CHECK_HIP(hipMemcpy(direct_out, A->tile_direct_list, sizeof(int32_t) * (size_t)A->tile_direct, hipMemcpyDeviceToHost));
+  }
   return KHIP_OK;
 }
 
@@ -1309,6 +1343,7 @@ static int launch_tile_L(khip_ctx *ctx, const khip_csr *A, const SpmvArgs &a, in
     if (grid2 > w.groups) grid2 = w.groups;
     if (grid2 >= 64) grid2 &= ~(int64_t)7;
     const dim3 gd2((unsigned)grid2), bd2(128);
+    tile_record_launch(ctx, A, w, 5, L >= 4 ? L : 4, NL, grid2, 128, lds1, false, dist);
 #define KHIP_TILE2(D, N)                                                                                                     \
   do {                                                                                                                       \
     if (w.ahead) hipLaunchKernelGGL((spmm_tile2_kernel<(L >= 4 ? L : 4), D, N, true>), gd2, bd2, lds1, ctx->stream, a, w);   \
@@ -1337,6 +1372,7 @@ static int launch_tile_L(khip_ctx *ctx, const khip_csr *A, const SpmvArgs &a, in
     if (nt) KHIP_TILE_LAUNCH1(D, N, true); else KHIP_TILE_LAUNCH1(D, N, false);                                         \
   } while (0)
   const bool nt = ctx->tune.spmm_tile_nt != 0;
+  tile_record_launch(ctx, A, w, 4, L, NL, grid, 64, lds, nt, dist);
   if (dist) {
     switch (NL) { case 1: KHIP_TILE_LAUNCH(true, 1); break; case 2: KHIP_TILE_LAUNCH(true, 2); break; case 3: KHIP_TILE_LAUNCH(true, 3); break; default: KHIP_TILE_LAUNCH(true, 4); break; }
   } else {
@@ -1363,6 +1399,8 @@ int launch_spmm_tile(khip_ctx *ctx, const khip_csr *A, const SpmvArgs &a, int p,
     for (int c = 0; c < p / 16; ++c) KHIP_TRY(launch_tile_L<4>(ctx, A, a, gshift, 128 * c));
     return KHIP_OK;
   }
+  // (the two errors below guard callers other than khip_spmm: launch_spmm asks `fits` and `p <= 32 || slices` before it comes here,
+  // so p = 64 without slices goes to the window / direct kernels and neither text can be met through the public product)
   if ((size_t)A->tile_cap * 8 * (size_t)p > (size_t)160 * 1024) { set_error("spmm_tile: window of %d panel rows x %d columns exceeds the LDS", A->tile_cap, p); return KHIP_ERR_UNSUPPORTED; }
   switch (p) {
     case 8: return launch_tile_L<2>(ctx, A, a, 6, 0);
