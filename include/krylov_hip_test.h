@@ -97,6 +97,15 @@ int khip_test_csr_tile_records(const khip_csr *A, int64_t *out16, double *reuse,
 int khip_test_csr_window_info(const khip_csr *A, int *win_L, int64_t *groups, int64_t *flagged);
 int khip_test_spmm_last_launch(const khip_ctx *ctx, int64_t *out24);
 
+/* test-only, host-only: the launch plan of the streaming vector kernels and the instantiation their dispatcher picks for it
+ * (csrc/vec_launch.hpp: vec_plan, vec_dispatch -- the two functions every launcher calls; no device, nothing is allocated).
+ * ptrs: up to 8 vector addresses as integers, 0 = absent; extra_aligned: what a launcher says of the vectors of a device table;
+ * u: accesses per lane; scalar_path_nt: 0 = the 8-byte path has no non-temporal instantiation (the solvers' fused passes),
+ * 1 = it follows the plan (blas1.hip).  out7 = workgroups g, v2, nt, comp of the plan, then the (VEC, NT, COMP) the dispatcher
+ * hands to its callable.  KHIP_ERR_INVALID with "vector too long for one launch" when g does not fit a launch. */
+int khip_test_vec_plan(int64_t n, const uint64_t *ptrs, int nptrs, int extra_aligned, int u, int nt_min_elems, int compensated,
+                       int scalar_path_nt, int64_t *out7);
+
 #ifdef __cplusplus
 }
 #endif

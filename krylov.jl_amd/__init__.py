@@ -271,6 +271,7 @@ SIGNATURES = {
     "khip_test_csr_window_info": (_int, [_vp, C.POINTER(_int), C.POINTER(_i64), C.POINTER(_i64)]),
     "khip_test_spmm_last_launch": (_int, [_vp, C.POINTER(_i64)]),
     "khip_test_set_halo_self": (_int, [_vp, _int]),
+    "khip_test_vec_plan": (_int, [_i64, C.POINTER(C.c_uint64), _int, _int, _int, _int, _int, _int, C.POINTER(_i64)]),
     "khip_test_sym_givens": (_int, [C.c_double, C.c_double, c_double_p, c_double_p, c_double_p]),
     "khip_test_roots_quadratic": (_int, [C.c_double, C.c_double, C.c_double, _int, c_double_p, c_double_p]),
     "khip_test_to_boundary": (_int, [_vp, _i64, _vp, _vp, C.c_double, _int, c_double_p, c_double_p]),

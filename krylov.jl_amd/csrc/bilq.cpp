@@ -17,16 +17,10 @@
 #include <chrono>
 #include <utility>
 
-#include "device_reduce.hpp"
 #include "solver_host.hpp"
+#include "vec_launch.hpp"
 
 using namespace khip;
-
-namespace {
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-}  // namespace
 
 namespace khip {   // (named, not anonymous: stable kernel names in traces)
 
@@ -45,7 +39,7 @@ __global__ __launch_bounds__(kBlock) void bilq_p1_kernel(int64_t n, const BilqDe
   const double ng = -st->gamma, nb = -st->beta;
   dd acc[1] = {dd{0.0, 0.0}};
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     const T qv = ldg<NT>(reinterpret_cast<const T *>(q) + i);
     const T pv = ldg<NT>(reinterpret_cast<const T *>(p) + i);
@@ -63,7 +57,7 @@ __global__ __launch_bounds__(kBlock) void bilq_p1_kernel(int64_t n, const BilqDe
     stg<false>(qo, reinterpret_cast<T *>(q) + i);                       // q, p are read again by P2
     stg<false>(po, reinterpret_cast<T *>(p) + i);
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     const double qn = fma(ng, v_prev[t], q[t]);
     q[t] = qn;
@@ -82,7 +76,7 @@ __global__ __launch_bounds__(kBlock) void bilq_p2_kernel(int64_t n, const BilqDe
   const double na = -st->alpha;
   dd acc[1] = {dd{0.0, 0.0}};
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     const T qv = ldg<NT>(reinterpret_cast<const T *>(q) + i);
     const T pv = ldg<NT>(reinterpret_cast<const T *>(p) + i);
@@ -100,7 +94,7 @@ __global__ __launch_bounds__(kBlock) void bilq_p2_kernel(int64_t n, const BilqDe
     stg<false>(qo, reinterpret_cast<T *>(q) + i);                       // q, p are read again by P3
     stg<false>(po, reinterpret_cast<T *>(p) + i);
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     const double qn = fma(na, v[t], q[t]);
     const double pn = fma(na, u[t], p[t]);
@@ -123,7 +117,7 @@ __global__ __launch_bounds__(kBlock) void bilq_p3_kernel(int64_t n, const BilqDe
   const bool divide = st->pq != 0.0;
   dd acc[2] = {dd{0.0, 0.0}, dd{0.0, 0.0}};
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     const T vv = ldg<false>(reinterpret_cast<const T *>(v) + i);       // v is the next iteration's v_prev
     T xo = {}, dv;
@@ -161,7 +155,7 @@ __global__ __launch_bounds__(kBlock) void bilq_p3_kernel(int64_t n, const BilqDe
     stg<false>(vo, reinterpret_cast<T *>(v_next) + i);                  // read by the next products
     stg<false>(uo, reinterpret_cast<T *>(u_next) + i);
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     const double ve = v[t];
     if (first) {
@@ -185,71 +179,37 @@ __global__ __launch_bounds__(kBlock) void bilq_p3_kernel(int64_t n, const BilqDe
 
 namespace {
 
-struct Launch {
-  int64_t g;
-  bool v2, nt, comp;
-};
-int plan(khip_ctx *ctx, int64_t n, std::initializer_list<const void *> ptrs, int nout, Launch *L) {
-  bool al = n >= 2;
-  for (const void *p : ptrs) if (p && !aligned16(p)) al = false;
-  L->v2 = al;
-  L->nt = n >= (int64_t)ctx->tune.nt_min_elems;
-  L->comp = ctx->tune.compensated != 0;
-  const int64_t nvec = al ? n / 2 : n;
-  int64_t t = (nvec + kBlock - 1) / kBlock;
-  L->g = t < 1 ? 1 : t;
-  if (L->g > 0x7fffffffLL) { set_error("vector too long for one launch"); return KHIP_ERR_INVALID; }
-  return ensure_reduction_scratch(ctx, L->g * kWavesPerBlock, nout);
-}
-
-#define KHIP_BQ_LAUNCH(KERNEL, ...)                                                                                         \
-  do {                                                                                                                      \
-    const dim3 grid((unsigned)L.g), blk(kBlock);                                                                            \
-    if (L.v2) {                                                                                                             \
-      if (L.nt) { if (L.comp) hipLaunchKernelGGL((KERNEL<2, true, true>), grid, blk, 0, ctx->stream, __VA_ARGS__);          \
-                  else hipLaunchKernelGGL((KERNEL<2, true, false>), grid, blk, 0, ctx->stream, __VA_ARGS__); }              \
-      else      { if (L.comp) hipLaunchKernelGGL((KERNEL<2, false, true>), grid, blk, 0, ctx->stream, __VA_ARGS__);         \
-                  else hipLaunchKernelGGL((KERNEL<2, false, false>), grid, blk, 0, ctx->stream, __VA_ARGS__); }             \
-    } else {                                                                                                                \
-      if (L.comp) hipLaunchKernelGGL((KERNEL<1, false, true>), grid, blk, 0, ctx->stream, __VA_ARGS__);                     \
-      else hipLaunchKernelGGL((KERNEL<1, false, false>), grid, blk, 0, ctx->stream, __VA_ARGS__);                           \
-    }                                                                                                                       \
-    KHIP_CHECK_HIP(hipGetLastError());                                                                                      \
-  } while (0)
+constexpr ScalarPathNT kScalarNT = ScalarPathNT::never;
 
 int launch_p1(khip_ctx *ctx, int64_t n, const BilqDevState *st, const double *v_prev, const double *u_prev, const double *u, double *q,
               double *p, int slot) {
-  Launch L;
-  KHIP_TRY(plan(ctx, n, {v_prev, u_prev, u, q, p}, 1, &L));
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {v_prev, u_prev, u, q, p}, &L, 1));
   RedArgs ra = make_red_args(ctx, slot);
-  KHIP_BQ_LAUNCH(bilq_p1_kernel, n, st, v_prev, u_prev, u, q, p, ra);
-  return launch_finish(ctx, L.g * kWavesPerBlock, 1, slot);
+  vec_dispatch<kScalarNT>(L, [&](auto V, auto N, auto C) {
+    hipLaunchKernelGGL((bilq_p1_kernel<V, N, C>), L.grid(), dim3(kBlock), 0, ctx->stream, n, st, v_prev, u_prev, u, q, p, ra); });
+  KHIP_CHECK_HIP(hipGetLastError());
+  return launch_finish(ctx, L.waves(), 1, slot);
 }
 int launch_p2(khip_ctx *ctx, int64_t n, const BilqDevState *st, const double *v, const double *u, double *q, double *p, int slot) {
-  Launch L;
-  KHIP_TRY(plan(ctx, n, {v, u, q, p}, 1, &L));
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {v, u, q, p}, &L, 1));
   RedArgs ra = make_red_args(ctx, slot);
-  KHIP_BQ_LAUNCH(bilq_p2_kernel, n, st, v, u, q, p, ra);
-  return launch_finish(ctx, L.g * kWavesPerBlock, 1, slot);
+  vec_dispatch<kScalarNT>(L, [&](auto V, auto N, auto C) {
+    hipLaunchKernelGGL((bilq_p2_kernel<V, N, C>), L.grid(), dim3(kBlock), 0, ctx->stream, n, st, v, u, q, p, ra); });
+  KHIP_CHECK_HIP(hipGetLastError());
+  return launch_finish(ctx, L.waves(), 1, slot);
 }
 int launch_p3(khip_ctx *ctx, int64_t n, const BilqDevState *st, double *x, double *dbar, const double *v, const double *u,
               const double *q, const double *p, double *v_next, double *u_next, bool first, int slot) {
-  Launch L;
-  KHIP_TRY(plan(ctx, n, {x, dbar, v, u, q, p, v_next, u_next}, 2, &L));
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {x, dbar, v, u, q, p, v_next, u_next}, &L, 2));
   RedArgs ra = make_red_args(ctx, slot);
-  KHIP_BQ_LAUNCH(bilq_p3_kernel, n, st, x, dbar, v, u, q, p, v_next, u_next, first ? 1 : 0, ra);
-  return launch_finish(ctx, L.g * kWavesPerBlock, 2, slot);
-}
-#undef KHIP_BQ_LAUNCH
-
-// y = op x outside the sequence's epilogues: the product carries the sequence number only
-int product(khip_ctx *ctx, const khip_operator *op, const double *x, double *y) {
-  const SeqCtl keep = ctx->ctl;
-  ctx->ctl.epi = EPI_NONE;
-  ctx->ctl.epi_state = nullptr;
-  const int rc = apply_op(ctx, op, x, y);
-  ctx->ctl = keep;
-  return rc;
+  vec_dispatch<kScalarNT>(L, [&](auto V, auto N, auto C) {
+    hipLaunchKernelGGL((bilq_p3_kernel<V, N, C>), L.grid(), dim3(kBlock), 0, ctx->stream, n, st, x, dbar, v, u, q, p, v_next, u_next,
+                       first ? 1 : 0, ra); });
+  KHIP_CHECK_HIP(hipGetLastError());
+  return launch_finish(ctx, L.waves(), 2, slot);
 }
 
 }  // namespace
@@ -267,12 +227,6 @@ struct khip_bilq_workspace {
 };
 
 namespace {
-
-int upload(khip_bilq_workspace *ws, const BilqDevState &s) {   // pinned[2] is the staging copy of the host-driven loop
-  ws->loop.pinned[2] = s;
-  KHIP_CHECK_HIP(hipMemcpyAsync(ws->loop.dev, &ws->loop.pinned[2], sizeof(BilqDevState), hipMemcpyHostToDevice, ws->ctx->stream));
-  return KHIP_OK;
-}
 
 void verbose_row(const khip_options &o, long long iter, double alpha, double rNorm, double t0) {     // src/bilq.jl:201, :374
   klogf(o.log_fd, "%5lld  %8.1e  %7.1e  %.2fs\n", iter, alpha, rNorm, now_s() - t0);
@@ -468,12 +422,12 @@ int khip_bilq_solve(khip_bilq_workspace *ws, const khip_operator *A, const khip_
   auto running = [&] { return !(s.solved_lq || s.solved_cg || tired || s.breakdown || user_exit || overtimed); };
   // q <- M A N v and p <- N' A' M' u (:234-242)
   auto products = [&](const double *vk, const double *uk, double *qk, double *pk) -> int {
-    if (!NisI) KHIP_TRY(product(ctx, N, vk, ws->s));
-    KHIP_TRY(product(ctx, A, NisI ? vk : ws->s, MisI ? qk : ws->t));
-    if (!MisI) KHIP_TRY(product(ctx, M, ws->t, qk));
-    if (!MisI) KHIP_TRY(product(ctx, Mt, uk, ws->t));
-    KHIP_TRY(product(ctx, At, MisI ? uk : ws->t, NisI ? pk : ws->s));
-    if (!NisI) KHIP_TRY(product(ctx, Nt, ws->s, pk));
+    if (!NisI) KHIP_TRY(apply_op_no_epilogue(ctx, N, vk, ws->s));
+    KHIP_TRY(apply_op_no_epilogue(ctx, A, NisI ? vk : ws->s, MisI ? qk : ws->t));
+    if (!MisI) KHIP_TRY(apply_op_no_epilogue(ctx, M, ws->t, qk));
+    if (!MisI) KHIP_TRY(apply_op_no_epilogue(ctx, Mt, uk, ws->t));
+    KHIP_TRY(apply_op_no_epilogue(ctx, At, MisI ? uk : ws->t, NisI ? pk : ws->s));
+    if (!NisI) KHIP_TRY(apply_op_no_epilogue(ctx, Nt, ws->s, pk));
     return KHIP_OK;
   };
   // the end of an iteration on the host-driven loops (:347, :367-374)
@@ -533,19 +487,19 @@ int khip_bilq_solve(khip_bilq_workspace *ws, const khip_operator *A, const khip_
     while (running()) {
       const int64_t k = ++iter;
       K(products(v, u, q, p));
-      K(upload(ws, s));
+      K(ws->loop.upload(ctx, s));
       int slot = take_slots(ctx, 1);
       K(launch_p1(ctx, n, ws->loop.dev, v_prev, u_prev, u, q, p, slot));
       double uq;
       K(fetch_results(ctx, slot, 1, &uq));
       bilq_step_a(s, uq);
-      K(upload(ws, s));
+      K(ws->loop.upload(ctx, s));
       slot = take_slots(ctx, 1);
       K(launch_p2(ctx, n, ws->loop.dev, v, u, q, p, slot));
       double pq;
       K(fetch_results(ctx, slot, 1, &pq));
       bilq_step_b(s, pq, k);
-      K(upload(ws, s));
+      K(ws->loop.upload(ctx, s));
       slot = take_slots(ctx, 2);
       K(launch_p3(ctx, n, ws->loop.dev, x, dbar, v, u, q, p, v_prev, u_prev, k == 1, slot));
       double r[2];

@@ -8,7 +8,7 @@
 // copy 6.7, axpy 6.5, dot 7.1 TB/s versus 4.2-4.5 TB/s for 2048-workgroup grid-stride loops.
 // Algorithmic bytes per element: dot 16 (8 if x === y), nrm2 8, axpy/axpby 24, copy/divcopy/
 // scalcopy 16, fill 8, scal 16, reflect 32; fused: axpy2_dot 48, axpy_dev_dot 24(+8), waxpy 24.
-#include "device_reduce.hpp"
+#include "vec_launch.hpp"
 
 namespace khip {
 
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(kBlock) void map_kernel(int64_t n, double a, double
                                                      double *w) {
   using T = typename VecT<VEC>::type;
   const int64_t nvec = n / VEC;
-  const int64_t base = (int64_t)blockIdx.x * (kBlock * U) + threadIdx.x;
+  const int64_t base = lane_index<U>();
   const T *X = reinterpret_cast<const T *>(x);
   T *Y = reinterpret_cast<T *>(y);
   T *W = reinterpret_cast<T *>((OP == OP_WAXPY || OP == OP_VMUL || OP == OP_VDIV) ? w : y);
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(kBlock) void map_kernel(int64_t n, double a, double
       if (OP == OP_REF) stg<NT>(ox, XO + i);
     }
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {   // odd tail element
+  if (VEC == 2 && owns_tail(n)) {   // odd tail element
     const int64_t t = n - 1;
     double sx, sy;
     map_scalar<OP>(a, b, reads_x<OP>() ? x[t] : 0.0, reads_y<OP>() ? y[t] : 0.0, sx, sy);
@@ -96,29 +96,17 @@ __global__ __launch_bounds__(kBlock) void map_kernel(int64_t n, double a, double
   }
 }
 
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-static inline bool use_nt(khip_ctx *ctx, int64_t n) { return n >= (int64_t)ctx->tune.nt_min_elems; }
-
-static inline int64_t tiles_for(int64_t nvec, int u) {
-  int64_t t = (nvec + (int64_t)kBlock * u - 1) / ((int64_t)kBlock * u);
-  return t < 1 ? 1 : t;
-}
+// every launcher below: vec_plan for (grid, VEC, NT, COMP), vec_dispatch for the instantiation (vec_launch.hpp)
+constexpr ScalarPathNT kScalarNT = ScalarPathNT::follow;
 
 template <int OP>
 static int launch_map_op(khip_ctx *ctx, int64_t n, double a, double b, const double *x, double *y, double *w) {
   if (n <= 0) return KHIP_OK;
   constexpr bool uses_w = (OP == OP_WAXPY || OP == OP_VMUL || OP == OP_VDIV);
-  const bool v2 = (!reads_x<OP>() || aligned16(x)) && aligned16(y) && (!uses_w || aligned16(w)) && n >= 2;
-  const bool nt = use_nt(ctx, n);
-  const int64_t nvec = v2 ? n / 2 : n;
-  const int64_t g = tiles_for(nvec, 1);
-  if (g > 0x7fffffffLL) { set_error("vector too long for one launch"); return KHIP_ERR_INVALID; }
-#define KHIP_MAP(VEC, NT) \
-  hipLaunchKernelGGL((map_kernel<OP, VEC, NT, 1>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, a, b, x, y, w)
-  if (v2) { if (nt) KHIP_MAP(2, true); else KHIP_MAP(2, false); }
-  else    { if (nt) KHIP_MAP(1, true); else KHIP_MAP(1, false); }
-#undef KHIP_MAP
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {reads_x<OP>() ? x : nullptr, y, uses_w ? w : nullptr}, &L));
+  vec_dispatch_vn<kScalarNT>(L, [&](auto V, auto N) {
+    hipLaunchKernelGGL((map_kernel<OP, V, N, 1>), L.grid(), dim3(kBlock), 0, ctx->stream, n, a, b, x, y, w); });
   KHIP_CHECK_HIP(hipGetLastError());
   return KHIP_OK;
 }
@@ -149,7 +137,7 @@ __global__ __launch_bounds__(kBlock) void cg_update_kernel(int64_t n, double a, 
                                                            double *x) {
   using T = typename VecT<VEC>::type;
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     const T rv = ldg<NT>(reinterpret_cast<const T *>(r) + i);
     const T pv = ldg<NT>(reinterpret_cast<T *>(p) + i);
@@ -163,7 +151,7 @@ __global__ __launch_bounds__(kBlock) void cg_update_kernel(int64_t n, double a, 
     stg<NT>(xo, reinterpret_cast<T *>(x) + i);
     stg<NT>(po, reinterpret_cast<T *>(p) + i);
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     const double pv = p[t];
     x[t] = fma(a, pv, x[t]);
@@ -173,15 +161,10 @@ __global__ __launch_bounds__(kBlock) void cg_update_kernel(int64_t n, double a, 
 
 int launch_cg_update(khip_ctx *ctx, int64_t n, double a, double b, const double *r, double *p, double *x) {
   if (n <= 0) return KHIP_OK;
-  const bool v2 = n >= 2 && aligned16(r) && aligned16(p) && aligned16(x);
-  const bool nt = use_nt(ctx, n);
-  const int64_t g = tiles_for(v2 ? n / 2 : n, 1);
-  if (g > 0x7fffffffLL) { set_error("vector too long for one launch"); return KHIP_ERR_INVALID; }
-#define KHIP_CGU(VEC, NT) \
-  hipLaunchKernelGGL((cg_update_kernel<VEC, NT>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, a, b, r, p, x)
-  if (v2) { if (nt) KHIP_CGU(2, true); else KHIP_CGU(2, false); }
-  else    { if (nt) KHIP_CGU(1, true); else KHIP_CGU(1, false); }
-#undef KHIP_CGU
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {r, p, x}, &L));
+  vec_dispatch_vn<kScalarNT>(L, [&](auto V, auto N) {
+    hipLaunchKernelGGL((cg_update_kernel<V, N>), L.grid(), dim3(kBlock), 0, ctx->stream, n, a, b, r, p, x); });
   KHIP_CHECK_HIP(hipGetLastError());
   return KHIP_OK;
 }
@@ -197,7 +180,7 @@ __global__ __launch_bounds__(kBlock) void cgcg_update_kernel(int64_t n, const Cg
   if (seq >= st->stop_seq) return;
   const double a = st->alpha, b = st->beta;
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     const T wv = ldg<NT>(reinterpret_cast<const T *>(w) + i), rv = ldg<NT>(reinterpret_cast<T *>(r) + i);
     const T pv = ldg<NT>(reinterpret_cast<T *>(p) + i), sv = ldg<NT>(reinterpret_cast<T *>(s) + i);
@@ -217,7 +200,7 @@ __global__ __launch_bounds__(kBlock) void cgcg_update_kernel(int64_t n, const Cg
     stg<NT>(xo, reinterpret_cast<T *>(x) + i);
     stg<NT>(ro, reinterpret_cast<T *>(r) + i);
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     const double pn = fma(b, p[t], r[t]), sn = fma(b, s[t], w[t]);
     p[t] = pn; s[t] = sn;
@@ -230,15 +213,10 @@ int launch_cgcg_update(khip_ctx *ctx, int64_t n, const void *st_dev, long long s
                        double *s, double *x) {
   if (n <= 0) return KHIP_OK;
   const CgcgDevState *st = static_cast<const CgcgDevState *>(st_dev);
-  const bool v2 = n >= 2 && aligned16(w) && aligned16(r) && aligned16(p) && aligned16(s) && aligned16(x);
-  const bool nt = use_nt(ctx, n);
-  const int64_t g = tiles_for(v2 ? n / 2 : n, 1);
-  if (g > 0x7fffffffLL) { set_error("vector too long for one launch"); return KHIP_ERR_INVALID; }
-#define KHIP_L(VEC, NT) \
-  hipLaunchKernelGGL((cgcg_update_kernel<VEC, NT>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, st, seq, w, r, p, s, x)
-  if (v2) { if (nt) KHIP_L(2, true); else KHIP_L(2, false); }
-  else    { if (nt) KHIP_L(1, true); else KHIP_L(1, false); }
-#undef KHIP_L
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {w, r, p, s, x}, &L));
+  vec_dispatch_vn<kScalarNT>(L, [&](auto V, auto N) {
+    hipLaunchKernelGGL((cgcg_update_kernel<V, N>), L.grid(), dim3(kBlock), 0, ctx->stream, n, st, seq, w, r, p, s, x); });
   KHIP_CHECK_HIP(hipGetLastError());
   return KHIP_OK;
 }
@@ -254,7 +232,7 @@ __global__ __launch_bounds__(kBlock) void pcg_update_kernel(int64_t n, const Cgc
   if (seq >= st->stop_seq) return;
   const double a = st->alpha, b = st->beta;
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     const T qv = ldg<NT>(reinterpret_cast<const T *>(q) + i), zv = ldg<NT>(reinterpret_cast<T *>(z) + i);
     const T sv = ldg<NT>(reinterpret_cast<T *>(s) + i), pv = ldg<NT>(reinterpret_cast<T *>(p) + i);
@@ -280,7 +258,7 @@ __global__ __launch_bounds__(kBlock) void pcg_update_kernel(int64_t n, const Cgc
     stg<NT>(ro, reinterpret_cast<T *>(r) + i);
     stg<NT>(wo, reinterpret_cast<T *>(w) + i);
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     const double zn = fma(b, z[t], q[t]), sn = fma(b, s[t], w[t]), pn = fma(b, p[t], r[t]);
     z[t] = zn; s[t] = sn; p[t] = pn;
@@ -294,15 +272,10 @@ int launch_pcg_update(khip_ctx *ctx, int64_t n, const void *st_dev, long long se
                       double *x, double *r, double *w) {
   if (n <= 0) return KHIP_OK;
   const CgcgDevState *st = static_cast<const CgcgDevState *>(st_dev);
-  const bool v2 = n >= 2 && aligned16(q) && aligned16(z) && aligned16(s) && aligned16(p) && aligned16(x) && aligned16(r) && aligned16(w);
-  const bool nt = use_nt(ctx, n);
-  const int64_t g = tiles_for(v2 ? n / 2 : n, 1);
-  if (g > 0x7fffffffLL) { set_error("vector too long for one launch"); return KHIP_ERR_INVALID; }
-#define KHIP_L(VEC, NT) \
-  hipLaunchKernelGGL((pcg_update_kernel<VEC, NT>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, st, seq, q, z, s, p, x, r, w)
-  if (v2) { if (nt) KHIP_L(2, true); else KHIP_L(2, false); }
-  else    { if (nt) KHIP_L(1, true); else KHIP_L(1, false); }
-#undef KHIP_L
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {q, z, s, p, x, r, w}, &L));
+  vec_dispatch_vn<kScalarNT>(L, [&](auto V, auto N) {
+    hipLaunchKernelGGL((pcg_update_kernel<V, N>), L.grid(), dim3(kBlock), 0, ctx->stream, n, st, seq, q, z, s, p, x, r, w); });
   KHIP_CHECK_HIP(hipGetLastError());
   return KHIP_OK;
 }
@@ -324,7 +297,7 @@ __global__ __launch_bounds__(kBlock) void bicg_sx_kernel(int64_t n, double alpha
     alpha = st->alpha;
   }
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     const T rv = ldg<NT>(reinterpret_cast<const T *>(r) + i), vv = ldg<NT>(reinterpret_cast<const T *>(v) + i);
     const T yv = ldg<NT>(reinterpret_cast<const T *>(y) + i), xv = ldg<NT>(reinterpret_cast<T *>(x) + i);
@@ -337,7 +310,7 @@ __global__ __launch_bounds__(kBlock) void bicg_sx_kernel(int64_t n, double alpha
     stg<NT>(so, reinterpret_cast<T *>(s) + i);
     stg<NT>(xo, reinterpret_cast<T *>(x) + i);
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     const double rt = r[t], vt = v[t], yt = y[t];
     s[t] = fma(-alpha, vt, rt);
@@ -355,7 +328,7 @@ __global__ __launch_bounds__(kBlock) void bicg_p_kernel(int64_t n, double omega,
     beta = st->beta;
   }
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     const T vv = ldg<NT>(reinterpret_cast<const T *>(v) + i), rv = ldg<NT>(reinterpret_cast<const T *>(r) + i);
     const T pv = ldg<NT>(reinterpret_cast<T *>(p) + i);
@@ -367,7 +340,7 @@ __global__ __launch_bounds__(kBlock) void bicg_p_kernel(int64_t n, double omega,
     }
     stg<NT>(po, reinterpret_cast<T *>(p) + i);
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     const double p1 = fma(-omega, v[t], p[t]);
     p[t] = fma(1.0, r[t], beta * p1);
@@ -383,7 +356,7 @@ __global__ __launch_bounds__(kBlock) void bicg_xr_kernel(int64_t n, double omega
   if (st) omega = st->omega;
   dd acc[2] = {dd{0.0, 0.0}, dd{0.0, 0.0}};
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     const T sv = ldg<NT>(reinterpret_cast<const T *>(s) + i), tv = ldg<NT>(reinterpret_cast<const T *>(t) + i);
     const T zv = (z == s) ? sv : ldg<NT>(reinterpret_cast<const T *>(z) + i);
@@ -400,7 +373,7 @@ __global__ __launch_bounds__(kBlock) void bicg_xr_kernel(int64_t n, double omega
     stg<NT>(xo, reinterpret_cast<T *>(x) + i);
     stg<NT>(ro, reinterpret_cast<T *>(r) + i);
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t k = n - 1;
     const double sk = s[k], tk = t[k], zk = z[k], ck = c[k];
     x[k] = fma(omega, zk, x[k]);
@@ -416,15 +389,10 @@ int launch_bicg_sx(khip_ctx *ctx, int64_t n, double alpha, const double *r, cons
                    double *x, const void *st_dev, long long seq) {
   const BicgDevState *st = static_cast<const BicgDevState *>(st_dev);
   if (n <= 0) return KHIP_OK;
-  const bool v2 = n >= 2 && aligned16(r) && aligned16(v) && aligned16(y) && aligned16(s) && aligned16(x);
-  const bool nt = use_nt(ctx, n);
-  const int64_t g = tiles_for(v2 ? n / 2 : n, 1);
-  if (g > 0x7fffffffLL) { set_error("vector too long for one launch"); return KHIP_ERR_INVALID; }
-#define KHIP_L(VEC, NT) \
-  hipLaunchKernelGGL((bicg_sx_kernel<VEC, NT>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, alpha, st, seq, r, v, y, s, x)
-  if (v2) { if (nt) KHIP_L(2, true); else KHIP_L(2, false); }
-  else    { if (nt) KHIP_L(1, true); else KHIP_L(1, false); }
-#undef KHIP_L
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {r, v, y, s, x}, &L));
+  vec_dispatch_vn<kScalarNT>(L, [&](auto V, auto N) {
+    hipLaunchKernelGGL((bicg_sx_kernel<V, N>), L.grid(), dim3(kBlock), 0, ctx->stream, n, alpha, st, seq, r, v, y, s, x); });
   KHIP_CHECK_HIP(hipGetLastError());
   return KHIP_OK;
 }
@@ -433,15 +401,10 @@ int launch_bicg_p(khip_ctx *ctx, int64_t n, double omega, double beta, const dou
                   const void *st_dev, long long seq) {
   const BicgDevState *st = static_cast<const BicgDevState *>(st_dev);
   if (n <= 0) return KHIP_OK;
-  const bool v2 = n >= 2 && aligned16(r) && aligned16(v) && aligned16(p);
-  const bool nt = use_nt(ctx, n);
-  const int64_t g = tiles_for(v2 ? n / 2 : n, 1);
-  if (g > 0x7fffffffLL) { set_error("vector too long for one launch"); return KHIP_ERR_INVALID; }
-#define KHIP_L(VEC, NT) \
-  hipLaunchKernelGGL((bicg_p_kernel<VEC, NT>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, omega, beta, st, seq, v, r, p)
-  if (v2) { if (nt) KHIP_L(2, true); else KHIP_L(2, false); }
-  else    { if (nt) KHIP_L(1, true); else KHIP_L(1, false); }
-#undef KHIP_L
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {r, v, p}, &L));
+  vec_dispatch_vn<kScalarNT>(L, [&](auto V, auto N) {
+    hipLaunchKernelGGL((bicg_p_kernel<V, N>), L.grid(), dim3(kBlock), 0, ctx->stream, n, omega, beta, st, seq, v, r, p); });
   KHIP_CHECK_HIP(hipGetLastError());
   return KHIP_OK;
 }
@@ -450,22 +413,13 @@ int launch_bicg_xr(khip_ctx *ctx, int64_t n, double omega, const double *s, cons
                    const double *c, double *x, double *r, int slot, const void *st_dev) {
   const BicgDevState *st = static_cast<const BicgDevState *>(st_dev);
   if (n < 0) { set_error("negative length"); return KHIP_ERR_INVALID; }
-  const bool v2 = n >= 2 && aligned16(s) && aligned16(t) && aligned16(z) && aligned16(c) && aligned16(x) && aligned16(r);
-  const bool comp = ctx->tune.compensated != 0;
-  const bool nt = use_nt(ctx, n);
-  const int64_t g = tiles_for(v2 ? n / 2 : n, 1);
-  if (g > 0x7fffffffLL) { set_error("vector too long for one launch"); return KHIP_ERR_INVALID; }
-  KHIP_TRY(ensure_reduction_scratch(ctx, g * kWavesPerBlock, 2));
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {s, t, z, c, x, r}, &L, 2));
   RedArgs ra = make_red_args(ctx, slot);
-#define KHIP_L(COMP, VEC, NT) \
-  hipLaunchKernelGGL((bicg_xr_kernel<COMP, VEC, NT>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, omega, st, s, t, z, c, x, r, ra)
-#define KHIP_L2(COMP) do { if (v2) { if (nt) KHIP_L(COMP, 2, true); else KHIP_L(COMP, 2, false); } \
-                           else    { if (nt) KHIP_L(COMP, 1, true); else KHIP_L(COMP, 1, false); } } while (0)
-  if (comp) KHIP_L2(true); else KHIP_L2(false);
-#undef KHIP_L2
-#undef KHIP_L
+  vec_dispatch_comp(L, [&](auto C) { vec_dispatch_vn<kScalarNT>(L, [&](auto V, auto N) {
+    hipLaunchKernelGGL((bicg_xr_kernel<C, V, N>), L.grid(), dim3(kBlock), 0, ctx->stream, n, omega, st, s, t, z, c, x, r, ra); }); });
   KHIP_CHECK_HIP(hipGetLastError());
-  return launch_finish(ctx, g * kWavesPerBlock, 2, slot);
+  return launch_finish(ctx, L.waves(), 2, slot);
 }
 
 // Device-scalar variant for the device-resident CG loop: alpha, beta and the `solved` flag come from
@@ -479,7 +433,7 @@ __global__ __launch_bounds__(kBlock) void cg_update_dev_kernel(int64_t n, const 
   const double a = st->alpha, b = st->beta;
   const bool solved = st->solved != 0;
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     const T pv = ldg<NT>(reinterpret_cast<T *>(p) + i);
     const T xv = ldg<NT>(reinterpret_cast<T *>(x) + i);
@@ -494,7 +448,7 @@ __global__ __launch_bounds__(kBlock) void cg_update_dev_kernel(int64_t n, const 
     stg<NT>(xo, reinterpret_cast<T *>(x) + i);
     if (!solved) stg<NT>(po, reinterpret_cast<T *>(p) + i);   // (a cacheable store of p for the next SpMV's gather was measured: slower)
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     const double pv = p[t];
     x[t] = fma(a, pv, x[t]);
@@ -506,15 +460,10 @@ int launch_cg_update_dev(khip_ctx *ctx, int64_t n, const void *cg_state_dev, lon
                          double *x) {
   if (n <= 0) return KHIP_OK;
   const CgDevState *st = static_cast<const CgDevState *>(cg_state_dev);
-  const bool v2 = n >= 2 && aligned16(r) && aligned16(p) && aligned16(x);
-  const bool nt = use_nt(ctx, n);
-  const int64_t g = tiles_for(v2 ? n / 2 : n, 1);
-  if (g > 0x7fffffffLL) { set_error("vector too long for one launch"); return KHIP_ERR_INVALID; }
-#define KHIP_CGU(VEC, NT) \
-  hipLaunchKernelGGL((cg_update_dev_kernel<VEC, NT>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, st, seq, r, p, x)
-  if (v2) { if (nt) KHIP_CGU(2, true); else KHIP_CGU(2, false); }
-  else    { if (nt) KHIP_CGU(1, true); else KHIP_CGU(1, false); }
-#undef KHIP_CGU
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {r, p, x}, &L));
+  vec_dispatch_vn<kScalarNT>(L, [&](auto V, auto N) {
+    hipLaunchKernelGGL((cg_update_dev_kernel<V, N>), L.grid(), dim3(kBlock), 0, ctx->stream, n, st, seq, r, p, x); });
   KHIP_CHECK_HIP(hipGetLastError());
   return KHIP_OK;
 }
@@ -544,7 +493,7 @@ __global__ __launch_bounds__(kBlock) void cg_defer_kernel(int64_t n, const CgDev
   const bool rd_q = MODE != CGD_LIGHT, rd_x = MODE != CGD_LIGHT || solved, rd_r = MODE != CGD_FLUSH && !solved;
   const bool wr_p = MODE != CGD_LIGHT, wr_p2 = MODE == CGD_LIGHT && !solved;
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     const T pv = ldg<NT>(reinterpret_cast<T *>(p) + i);
     T qv = {}, xv = {}, rv = {};
@@ -563,7 +512,7 @@ __global__ __launch_bounds__(kBlock) void cg_defer_kernel(int64_t n, const CgDev
     if (wr_p) stg<NT>(po, reinterpret_cast<T *>(p) + i);
     if (wr_p2) stg<NT>(po, reinterpret_cast<T *>(p2) + i);
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     double sx, sp;
     cg_defer_elem<MODE>(solved, a0, a, b, rd_r ? r[t] : 0.0, p[t], rd_q ? p2[t] : 0.0, rd_x ? x[t] : 0.0, sx, sp);
@@ -577,20 +526,16 @@ int launch_cg_defer(khip_ctx *ctx, int64_t n, int mode, const void *cg_state_dev
                     double *p, double *p2, double *x) {
   if (n <= 0) return KHIP_OK;
   const CgDevState *st = static_cast<const CgDevState *>(cg_state_dev);
-  const bool v2 = n >= 2 && aligned16(r) && aligned16(p) && aligned16(p2) && aligned16(x);
-  const bool nt = use_nt(ctx, n);
-  const int64_t g = tiles_for(v2 ? n / 2 : n, 1);
-  if (g > 0x7fffffffLL) { set_error("vector too long for one launch"); return KHIP_ERR_INVALID; }
-#define KHIP_CGD(MODE, VEC, NT) \
-  hipLaunchKernelGGL((cg_defer_kernel<MODE, VEC, NT>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, st, seq, flush_prev, r, p, p2, x)
-#define KHIP_CGD_M(MODE) do { if (v2) { if (nt) KHIP_CGD(MODE, 2, true); else KHIP_CGD(MODE, 2, false); } \
-                              else    { if (nt) KHIP_CGD(MODE, 1, true); else KHIP_CGD(MODE, 1, false); } } while (0)
-  if (mode == CGD_LIGHT) KHIP_CGD_M(CGD_LIGHT);
-  else if (mode == CGD_HEAVY) KHIP_CGD_M(CGD_HEAVY);
-  else if (mode == CGD_FLUSH) KHIP_CGD_M(CGD_FLUSH);
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {r, p, p2, x}, &L));
+  auto launch = [&](auto MODE) {
+    vec_dispatch_vn<kScalarNT>(L, [&](auto V, auto N) {
+      hipLaunchKernelGGL((cg_defer_kernel<MODE, V, N>), L.grid(), dim3(kBlock), 0, ctx->stream, n, st, seq, flush_prev, r, p, p2, x); });
+  };
+  if (mode == CGD_LIGHT) launch(std::integral_constant<int, CGD_LIGHT>{});
+  else if (mode == CGD_HEAVY) launch(std::integral_constant<int, CGD_HEAVY>{});
+  else if (mode == CGD_FLUSH) launch(std::integral_constant<int, CGD_FLUSH>{});
   else { set_error("launch_cg_defer: unknown mode %d", mode); return KHIP_ERR_INVALID; }
-#undef KHIP_CGD_M
-#undef KHIP_CGD
   KHIP_CHECK_HIP(hipGetLastError());
   return KHIP_OK;
 }
@@ -671,7 +616,7 @@ __global__ __launch_bounds__(kBlock) void reduce_kernel(int64_t n, RedPtrs p, Re
 #pragma unroll
   for (int o = 0; o < NOUT; ++o) acc[o] = dd{0.0, 0.0};
   const int64_t nvec = n / VEC;
-  const int64_t base = (int64_t)blockIdx.x * (kBlock * U) + threadIdx.x;
+  const int64_t base = lane_index<U>();
   const T *X = reinterpret_cast<const T *>(p.x);
   const T *Y = reinterpret_cast<const T *>(p.y);
   T *Uv = reinterpret_cast<T *>(p.u);
@@ -744,7 +689,7 @@ __global__ __launch_bounds__(kBlock) void reduce_kernel(int64_t n, RedPtrs p, Re
       }
     }
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {   // odd tail element, scalar
+  if (VEC == 2 && owns_tail(n)) {   // odd tail element, scalar
     const int64_t t = n - 1;
     double xe = p.x[t];
     if (ROP == RED_DOT) acc_prod<COMP>(acc[0], xe, p.y[t]);
@@ -770,38 +715,31 @@ __global__ __launch_bounds__(kBlock) void reduce_kernel(int64_t n, RedPtrs p, Re
 template <int ROP>
 static int launch_reduce(khip_ctx *ctx, int64_t n, const RedPtrs &p, int slot) {
   if (n < 0) { set_error("negative length"); return KHIP_ERR_INVALID; }
-  const bool v2 = n >= 2 && aligned16(p.x) && (p.y == nullptr || aligned16(p.y)) && (p.u == nullptr || aligned16(p.u)) &&
-                  (p.v == nullptr || aligned16(p.v)) && (p.w == nullptr || aligned16(p.w));
-  const bool comp = ctx->tune.compensated != 0;
+  constexpr int NOUT = RedOut<ROP>::n;
   // MGS cascade (AXPYDEV): q and the basis vector just dotted are read again by the very next kernel; when both
   // fit in the 256 MiB Infinity Cache, leaving them cacheable beats streaming them (GMRES(30) at 256^3:
   // 1.91 -> 1.71 ms per inner iteration; at 384^3 it costs 2-5 %: profiles/r01h_mgs_keep.log)
   int keep = ctx->tune.mgs_keep;
   if (keep < 0) keep = (ROP == RED_AXPYDEV && (size_t)n * sizeof(double) <= (size_t)144 << 20) ? 1 : 0;
-  const bool nt = use_nt(ctx, n) && !(ROP == RED_AXPYDEV && keep == 2);
-  const int64_t nvec = v2 ? n / 2 : n;
+  const int64_t nvec = vec_pairs(n, {p.x, p.y, p.u, p.v, p.w}) ? n / 2 : n;
   // 16-byte accesses per lane: 4 for the read-only reductions of long vectors (dot 6.1 vs 5.8 TB/s, nrm2 6.1 vs 4.3),
   // 1 for the ones that also write (r -= a Ap ; r.r: 5.96 vs 5.72 TB/s) -- measured at n = 512^3, tools/archive/sweep_reduce_width.py
   constexpr bool writes = (ROP == RED_AXPY2 || ROP == RED_AXPYDEV || ROP == RED_AXPYSQ || ROP == RED_CGSETUP);
   const bool u4 = ctx->tune.red_u == 0 ? (!writes && nvec >= (int64_t)kBlock * 4 * 1024) : ctx->tune.red_u == 4;
-  const int64_t g = tiles_for(nvec, u4 ? 4 : 1);
-  if (g > 0x7fffffffLL) { set_error("vector too long for one launch"); return KHIP_ERR_INVALID; }
-  KHIP_TRY(ensure_reduction_scratch(ctx, g * kWavesPerBlock, RedOut<ROP>::n));
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {p.x, p.y, p.u, p.v, p.w}, &L, NOUT, true, u4 ? 4 : 1));
+  if (ROP == RED_AXPYDEV && keep == 2) L.nt = false;
   RedArgs ra = make_red_args(ctx, slot);
-#define KHIP_RED(COMP, VEC, NT, U) \
-  hipLaunchKernelGGL((reduce_kernel<ROP, COMP, VEC, NT, U>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, p, ra)
-#define KHIP_RED_U(COMP, VEC, NT) do { if (u4) KHIP_RED(COMP, VEC, NT, 4); else KHIP_RED(COMP, VEC, NT, 1); } while (0)
-#define KHIP_RED_NT(COMP, VEC) do { if (nt) KHIP_RED_U(COMP, VEC, true); else KHIP_RED_U(COMP, VEC, false); } while (0)
-  if (ROP == RED_AXPYDEV && nt && v2 && comp && keep == 1) {
-    if (u4) hipLaunchKernelGGL((reduce_kernel<ROP, true, 2, true, 4, true>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, p, ra);
-    else hipLaunchKernelGGL((reduce_kernel<ROP, true, 2, true, 1, true>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, p, ra);
-  } else if (comp) { if (v2) KHIP_RED_NT(true, 2); else KHIP_RED_NT(true, 1); }
-  else             { if (v2) KHIP_RED_NT(false, 2); else KHIP_RED_NT(false, 1); }
-#undef KHIP_RED_NT
-#undef KHIP_RED_U
-#undef KHIP_RED
+  if (ROP == RED_AXPYDEV && L.nt && L.v2 && L.comp && keep == 1) {
+    if (u4) hipLaunchKernelGGL((reduce_kernel<ROP, true, 2, true, 4, true>), L.grid(), dim3(kBlock), 0, ctx->stream, n, p, ra);
+    else hipLaunchKernelGGL((reduce_kernel<ROP, true, 2, true, 1, true>), L.grid(), dim3(kBlock), 0, ctx->stream, n, p, ra);
+  } else {
+    vec_dispatch_comp(L, [&](auto C) { vec_dispatch_vn<kScalarNT>(L, [&](auto V, auto N) {
+      if (u4) hipLaunchKernelGGL((reduce_kernel<ROP, C, V, N, 4>), L.grid(), dim3(kBlock), 0, ctx->stream, n, p, ra);
+      else hipLaunchKernelGGL((reduce_kernel<ROP, C, V, N, 1>), L.grid(), dim3(kBlock), 0, ctx->stream, n, p, ra); }); });
+  }
   KHIP_CHECK_HIP(hipGetLastError());
-  return launch_finish(ctx, g * kWavesPerBlock, RedOut<ROP>::n, slot);
+  return launch_finish(ctx, L.waves(), NOUT, slot);
 }
 
 int launch_dot(khip_ctx *ctx, int64_t n, const double *x, const double *y, int slot) {
@@ -850,7 +788,7 @@ __global__ __launch_bounds__(kBlock) void multi_axpy_kernel(int64_t n, int k, Mu
   using T = typename VecT<VEC>::type;
   const int64_t nvec = n / VEC;
   T *X = reinterpret_cast<T *>(x);
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     T xv = ldg<NT>(X + i);
     int j = 0;
@@ -876,7 +814,7 @@ __global__ __launch_bounds__(kBlock) void multi_axpy_kernel(int64_t n, int k, Mu
     }
     stg<NT>(xv, X + i);
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     double s = x[t];
     for (int j = 0; j < k; ++j) s = fma(ma.c[j], ma.v[j][t], s);
@@ -898,7 +836,7 @@ __global__ __launch_bounds__(kBlock) void multi_dot4_kernel(int64_t n, Dot4Ptrs 
 #pragma unroll
   for (int o = 0; o < 4; ++o) acc[o] = dd{0.0, 0.0};
   const int64_t nvec = n / VEC;
-  const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t j = lane_index();
   if (j < nvec) {
     const T xv = ldg<NT>(reinterpret_cast<const T *>(p.x) + j);
     T yv[4];
@@ -912,7 +850,7 @@ __global__ __launch_bounds__(kBlock) void multi_dot4_kernel(int64_t n, Dot4Ptrs 
         for (int e = 0; e < VEC; ++e) acc_prod<COMP>(acc[o], vget(yv[o], e), vget(xv, e));
       }
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     for (int o = 0; o < p.cnt; ++o) acc_prod<COMP>(acc[o], p.y[o][t], p.x[t]);
   }
@@ -922,27 +860,19 @@ __global__ __launch_bounds__(kBlock) void multi_dot4_kernel(int64_t n, Dot4Ptrs 
 // results[slot + i] = V_i . q for i < k (k <= kResultSlots), four per launch; the caller all-reduces and reads them
 int launch_multi_dot(khip_ctx *ctx, int64_t n, int k, const double *const *V_host, const double *q, int slot) {
   if (k <= 0) return KHIP_OK;
-  const bool comp = ctx->tune.compensated != 0;
-  const bool nt = use_nt(ctx, n);
   for (int base = 0; base < k; base += 4) {
     Dot4Ptrs p;
     p.x = q;
     p.cnt = k - base < 4 ? k - base : 4;
-    bool v2 = n >= 2 && aligned16(q);
-    for (int o = 0; o < 4; ++o) {
-      p.y[o] = o < p.cnt ? V_host[base + o] : q;
-      if (!aligned16(p.y[o])) v2 = false;
-    }
-    const int64_t g = tiles_for(v2 ? n / 2 : n, 1);
-    KHIP_TRY(ensure_reduction_scratch(ctx, g * kWavesPerBlock, 4));
+    for (int o = 0; o < 4; ++o) p.y[o] = o < p.cnt ? V_host[base + o] : q;
+    VecPlan L;
+    KHIP_TRY(vec_plan(ctx, n, {q, p.y[0], p.y[1], p.y[2], p.y[3]}, &L, 4));
     RedArgs ra = make_red_args(ctx, slot + base);
-#define KHIP_MD(COMP, VEC, NT) hipLaunchKernelGGL((multi_dot4_kernel<COMP, VEC, NT>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, p, ra)
-    if (comp) { if (v2) { if (nt) KHIP_MD(true, 2, true); else KHIP_MD(true, 2, false); } else { if (nt) KHIP_MD(true, 1, true); else KHIP_MD(true, 1, false); } }
-    else      { if (v2) { if (nt) KHIP_MD(false, 2, true); else KHIP_MD(false, 2, false); } else { if (nt) KHIP_MD(false, 1, true); else KHIP_MD(false, 1, false); } }
-#undef KHIP_MD
+    vec_dispatch_comp(L, [&](auto C) { vec_dispatch_vn<kScalarNT>(L, [&](auto V, auto N) {
+      hipLaunchKernelGGL((multi_dot4_kernel<C, V, N>), L.grid(), dim3(kBlock), 0, ctx->stream, n, p, ra); }); });
     KHIP_CHECK_HIP(hipGetLastError());
     // a finish of 4 outputs writes slot + base .. slot + base + 3; the unused ones of the last group are scratch slots
-    KHIP_TRY(launch_finish(ctx, g * kWavesPerBlock, 4, slot + base));
+    KHIP_TRY(launch_finish(ctx, L.waves(), 4, slot + base));
   }
   return KHIP_OK;
 }
@@ -955,7 +885,7 @@ __global__ __launch_bounds__(kBlock) void multi_axpy_dev_kernel(int64_t n, int k
   using T = typename VecT<VEC>::type;
   const int64_t nvec = n / VEC;
   T *X = reinterpret_cast<T *>(x);
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     T xv = ldg<NT>(X + i);
     int j = 0;
@@ -983,7 +913,7 @@ __global__ __launch_bounds__(kBlock) void multi_axpy_dev_kernel(int64_t n, int k
     }
     stg<NT>(xv, X + i);
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     double sacc = x[t];
     for (int j = 0; j < k; ++j) sacc = fma(-coef[j], mv.v[j][t], sacc);
@@ -993,23 +923,18 @@ __global__ __launch_bounds__(kBlock) void multi_axpy_dev_kernel(int64_t n, int k
 
 int launch_multi_axpy_dev(khip_ctx *ctx, int64_t n, int k, const double *coef_dev, const double *const *V_host, double *x) {
   if (n <= 0 || k <= 0) return KHIP_OK;
-  const bool nt = use_nt(ctx, n);
   for (int base = 0; base < k; base += kMultiMax) {
     const int kk = k - base < kMultiMax ? k - base : kMultiMax;
     MultiPtrs mv;
-    bool v2 = n >= 2 && aligned16(x);
+    bool aligned = true;
     for (int j = 0; j < kMultiMax; ++j) {
       mv.v[j] = j < kk ? V_host[base + j] : nullptr;
-      if (j < kk && !aligned16(mv.v[j])) v2 = false;
+      aligned = aligned && aligned16(mv.v[j]);
     }
-    const int64_t g = tiles_for(v2 ? n / 2 : n, 1);
-    if (v2) {
-      if (nt) hipLaunchKernelGGL((multi_axpy_dev_kernel<2, true>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, kk, mv, coef_dev + base, x);
-      else hipLaunchKernelGGL((multi_axpy_dev_kernel<2, false>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, kk, mv, coef_dev + base, x);
-    } else {
-      if (nt) hipLaunchKernelGGL((multi_axpy_dev_kernel<1, true>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, kk, mv, coef_dev + base, x);
-      else hipLaunchKernelGGL((multi_axpy_dev_kernel<1, false>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, kk, mv, coef_dev + base, x);
-    }
+    VecPlan L;
+    KHIP_TRY(vec_plan(ctx, n, {x}, &L, 0, aligned));
+    vec_dispatch_vn<kScalarNT>(L, [&](auto V, auto N) {
+      hipLaunchKernelGGL((multi_axpy_dev_kernel<V, N>), L.grid(), dim3(kBlock), 0, ctx->stream, n, kk, mv, coef_dev + base, x); });
     KHIP_CHECK_HIP(hipGetLastError());
   }
   return KHIP_OK;
@@ -1018,24 +943,19 @@ int launch_multi_axpy_dev(khip_ctx *ctx, int64_t n, int k, const double *coef_de
 int launch_multi_axpy(khip_ctx *ctx, int64_t n, int k, const double *coef_host, const double *const *V_host,
                       double *x) {
   if (n <= 0 || k <= 0) return KHIP_OK;
-  const bool nt = use_nt(ctx, n);
   for (int base = 0; base < k; base += kMultiMax) {
     const int kk = k - base < kMultiMax ? k - base : kMultiMax;
     MultiArgs ma;
-    bool v2 = n >= 2 && aligned16(x);
+    bool aligned = true;
     for (int j = 0; j < kMultiMax; ++j) {
       ma.v[j] = j < kk ? V_host[base + j] : nullptr;
       ma.c[j] = j < kk ? coef_host[base + j] : 0.0;
-      if (j < kk && !aligned16(ma.v[j])) v2 = false;
+      aligned = aligned && aligned16(ma.v[j]);
     }
-    const int64_t g = tiles_for(v2 ? n / 2 : n, 1);
-    if (v2) {
-      if (nt) hipLaunchKernelGGL((multi_axpy_kernel<2, true>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, kk, ma, x);
-      else hipLaunchKernelGGL((multi_axpy_kernel<2, false>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, kk, ma, x);
-    } else {
-      if (nt) hipLaunchKernelGGL((multi_axpy_kernel<1, true>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, kk, ma, x);
-      else hipLaunchKernelGGL((multi_axpy_kernel<1, false>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, kk, ma, x);
-    }
+    VecPlan L;
+    KHIP_TRY(vec_plan(ctx, n, {x}, &L, 0, aligned));
+    vec_dispatch_vn<kScalarNT>(L, [&](auto V, auto N) {
+      hipLaunchKernelGGL((multi_axpy_kernel<V, N>), L.grid(), dim3(kBlock), 0, ctx->stream, n, kk, ma, x); });
     KHIP_CHECK_HIP(hipGetLastError());
   }
   return KHIP_OK;
@@ -1115,7 +1035,7 @@ __global__ __launch_bounds__(kBlock) void divcopy_dev_kernel(int64_t n, const do
   using T = typename VecT<VEC>::type;
   const double s = sqrt(*sumsq);
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     const T xv = ldg<NT>(reinterpret_cast<const T *>(x) + i);
     T yo;
@@ -1123,22 +1043,33 @@ __global__ __launch_bounds__(kBlock) void divcopy_dev_kernel(int64_t n, const do
     for (int e = 0; e < VEC; ++e) vset(yo, e, vget(xv, e) / s);
     stg<NT>(yo, reinterpret_cast<T *>(y) + i);
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) y[n - 1] = x[n - 1] / s;
+  if (VEC == 2 && owns_tail(n)) y[n - 1] = x[n - 1] / s;
 }
 
 int launch_divcopy_dev(khip_ctx *ctx, int64_t n, const double *sumsq_dev, const double *x, double *y) {
   if (n <= 0) return KHIP_OK;
-  const bool v2 = n >= 2 && aligned16(x) && aligned16(y);
-  const bool nt = use_nt(ctx, n);
-  const int64_t g = tiles_for(v2 ? n / 2 : n, 1);
-  if (g > 0x7fffffffLL) { set_error("vector too long for one launch"); return KHIP_ERR_INVALID; }
-#define KHIP_L(VEC, NT) \
-  hipLaunchKernelGGL((divcopy_dev_kernel<VEC, NT>), dim3((unsigned)g), dim3(kBlock), 0, ctx->stream, n, sumsq_dev, x, y)
-  if (v2) { if (nt) KHIP_L(2, true); else KHIP_L(2, false); }
-  else    { if (nt) KHIP_L(1, true); else KHIP_L(1, false); }
-#undef KHIP_L
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {x, y}, &L));
+  vec_dispatch_vn<kScalarNT>(L, [&](auto V, auto N) {
+    hipLaunchKernelGGL((divcopy_dev_kernel<V, N>), L.grid(), dim3(kBlock), 0, ctx->stream, n, sumsq_dev, x, y); });
   KHIP_CHECK_HIP(hipGetLastError());
   return KHIP_OK;
 }
 
 }  // namespace khip
+
+// test-only, host-only (include/krylov_hip_test.h): the plan and the instantiation the launchers above would get
+extern "C" int khip_test_vec_plan(int64_t n, const uint64_t *ptrs, int nptrs, int extra_aligned, int u, int nt_min_elems,
+                                  int compensated, int scalar_path_nt, int64_t *out7) {
+  using namespace khip;
+  KHIP_REQUIRE(out7 && nptrs >= 0 && nptrs <= 8 && (ptrs || nptrs == 0) && u >= 1, "test_vec_plan: bad argument");
+  const void *q[8] = {};
+  for (int i = 0; i < nptrs; ++i) q[i] = reinterpret_cast<const void *>(static_cast<uintptr_t>(ptrs[i]));
+  VecPlan L;
+  KHIP_TRY(vec_plan(n, {q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7]}, extra_aligned != 0, u, nt_min_elems, compensated, &L));
+  out7[0] = L.g; out7[1] = L.v2; out7[2] = L.nt; out7[3] = L.comp;
+  auto record = [&](auto V, auto N, auto C) { out7[4] = V; out7[5] = N; out7[6] = C; };
+  if (scalar_path_nt) vec_dispatch<ScalarPathNT::follow>(L, record);
+  else vec_dispatch<ScalarPathNT::never>(L, record);
+  return KHIP_OK;
+}

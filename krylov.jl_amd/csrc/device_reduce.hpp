@@ -50,6 +50,12 @@ constexpr int kBlock = 256;            // 4 waves of 64
 constexpr int kWavesPerBlock = kBlock / 64;
 constexpr int kFinishMaxBlocks = 256;
 
+// the skeleton of a loop-free streaming kernel: a lane's first VEC-vector in its workgroup's tile of kBlock * U, and the one
+// lane that takes the odd tail element of the 16-byte path.  `VEC == 2 && owns_tail(n)` at the call: with the constant in
+// sight the compiler never emits the tail of a VEC = 1 instantiation, and the kernels keep the code they always had.
+template <int U = 1> __device__ __forceinline__ int64_t lane_index() { return (int64_t)blockIdx.x * (kBlock * U) + threadIdx.x; }
+__device__ __forceinline__ bool owns_tail(int64_t n) { return (n & 1) && blockIdx.x == 0 && threadIdx.x == 0; }
+
 __device__ __forceinline__ void two_sum(double a, double b, double &s, double &e) {
   s = a + b;
   double z = s - a;

@@ -19,16 +19,10 @@
 #include <string>
 #include <utility>
 
-#include "device_reduce.hpp"
 #include "solver_host.hpp"
+#include "vec_launch.hpp"
 
 using namespace khip;
-
-namespace {
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-}  // namespace
 
 namespace khip {   // (named, not anonymous: stable kernel names in traces)
 
@@ -44,7 +38,7 @@ __global__ __launch_bounds__(kBlock) void lzshift_p1_kernel(int64_t n, const Lan
   const double nd = -st->delta, nb = -st->beta;
   dd acc[1] = {dd{0.0, 0.0}};
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   auto one = [&](double ye, double ce, double pe) {
     double w = fma(nd, ce, ye);
     if (sub_prev) w = fma(nb, pe, w);
@@ -61,7 +55,7 @@ __global__ __launch_bounds__(kBlock) void lzshift_p1_kernel(int64_t n, const Lan
     for (int e = 0; e < VEC; ++e) vset(wo, e, one(vget(yv, e), vget(cv, e), vget(pv, e)));
     stg<false>(wo, reinterpret_cast<T *>(y) + i);                      // w is read again by P2
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     y[t] = one(y[t], cur[t], sub_prev ? prev[t] : 0.0);
   }
@@ -77,7 +71,7 @@ __global__ __launch_bounds__(kBlock) void lzshift_scale_kernel(int64_t n, const 
   const double ib = st->inv_beta;
   dd acc[1] = {dd{0.0, 0.0}};
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     const T vv = ldg<NT>(reinterpret_cast<const T *>(v) + i);
     const T mv = ldg<NT>(reinterpret_cast<const T *>(Mv) + i);
@@ -92,7 +86,7 @@ __global__ __launch_bounds__(kBlock) void lzshift_scale_kernel(int64_t n, const 
     stg<false>(vo, reinterpret_cast<T *>(v) + i);
     stg<false>(mo, reinterpret_cast<T *>(Mv) + i);
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     const double a = ib * v[t];
     v[t] = a;
@@ -117,7 +111,7 @@ __global__ __launch_bounds__(kBlock) void lzshift_p2_kernel(int64_t n, const dou
   const double ib = *inv_beta;
   const int na = act[0];
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     const T wv = ldg<NT>(reinterpret_cast<const T *>(w) + i);
     T vv;
@@ -155,7 +149,7 @@ __global__ __launch_bounds__(kBlock) void lzshift_p2_kernel(int64_t n, const dou
       }
     }
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     double v = w[t];
     if (SCALE) { v = ib * v; w[t] = v; }
@@ -175,7 +169,7 @@ __global__ __launch_bounds__(kBlock) void lzshift_init_kernel(int64_t n, int p, 
                                                              const double *src, int copy_p) {
   using T = typename VecT<VEC>::type;
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     T sv = {};
     if (copy_p) sv = ldg<NT>(reinterpret_cast<const T *>(src) + i);
@@ -185,7 +179,7 @@ __global__ __launch_bounds__(kBlock) void lzshift_init_kernel(int64_t n, int p, 
       if (copy_p) stg<NT>(sv, reinterpret_cast<T *>(tab[2 * s + 1]) + i);
     }
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     for (int s = 0; s < p; ++s) {
       tab[2 * s][t] = 0.0;
@@ -198,87 +192,49 @@ __global__ __launch_bounds__(kBlock) void lzshift_init_kernel(int64_t n, int p, 
 
 namespace {
 
-struct Launch {
-  int64_t g;
-  bool v2, nt, comp;
-};
-int plan(khip_ctx *ctx, int64_t n, std::initializer_list<const void *> ptrs, bool aligned_extra, Launch *L, bool reduce) {
-  bool al = n >= 2 && aligned_extra;
-  for (const void *p : ptrs) if (p && !aligned16(p)) al = false;
-  L->v2 = al;
-  L->nt = n >= (int64_t)ctx->tune.nt_min_elems;
-  L->comp = ctx->tune.compensated != 0;
-  const int64_t nvec = al ? n / 2 : n;
-  int64_t t = (nvec + kBlock - 1) / kBlock;
-  L->g = t < 1 ? 1 : t;
-  if (L->g > 0x7fffffffLL) { set_error("vector too long for one launch"); return KHIP_ERR_INVALID; }
-  return reduce ? ensure_reduction_scratch(ctx, L->g * kWavesPerBlock, 1) : KHIP_OK;
-}
-
-#define KHIP_LZ_LAUNCH(KERNEL, ...)                                                                                         \
-  do {                                                                                                                      \
-    const dim3 grid((unsigned)L.g), blk(kBlock);                                                                            \
-    if (L.v2) {                                                                                                             \
-      if (L.nt) { if (L.comp) hipLaunchKernelGGL((KERNEL<2, true, true>), grid, blk, 0, ctx->stream, __VA_ARGS__);          \
-                  else hipLaunchKernelGGL((KERNEL<2, true, false>), grid, blk, 0, ctx->stream, __VA_ARGS__); }              \
-      else      { if (L.comp) hipLaunchKernelGGL((KERNEL<2, false, true>), grid, blk, 0, ctx->stream, __VA_ARGS__);         \
-                  else hipLaunchKernelGGL((KERNEL<2, false, false>), grid, blk, 0, ctx->stream, __VA_ARGS__); }             \
-    } else {                                                                                                                \
-      if (L.comp) hipLaunchKernelGGL((KERNEL<1, false, true>), grid, blk, 0, ctx->stream, __VA_ARGS__);                     \
-      else hipLaunchKernelGGL((KERNEL<1, false, false>), grid, blk, 0, ctx->stream, __VA_ARGS__);                           \
-    }                                                                                                                       \
-    KHIP_CHECK_HIP(hipGetLastError());                                                                                      \
-  } while (0)
+constexpr ScalarPathNT kScalarNT = ScalarPathNT::never;
 
 int launch_p1(khip_ctx *ctx, int64_t n, const LanczosShiftDevState *st, const double *prev, const double *cur, double *y,
               bool sub_prev, bool dot, int slot) {
-  Launch L;
-  KHIP_TRY(plan(ctx, n, {sub_prev ? prev : nullptr, cur, y}, true, &L, dot));
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {sub_prev ? prev : nullptr, cur, y}, &L, dot ? 1 : 0));
   RedArgs ra = make_red_args(ctx, slot);
-  KHIP_LZ_LAUNCH(lzshift_p1_kernel, n, st, prev, cur, y, sub_prev ? 1 : 0, dot ? 1 : 0, ra);
+  vec_dispatch<kScalarNT>(L, [&](auto V, auto N, auto C) {
+    hipLaunchKernelGGL((lzshift_p1_kernel<V, N, C>), L.grid(), dim3(kBlock), 0, ctx->stream, n, st, prev, cur, y, sub_prev ? 1 : 0,
+                       dot ? 1 : 0, ra); });
+  KHIP_CHECK_HIP(hipGetLastError());
   if (!dot) return KHIP_OK;        // nothing reads the partials
-  return launch_finish(ctx, L.g * kWavesPerBlock, 1, slot);
+  return launch_finish(ctx, L.waves(), 1, slot);
 }
 int launch_scale(khip_ctx *ctx, int64_t n, const LanczosShiftDevState *st, double *v, double *Mv, int slot) {
-  Launch L;
-  KHIP_TRY(plan(ctx, n, {v, Mv}, true, &L, true));
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {v, Mv}, &L, 1));
   RedArgs ra = make_red_args(ctx, slot);
-  KHIP_LZ_LAUNCH(lzshift_scale_kernel, n, st, v, Mv, ra);
-  return launch_finish(ctx, L.g * kWavesPerBlock, 1, slot);
+  vec_dispatch<kScalarNT>(L, [&](auto V, auto N, auto C) {
+    hipLaunchKernelGGL((lzshift_scale_kernel<V, N, C>), L.grid(), dim3(kBlock), 0, ctx->stream, n, st, v, Mv, ra); });
+  KHIP_CHECK_HIP(hipGetLastError());
+  return launch_finish(ctx, L.waves(), 1, slot);
 }
-#undef KHIP_LZ_LAUNCH
 
 // tab_aligned: every x_i / p_i of the table is 16-byte aligned (checked when the table is built)
 int launch_p2(khip_ctx *ctx, int64_t n, const double *inv_beta, const int *act, const double *coef, double *const *tab,
               bool tab_aligned, double *w, bool scale) {
-  Launch L;
-  KHIP_TRY(plan(ctx, n, {w}, tab_aligned, &L, false));
-  const dim3 grid((unsigned)L.g), blk(kBlock);
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {w}, &L, 0, tab_aligned));
   const long long *stop = ctx->ctl.stop_seq;
   const long long seq = ctx->ctl.seq;
-#define KHIP_LZ_P2(VEC, NT, SC) \
-  hipLaunchKernelGGL((lzshift_p2_kernel<VEC, NT, SC>), grid, blk, 0, ctx->stream, n, inv_beta, act, coef, tab, w, stop, seq)
-  if (L.v2) {
-    if (L.nt) { if (scale) KHIP_LZ_P2(2, true, true); else KHIP_LZ_P2(2, true, false); }
-    else      { if (scale) KHIP_LZ_P2(2, false, true); else KHIP_LZ_P2(2, false, false); }
-  } else {
-    if (scale) KHIP_LZ_P2(1, false, true); else KHIP_LZ_P2(1, false, false);
-  }
-#undef KHIP_LZ_P2
+  vec_dispatch_vn<kScalarNT>(L, [&](auto V, auto N) {
+    if (scale) hipLaunchKernelGGL((lzshift_p2_kernel<V, N, true>), L.grid(), dim3(kBlock), 0, ctx->stream, n, inv_beta, act, coef, tab, w, stop, seq);
+    else hipLaunchKernelGGL((lzshift_p2_kernel<V, N, false>), L.grid(), dim3(kBlock), 0, ctx->stream, n, inv_beta, act, coef, tab, w, stop, seq); });
   KHIP_CHECK_HIP(hipGetLastError());
   return KHIP_OK;
 }
 int launch_init(khip_ctx *ctx, int64_t n, int p, double *const *tab, bool tab_aligned, const double *src, bool copy_p) {
   if (n <= 0 || p <= 0) return KHIP_OK;
-  Launch L;
-  KHIP_TRY(plan(ctx, n, {copy_p ? src : nullptr}, tab_aligned, &L, false));
-  const dim3 grid((unsigned)L.g), blk(kBlock);
-  if (L.v2) {
-    if (L.nt) hipLaunchKernelGGL((lzshift_init_kernel<2, true>), grid, blk, 0, ctx->stream, n, p, tab, src, copy_p ? 1 : 0);
-    else hipLaunchKernelGGL((lzshift_init_kernel<2, false>), grid, blk, 0, ctx->stream, n, p, tab, src, copy_p ? 1 : 0);
-  } else {
-    hipLaunchKernelGGL((lzshift_init_kernel<1, false>), grid, blk, 0, ctx->stream, n, p, tab, src, copy_p ? 1 : 0);
-  }
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {copy_p ? src : nullptr}, &L, 0, tab_aligned));
+  vec_dispatch_vn<kScalarNT>(L, [&](auto V, auto N) {
+    hipLaunchKernelGGL((lzshift_init_kernel<V, N>), L.grid(), dim3(kBlock), 0, ctx->stream, n, p, tab, src, copy_p ? 1 : 0); });
   KHIP_CHECK_HIP(hipGetLastError());
   return KHIP_OK;
 }
@@ -320,13 +276,6 @@ LzShiftArrays host_arrays(khip_cg_lanczos_shift_workspace *ws, const double *shi
   return LzShiftArrays{shifts, ws->sigma.data(), ws->dhat.data(), ws->omega.data(), ws->gamma.data(), ws->rNorms.data(),
                        ws->coef.data(), ws->converged.data(), ws->not_cv.data(), ws->indefinite.data(), ws->act.data(),
                        ws->nhist.data()};
-}
-
-int upload_state(khip_cg_lanczos_shift_workspace *ws, const LanczosShiftDevState &s) {   // pinned[2]: the host-driven loop's staging copy
-  ws->loop.pinned[2] = s;
-  KHIP_CHECK_HIP(hipMemcpyAsync(ws->loop.dev, &ws->loop.pinned[2], sizeof(LanczosShiftDevState), hipMemcpyHostToDevice,
-                                ws->ctx->stream));
-  return KHIP_OK;
 }
 
 // act / coef of the host-driven loop's iteration (from pageable host memory: waited for)
@@ -661,7 +610,7 @@ int khip_cg_lanczos_shift_solve(khip_cg_lanczos_shift_workspace *ws, const khip_
         K(launch_dot(ctx, n, vin, nxt, slot));
       }
       K(fetch_results(ctx, slot, 1, &s.delta));
-      K(upload_state(ws, s));
+      K(ws->loop.upload(ctx, s));
       slot = take_slots(ctx, 1);
       K(launch_p1(ctx, n, ws->loop.dev, prev, cur, nxt, k >= 2, MisI, slot));           // w ; w.w
       double b2;
@@ -673,13 +622,13 @@ int khip_cg_lanczos_shift_solve(khip_cg_lanczos_shift_workspace *ws, const khip_
       }
       lzshift_beta(s, b2);
       if (!MisI) {
-        K(upload_state(ws, s));
+        K(ws->loop.upload(ctx, s));
         slot = take_slots(ctx, 1);
         K(launch_scale(ctx, n, ws->loop.dev, v, nxt, slot));                             // v, Mv /= β ; ρ = v.v
         K(fetch_results(ctx, slot, 1, &s.rho));
       }
       solved = lzshift_step(s, ha, k, row.data());
-      K(upload_state(ws, s));
+      K(ws->loop.upload(ctx, s));
       K(upload_coefs(ws));
       K(launch_p2(ctx, n, &ws->loop.dev->inv_beta, ws->act_dev, ws->coef_dev, ws->tab, tab_aligned, MisI ? nxt : v, MisI));
       double *old_prev = prev;                                                            // Mv_prev <- Mv ; Mv <- Mv_next

@@ -18,16 +18,10 @@
 #include <chrono>
 #include <utility>
 
-#include "device_reduce.hpp"
 #include "solver_host.hpp"
+#include "vec_launch.hpp"
 
 using namespace khip;
-
-namespace {
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-}  // namespace
 
 namespace khip {   // (named, not anonymous: stable kernel names in traces)
 
@@ -44,7 +38,7 @@ __global__ __launch_bounds__(kBlock) void minres_p1_kernel(int64_t n, const Minr
   const bool use_lam = lam != 0.0;
   dd acc[1] = {dd{0.0, 0.0}};
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   auto one = [&](double ye, double ve, double re) {
     double t = ye;
     if (use_lam) t = fma(lam, ve, t);
@@ -63,7 +57,7 @@ __global__ __launch_bounds__(kBlock) void minres_p1_kernel(int64_t n, const Minr
     for (int e = 0; e < VEC; ++e) vset(yo, e, one(vget(yv, e), vget(vv, e), vget(rv, e)));
     stg<false>(yo, reinterpret_cast<T *>(y) + i);                      // y is read again by P2
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     y[t] = one(y[t], v[t], sub_r1 ? r1[t] : 0.0);
   }
@@ -82,7 +76,7 @@ __global__ __launch_bounds__(kBlock) void minres_p2_kernel(int64_t n, const Minr
   const bool same = (r2 == v);
   dd acc[1] = {dd{0.0, 0.0}};
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   auto one = [&](double ye, double re, double ve, double w1e, double w2e, double &wo) {
     const double yn = fma(c2, re, ye);
     if (first) {
@@ -115,7 +109,7 @@ __global__ __launch_bounds__(kBlock) void minres_p2_kernel(int64_t n, const Minr
     stg<NT>(yo, reinterpret_cast<T *>(y) + i);
     stg<false>(wo, reinterpret_cast<T *>(first ? w2 : w1) + i);       // w is read again by P3
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     double we;
     y[t] = one(y[t], r2[t], v[t], first ? 0.0 : w1[t], first ? 0.0 : w2[t], we);
@@ -132,7 +126,7 @@ __global__ __launch_bounds__(kBlock) void minres_p3_kernel(int64_t n, const Minr
   const double ig = st->inv_gamma, phi = st->phi;
   dd acc[1] = {dd{0.0, 0.0}};
   const int64_t nvec = n / VEC;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane_index();
   if (i < nvec) {
     const T wv = ldg<false>(reinterpret_cast<const T *>(w) + i);
     const T xv = ldg<NT>(reinterpret_cast<const T *>(x) + i);
@@ -148,7 +142,7 @@ __global__ __launch_bounds__(kBlock) void minres_p3_kernel(int64_t n, const Minr
     stg<NT>(wo, reinterpret_cast<T *>(w) + i);
     stg<NT>(xo, reinterpret_cast<T *>(x) + i);
   }
-  if (VEC == 2 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (VEC == 2 && owns_tail(n)) {
     const int64_t t = n - 1;
     const double wn = ig * w[t];
     const double xn = fma(phi, wn, x[t]);
@@ -163,63 +157,39 @@ __global__ __launch_bounds__(kBlock) void minres_p3_kernel(int64_t n, const Minr
 
 namespace {
 
-struct Launch {
-  int64_t g;
-  bool v2, nt, comp;
-};
-int plan(khip_ctx *ctx, int64_t n, std::initializer_list<const void *> ptrs, Launch *L) {
-  bool al = n >= 2;
-  for (const void *p : ptrs) if (p && !aligned16(p)) al = false;
-  L->v2 = al;
-  L->nt = n >= (int64_t)ctx->tune.nt_min_elems;
-  L->comp = ctx->tune.compensated != 0;
-  const int64_t nvec = al ? n / 2 : n;
-  int64_t t = (nvec + kBlock - 1) / kBlock;
-  L->g = t < 1 ? 1 : t;
-  if (L->g > 0x7fffffffLL) { set_error("vector too long for one launch"); return KHIP_ERR_INVALID; }
-  return ensure_reduction_scratch(ctx, L->g * kWavesPerBlock, 1);
-}
-
-#define KHIP_MR_LAUNCH(KERNEL, ...)                                                                                         \
-  do {                                                                                                                      \
-    const dim3 grid((unsigned)L.g), blk(kBlock);                                                                            \
-    if (L.v2) {                                                                                                             \
-      if (L.nt) { if (L.comp) hipLaunchKernelGGL((KERNEL<2, true, true>), grid, blk, 0, ctx->stream, __VA_ARGS__);          \
-                  else hipLaunchKernelGGL((KERNEL<2, true, false>), grid, blk, 0, ctx->stream, __VA_ARGS__); }              \
-      else      { if (L.comp) hipLaunchKernelGGL((KERNEL<2, false, true>), grid, blk, 0, ctx->stream, __VA_ARGS__);         \
-                  else hipLaunchKernelGGL((KERNEL<2, false, false>), grid, blk, 0, ctx->stream, __VA_ARGS__); }             \
-    } else {                                                                                                                \
-      if (L.comp) hipLaunchKernelGGL((KERNEL<1, false, true>), grid, blk, 0, ctx->stream, __VA_ARGS__);                     \
-      else hipLaunchKernelGGL((KERNEL<1, false, false>), grid, blk, 0, ctx->stream, __VA_ARGS__);                           \
-    }                                                                                                                       \
-    KHIP_CHECK_HIP(hipGetLastError());                                                                                      \
-  } while (0)
+constexpr ScalarPathNT kScalarNT = ScalarPathNT::never;
 
 int launch_p1(khip_ctx *ctx, int64_t n, const MinresDevState *st, const double *v, const double *r1, double *y, bool sub_r1,
               int slot) {
-  Launch L;
-  KHIP_TRY(plan(ctx, n, {v, sub_r1 ? r1 : nullptr, y}, &L));
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {v, sub_r1 ? r1 : nullptr, y}, &L, 1));
   RedArgs ra = make_red_args(ctx, slot);
-  KHIP_MR_LAUNCH(minres_p1_kernel, n, st, v, r1, y, sub_r1 ? 1 : 0, ra);
-  return launch_finish(ctx, L.g * kWavesPerBlock, 1, slot);
+  vec_dispatch<kScalarNT>(L, [&](auto V, auto N, auto C) {
+    hipLaunchKernelGGL((minres_p1_kernel<V, N, C>), L.grid(), dim3(kBlock), 0, ctx->stream, n, st, v, r1, y, sub_r1 ? 1 : 0, ra); });
+  KHIP_CHECK_HIP(hipGetLastError());
+  return launch_finish(ctx, L.waves(), 1, slot);
 }
 int launch_p2(khip_ctx *ctx, int64_t n, const MinresDevState *st, const double *r2, const double *v, double *y, double *w1,
               double *w2, int k, bool dot, int slot) {
-  Launch L;
-  KHIP_TRY(plan(ctx, n, {r2, v, y, w1, w2}, &L));
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {r2, v, y, w1, w2}, &L, 1));
   RedArgs ra = make_red_args(ctx, slot);
-  KHIP_MR_LAUNCH(minres_p2_kernel, n, st, r2, v, y, w1, w2, k == 1 ? 1 : 0, k >= 3 ? 1 : 0, dot ? 1 : 0, ra);
+  vec_dispatch<kScalarNT>(L, [&](auto V, auto N, auto C) {
+    hipLaunchKernelGGL((minres_p2_kernel<V, N, C>), L.grid(), dim3(kBlock), 0, ctx->stream, n, st, r2, v, y, w1, w2, k == 1 ? 1 : 0,
+                       k >= 3 ? 1 : 0, dot ? 1 : 0, ra); });
+  KHIP_CHECK_HIP(hipGetLastError());
   if (!dot) return KHIP_OK;        // the partials are not folded: nothing reads them
-  return launch_finish(ctx, L.g * kWavesPerBlock, 1, slot);
+  return launch_finish(ctx, L.waves(), 1, slot);
 }
 int launch_p3(khip_ctx *ctx, int64_t n, const MinresDevState *st, double *w, double *x, int slot) {
-  Launch L;
-  KHIP_TRY(plan(ctx, n, {w, x}, &L));
+  VecPlan L;
+  KHIP_TRY(vec_plan(ctx, n, {w, x}, &L, 1));
   RedArgs ra = make_red_args(ctx, slot);
-  KHIP_MR_LAUNCH(minres_p3_kernel, n, st, w, x, ra);
-  return launch_finish(ctx, L.g * kWavesPerBlock, 1, slot);
+  vec_dispatch<kScalarNT>(L, [&](auto V, auto N, auto C) {
+    hipLaunchKernelGGL((minres_p3_kernel<V, N, C>), L.grid(), dim3(kBlock), 0, ctx->stream, n, st, w, x, ra); });
+  KHIP_CHECK_HIP(hipGetLastError());
+  return launch_finish(ctx, L.waves(), 1, slot);
 }
-#undef KHIP_MR_LAUNCH
 
 // y = A v followed by P1, reduction v.y into results[slot].  fuse (SpmvPlan::carries_lanczos): ONE launch -- the sliced SpMV applies the
 // Lanczos epilogue to each row's product and forms v.y in its fused dot; otherwise the plain product, then P1.  Same elementwise
@@ -232,12 +202,7 @@ int lanczos_product(khip_ctx *ctx, const khip_operator *A, bool fuse, int64_t n,
     ctx->lz = LanczosEpi{};
     return rc;
   }
-  const SeqCtl keep = ctx->ctl;
-  ctx->ctl.epi = EPI_NONE;
-  ctx->ctl.epi_state = nullptr;
-  const int rc = apply_op(ctx, A, v, y);
-  ctx->ctl = keep;
-  if (rc != KHIP_OK) return rc;
+  KHIP_TRY(apply_op_no_epilogue(ctx, A, v, y));
   return launch_p1(ctx, n, st, v, r1, y, sub_r1, slot);
 }
 
@@ -263,12 +228,6 @@ namespace {
 struct Bufs {
   double *x, *r1, *r2, *y, *v, *w1, *w2;   // v == r2 when M = I
 };
-
-int upload(khip_minres_workspace *ws, const MinresDevState &s) {   // pinned[2] is the staging copy of the host-driven loop
-  ws->loop.pinned[2] = s;
-  KHIP_CHECK_HIP(hipMemcpyAsync(ws->loop.dev, &ws->loop.pinned[2], sizeof(MinresDevState), hipMemcpyHostToDevice, ws->ctx->stream));
-  return KHIP_OK;
-}
 
 void verbose_row(const khip_options &o, long long iter, const MinresDevState &s, double t0, bool first_row) {
   if (first_row)
@@ -530,13 +489,13 @@ int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const k
     s.hist_r = s.hist_ar = s.hist_acond = nullptr;
     while (!stop) {
       const int64_t k = ++iter;
-      K(upload(ws, s));
+      K(ws->loop.upload(ctx, s));
       int slot = take_slots(ctx, 1);
       K(lanczos_product(ctx, A, fuse, n, ws->loop.dev, B.v, B.r1, B.y, k >= 2, slot));
       double vy;
       K(fetch_results(ctx, slot, 1, &vy));
       minres_step_a(s, vy);
-      K(upload(ws, s));
+      K(ws->loop.upload(ctx, s));
       slot = take_slots(ctx, 1);
       K(launch_p2(ctx, n, ws->loop.dev, B.r2, B.v, B.y, B.w1, B.w2, (int)std::min<int64_t>(k, 3), MisI, slot));
       double *w = k == 1 ? B.w2 : B.w1;
@@ -552,7 +511,7 @@ int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const k
       }
       if (!minres_step_b(s, b2, k)) return ws->box.fail(KHIP_ERR_NUMERIC, "Preconditioner is not positive definite");
       if (history) ws->aresiduals.push_back(s.ArNorm);
-      K(upload(ws, s));
+      K(ws->loop.upload(ctx, s));
       slot = take_slots(ctx, 1);
       K(launch_p3(ctx, n, ws->loop.dev, w, B.x, slot));
       double xx;

@@ -136,6 +136,17 @@ int adopt_named(khip_ctx *ctx, Borrowed &b, std::initializer_list<NamedSlot> tab
   return KHIP_ERR_INVALID;
 }
 
+// y = op x inside a sequence whose reductions carry epilogues: the product keeps the sequence number (it is skipped once the
+// loop has stopped) and runs no epilogue of its own
+int apply_op_no_epilogue(khip_ctx *ctx, const khip_operator *op, const double *x, double *y) {
+  const SeqCtl keep = ctx->ctl;
+  ctx->ctl.epi = EPI_NONE;
+  ctx->ctl.epi_state = nullptr;
+  const int rc = apply_op(ctx, op, x, y);
+  ctx->ctl = keep;
+  return rc;
+}
+
 // ---- the device-resident loops ---------------------------------------------------------------------------------------------
 constexpr int kDevChunk = 4;             // iterations enqueued between two snapshots of the device state
 
@@ -184,6 +195,14 @@ struct DeviceLoop {
     if (!dev) KHIP_CHECK_HIP(hipMalloc(&dev, sizeof(S)));
     if (!pinned) KHIP_CHECK_HIP(hipHostMalloc(reinterpret_cast<void **>(&pinned), kPinned * sizeof(S), hipHostMallocDefault));
     for (auto &e : snap_ev) if (!e) KHIP_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return KHIP_OK;
+  }
+
+  // the host-driven loop on the same kernels: its state of the moment, staged in pinned[2], becomes the device copy
+  int upload(khip_ctx *ctx, const S &s) {
+    static_assert(kPinned == 3, "DeviceLoop::upload stages in pinned[2]");
+    pinned[2] = s;
+    KHIP_CHECK_HIP(hipMemcpyAsync(dev, &pinned[2], sizeof(S), hipMemcpyHostToDevice, ctx->stream));
     return KHIP_OK;
   }
 
