@@ -131,6 +131,12 @@ int khip_csr_sell_info(const khip_csr *A, int *state, int *units_per_slice, int6
  * 32-bit word of eight codes per row (indexed by the row) and the slices hold values only -- 60 instead of 64 B per 7-point row
  * (ctx option "spmv_sell_narrow" = 1; default 0: it measured 8-10 % slower than the byte-coded words at 512^3, whose slices are 4 KB blocks). */
 int khip_csr_sell_narrow(const khip_csr *A, int *narrow);
+/* *pairs = size of the entry dictionary when the sliced copy is ENTRY-CODED, 0 when it is not: a handle with 8-bit diagonal codes,
+ * rows of at most 64 entries and at most 255 distinct entries -- pairs (column - row, bit pattern of the value) -- keeps one byte
+ * per entry (the rank of its pair, ascending (offset, value bits as unsigned); 0xFF = no entry) and no values in its slices:
+ * 8 B per row of at most 8 entries, ceil(L / 8) words padded to an even count beyond.  khip_csr_sell_info reports this copy.
+ * ctx option "spmv_sell_entries": 1 (default) = handles of at least 2^22 entries, 2 = whenever the handle qualifies, 0 = never. */
+int khip_csr_sell_entries(const khip_csr *A, int *pairs);
 /* The same for the int32 column stream -- operators that are not coded (more than 2048 diagonals, fewer than 4 M entries under
  * "spmv_codes" = 1, or "spmv_codes" = 0) with short rows (the staged kernel's operators: at most 12 entries per row on average):
  * per slice, per lane, ceil(L / 2) words of two int32 columns (-1 = no entry) then L values; same padding rule, same size rule as

@@ -107,6 +107,7 @@ SIGNATURES = {
     "khip_csr_sell_info": (_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64)]),
     "khip_csr_sell32_info": (_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64)]),
     "khip_csr_sell_narrow": (_int, [_vp, C.POINTER(C.c_int)]),
+    "khip_csr_sell_entries": (_int, [_vp, C.POINTER(C.c_int)]),
     "khip_spmv_kernel_info": (_int, [_vp, _vp, C.POINTER(C.c_int)]),
     "khip_csr_delta_info": (_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64)]),
     "khip_csr_tile_info": (_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64),
@@ -791,6 +792,14 @@ class CsrMatrix:
         v = C.c_int()
         _ck(lib().khip_csr_sell_narrow(self._h, C.byref(v)))
         return bool(v.value)
+
+    @property
+    def sell_entries(self) -> int:
+        """Pairs (column - row, value bits) in the dictionary of an entry-coded sliced copy (khip_csr_sell_entries); 0 when the
+        copy is not entry-coded."""
+        v = C.c_int()
+        _ck(lib().khip_csr_sell_entries(self._h, C.byref(v)))
+        return v.value
 
     @property
     def sell32_info(self):

@@ -14,6 +14,7 @@
 // open-addressing table (read first, atomicCAS only on an empty slot -> after the first few workgroups the pass is a
 // read-only stream of col), the host sorts the <= 2048 keys (deterministic), a second pass writes rank(d) per entry.
 #include <algorithm>
+#include <cstring>
 
 #include "spmv_common.hpp"
 
@@ -150,10 +151,137 @@ __global__ __launch_bounds__(kBlock) void sell_fill_kernel(const int32_t *rowptr
   for (int k = 0; k < L; ++k) slot(W + k) = k < len ? (unsigned long long)__double_as_longlong(val[q0 + k]) : 0ull;
 }
 
+// ---------------------------------------------------------------- entry-coded sliced form (spmv_sell_kernel, ENT) ----
+// A stencil operator repeats not only its diagonals but its ENTRIES: the pair (column - row, value) takes 7 distinct values on the
+// 7-point operator with constant coefficients, 27 on the 27-point one.  A handle with 8-bit diagonal codes, rows of at most 64
+// entries and at most 255 distinct pairs -- values compared as 64-bit patterns: +0.0 and -0.0 are two, NaNs with different payloads
+// are two -- keeps in its sliced fields code words ONLY: one byte per entry = the rank of its pair in the handle's entry dictionary
+// (ascending by offset, then by the value's bits taken as unsigned; 0xFF = no entry), the SAME 64-row slices and the same per-lane
+// word order as the code words above, without the values.  A slice whose longest row has L entries holds, per lane, one word
+// (L <= 8: 512 B per slice, 8 B per row) or ceil(L / 8) words padded to an even count and stored in 16-byte pairs as in mode 5.  The
+// kernel rebuilds col = row + off[code] and val[code] from a 256-slot table in LDS: stored order, the same bits, the same y.
+// Construction on the device, verified entry by entry: a CAS set of the value patterns, a presence map over (diagonal code, value id),
+// the host sorts / compacts the at most 255 pairs, the fill pass checks every entry it codes against the table and refuses the
+// form on any mismatch.
+constexpr int kEntMax = 255;               // pairs at most (0xFF = no entry)
+constexpr int kEntHash = 1024;             // slots of the value set (power of two)
+constexpr unsigned long long kEntEmpty = ~0ull;   // empty slot; a value with this very pattern (a NaN) is flagged apart
+
+__device__ __forceinline__ unsigned ent_hash(unsigned long long b) { return (unsigned)((b * 0x9E3779B97F4A7C15ull) >> 54); }   // 10 bits
+
+// flags: [0] distinct values so far, [1] failure, [2] the all-ones pattern occurs
+__global__ __launch_bounds__(kBlock) void ent_values_kernel(const int32_t *rowptr, const double *val, int64_t m, unsigned long long *keys, int *flags) {
+  const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (row >= m) return;
+  if (__atomic_load_n(&flags[1], __ATOMIC_RELAXED)) return;
+  unsigned long long last = 0;
+  bool have = false;
+  for (int32_t q = rowptr[row]; q < rowptr[row + 1]; ++q) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(val[q]);
+    if (have && b == last) continue;
+    last = b; have = true;
+    if (b == kEntEmpty) { if (!__atomic_load_n(&flags[2], __ATOMIC_RELAXED)) atomicOr(&flags[2], 1); continue; }
+    unsigned slot = ent_hash(b) & (kEntHash - 1);
+    bool done = false;
+    for (int probe = 0; probe < kEntHash && !done; ++probe) {
+      unsigned long long cur = __atomic_load_n(&keys[slot], __ATOMIC_RELAXED);
+      if (cur == kEntEmpty) {
+        cur = atomicCAS(&keys[slot], kEntEmpty, b);
+        if (cur == kEntEmpty) {
+          if (atomicAdd(&flags[0], 1) >= kEntMax) atomicMax(&flags[1], 1);
+          cur = b;
+        }
+      }
+      if (cur == b) done = true;
+      else slot = (slot + 1) & (kEntHash - 1);
+    }
+    if (!done) { atomicMax(&flags[1], 1); return; }
+  }
+}
+
+// rank of the pattern b in the ascending table vals[0, V), or -1
+__device__ __forceinline__ int ent_value_id(const unsigned long long *vals, int V, unsigned long long b) {
+  int lo = 0, hi = V - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (vals[mid] < b) lo = mid + 1; else hi = mid;
+  }
+  return (V > 0 && vals[lo] == b) ? lo : -1;
+}
+
+// presence map over (diagonal code, value id): bit (code * 256 + id) of 65,536
+__global__ __launch_bounds__(kBlock) void ent_presence_kernel(const int32_t *rowptr, const double *val, const uint8_t *code, int64_t m,
+                                                              const unsigned long long *vals, int V, unsigned *present, int *flags) {
+  __shared__ unsigned long long s_vals[256];
+  for (int i = threadIdx.x; i < 256; i += kBlock) s_vals[i] = i < V ? vals[i] : kEntEmpty;
+  __syncthreads();
+  const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (row >= m) return;
+  for (int32_t q = rowptr[row]; q < rowptr[row + 1]; ++q) {
+    const int id = ent_value_id(s_vals, V, (unsigned long long)__double_as_longlong(val[q]));
+    if (id < 0) { atomicMax(&flags[1], 1); return; }
+    const unsigned bit = (unsigned)code[q] * 256u + (unsigned)id;
+    if (!((__atomic_load_n(&present[bit >> 5], __ATOMIC_RELAXED) >> (bit & 31)) & 1u)) atomicOr(&present[bit >> 5], 1u << (bit & 31));
+  }
+}
+
+// units of a slice: one word of eight entry codes up to 8 entries per row, else ceil(L / 8) words padded to an even count (16-byte pairs)
+__host__ __device__ __forceinline__ int ent_units(int L) { return L <= 0 ? 0 : (L <= 8 ? 1 : ((L + 7) / 8) + (((L + 7) / 8) & 1)); }
+
+__global__ __launch_bounds__(kBlock) void ent_units_kernel(const int32_t *rowptr, int64_t m, int64_t slices, int32_t *units) {
+  const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (s >= slices) return;
+  int L = 0;
+  const int64_t r0 = s * 64, r1 = (r0 + 64 < m) ? r0 + 64 : m;
+  int32_t prev = rowptr[r0];
+  for (int64_t r = r0; r < r1; ++r) {
+    const int32_t nxt = rowptr[r + 1];
+    L = (nxt - prev > L) ? nxt - prev : L;
+    prev = nxt;
+  }
+  units[s] = ent_units(L);
+}
+
+// pairmap[code * 256 + id] = rank of the pair (0xFF: absent); tab_off / tab_val = the dictionary (256 slots each).  Every entry is
+// checked against the table it is coded with: offset and value bits, exactly.
+__global__ __launch_bounds__(kBlock) void ent_fill_kernel(const int32_t *rowptr, const int32_t *col, const double *val, const uint8_t *code, int64_t m,
+                                                          int64_t slices, const uint32_t *off, int uniform_units, const unsigned long long *vals, int V,
+                                                          const uint8_t *pairmap, const int32_t *tab_off, const double *tab_val,
+                                                          unsigned long long *sell, int *flags) {
+  __shared__ unsigned long long s_vals[256];
+  for (int i = threadIdx.x; i < 256; i += kBlock) s_vals[i] = i < V ? vals[i] : kEntEmpty;
+  __syncthreads();
+  const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;      // rows of the last slice beyond m are written too (no entry)
+  if (row >= slices * 64) return;
+  const int64_t s = row >> 6;
+  const int lane = (int)(row & 63);
+  const int64_t o0 = uniform_units ? s * uniform_units : (int64_t)off[s];
+  const int T = uniform_units ? uniform_units : (int)(off[s + 1] - off[s]);
+  const int32_t q0 = row < m ? rowptr[row] : 0;
+  const int len = row < m ? rowptr[row + 1] - q0 : 0;
+  if (len > 8 * T) { atomicMax(&flags[1], 1); return; }
+  for (int w = 0; w < T; ++w) {
+    unsigned long long word = 0;
+    for (int u = 0; u < 8; ++u) {
+      const int k = 8 * w + u;
+      unsigned long long e = 0xFFull;
+      if (k < len) {
+        const unsigned long long b = (unsigned long long)__double_as_longlong(val[q0 + k]);
+        const int id = ent_value_id(s_vals, V, b);
+        e = id >= 0 ? (unsigned long long)pairmap[(size_t)code[q0 + k] * 256 + (size_t)id] : 0xFFull;
+        if (e == 0xFFull || tab_off[e] != col[q0 + k] - (int32_t)row || (unsigned long long)__double_as_longlong(tab_val[e]) != b) { atomicMax(&flags[1], 1); return; }
+      }
+      word |= e << (8 * u);
+    }
+    // word w of this lane: one word per lane (T == 1), else pairs ((w / 2) * 64 + lane) * 2 + (w & 1)
+    sell[(size_t)o0 * 64 + (T == 1 ? (size_t)lane : ((size_t)(w >> 1) * 64 + lane) * 2 + (w & 1))] = word;
+  }
+}
+
 void csr_free_sell(khip_csr *A) {
-  (void)hipFree(A->sell); (void)hipFree(A->sell_off); (void)hipFree(A->sell_c4);
-  A->sell = nullptr; A->sell_off = nullptr; A->sell_c4 = nullptr; A->sell_pair = 0;
-  A->sell_units = 0; A->sell_total_units = 0; A->sell_state = 0;
+  (void)hipFree(A->sell); (void)hipFree(A->sell_off); (void)hipFree(A->sell_c4); (void)hipFree(A->sell_ent_tab);
+  A->sell = nullptr; A->sell_off = nullptr; A->sell_c4 = nullptr; A->sell_pair = 0; A->sell_ent_tab = nullptr;
+  A->sell_units = 0; A->sell_total_units = 0; A->sell_state = 0; A->sell_entries = 0; A->sell_ent_state = 0;
 }
 
 void csr_free_sell32(khip_csr *A) {
@@ -164,7 +292,9 @@ void csr_free_sell32(khip_csr *A) {
 
 // cols32 = false: code words (needs the 8-bit codes); true: int32 column words
 static int build_sell_form(khip_ctx *ctx, khip_csr *A, bool cols32) {
+  const bool ent_refused = !cols32 && A->sell_ent_state == -1;       // the entry-coded build was tried on this handle: stays tried
   if (cols32) csr_free_sell32(A); else csr_free_sell(A);
+  if (ent_refused) A->sell_ent_state = -1;
   int &state = cols32 ? A->sell32_state : A->sell_state;
   unsigned long long *&words = cols32 ? A->sell32 : A->sell;
   uint32_t *&offs = cols32 ? A->sell32_off : A->sell_off;
@@ -218,6 +348,116 @@ static int build_sell_form(khip_ctx *ctx, khip_csr *A, bool cols32) {
   (cols32 ? A->sell32_total_units : A->sell_total_units) = total;
   if (cols32) A->sell32_pair = mode == 4 ? 2 : 0; else A->sell_pair = mode == 3 ? 1 : (mode == 5 ? 2 : 0);
   state = 1;
+  return KHIP_OK;
+}
+
+// The entry-coded copy in the handle's sliced fields.  Success: sell_state = sell_ent_state = 1.  Refusal (more than 255 pairs, a row
+// of more than 64 entries, too much padding, a mismatch found by the fill pass): sell_ent_state = -1 and sell_state stays 0 -- the
+// caller builds the copy with values.
+int csr_build_sell_entries(khip_ctx *ctx, khip_csr *A) {
+  csr_free_sell(A);
+  A->sell_ent_state = -1;
+  const int64_t m = A->m;
+  if (m == 0 || A->nnz == 0 || A->max_row_nnz > 64) return KHIP_OK;
+  if (A->code_state != 1 || A->code_bits != 8 || A->code_T > 255) return KHIP_OK;
+  const int64_t slices = (m + 63) / 64;
+  struct Dev { void *p = nullptr; ~Dev() { (void)hipFree(p); } };
+  Dev keys_d, flags_d, vals_d, present_d, map_d, units_d;
+  KHIP_CHECK_HIP(hipMalloc(&keys_d.p, sizeof(unsigned long long) * kEntHash));
+  KHIP_CHECK_HIP(hipMalloc(&flags_d.p, sizeof(int) * 4));
+  KHIP_CHECK_HIP(hipMemsetAsync(keys_d.p, 0xFF, sizeof(unsigned long long) * kEntHash, ctx->stream));
+  KHIP_CHECK_HIP(hipMemsetAsync(flags_d.p, 0, sizeof(int) * 4, ctx->stream));
+  int *flags = (int *)flags_d.p;
+  const unsigned grid = (unsigned)((m + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(ent_values_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, A->rowptr, A->val, m, (unsigned long long *)keys_d.p, flags);
+  KHIP_CHECK_HIP(hipGetLastError());
+  int h[4] = {0, 0, 0, 0};
+  std::vector<unsigned long long> hk(kEntHash);
+  KHIP_CHECK_HIP(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+  KHIP_CHECK_HIP(hipMemcpyAsync(hk.data(), keys_d.p, sizeof(unsigned long long) * kEntHash, hipMemcpyDeviceToHost, ctx->stream));
+  KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  if (h[1]) return KHIP_OK;                                           // more than 255 values: more than 255 pairs
+  std::vector<unsigned long long> vals;
+  for (unsigned long long k : hk) if (k != kEntEmpty) vals.push_back(k);
+  if (h[2]) vals.push_back(kEntEmpty);
+  std::sort(vals.begin(), vals.end());
+  const int V = (int)vals.size();
+  if (V == 0 || V > kEntMax) return KHIP_OK;
+  KHIP_CHECK_HIP(hipMalloc(&vals_d.p, sizeof(unsigned long long) * 256));
+  KHIP_CHECK_HIP(hipMalloc(&present_d.p, 65536 / 8));
+  KHIP_CHECK_HIP(hipMemcpyAsync(vals_d.p, vals.data(), sizeof(unsigned long long) * (size_t)V, hipMemcpyHostToDevice, ctx->stream));
+  KHIP_CHECK_HIP(hipMemsetAsync(present_d.p, 0, 65536 / 8, ctx->stream));
+  hipLaunchKernelGGL(ent_presence_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, A->rowptr, A->val, (const uint8_t *)A->code, m,
+                     (const unsigned long long *)vals_d.p, V, (unsigned *)present_d.p, flags);
+  KHIP_CHECK_HIP(hipGetLastError());
+  std::vector<unsigned> present(65536 / 32);
+  std::vector<int32_t> diag((size_t)A->code_T);
+  KHIP_CHECK_HIP(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+  KHIP_CHECK_HIP(hipMemcpyAsync(present.data(), present_d.p, 65536 / 8, hipMemcpyDeviceToHost, ctx->stream));
+  KHIP_CHECK_HIP(hipMemcpyAsync(diag.data(), A->code_tab, sizeof(int32_t) * (size_t)A->code_T, hipMemcpyDeviceToHost, ctx->stream));
+  KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  if (h[1]) return KHIP_OK;
+  // the dictionary: diagonal codes ascend with the offset, value ids with the bits, so walking the map in order IS the sorted order
+  struct Table { int32_t off[256]; double val[256]; } tab;
+  memset(&tab, 0, sizeof(tab));
+  std::vector<uint8_t> pairmap(65536, 0xFF);
+  int P = 0;
+  for (int c = 0; c < A->code_T; ++c)
+    for (int id = 0; id < V; ++id) {
+      const unsigned bit = (unsigned)c * 256u + (unsigned)id;
+      if (!((present[bit >> 5] >> (bit & 31)) & 1u)) continue;
+      if (P >= kEntMax) return KHIP_OK;                               // 256 pairs or more: refused
+      tab.off[P] = diag[(size_t)c];
+      memcpy(&tab.val[P], &vals[(size_t)id], sizeof(double));
+      pairmap[bit] = (uint8_t)P++;
+    }
+  if (P == 0) return KHIP_OK;
+  // slices: the rules of build_sell_form with this form's units
+  KHIP_CHECK_HIP(hipMalloc(&units_d.p, sizeof(int32_t) * (size_t)slices));
+  hipLaunchKernelGGL(ent_units_kernel, dim3((unsigned)((slices + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, A->rowptr, m, slices, (int32_t *)units_d.p);
+  KHIP_CHECK_HIP(hipGetLastError());
+  std::vector<int32_t> units((size_t)slices);
+  KHIP_CHECK_HIP(hipMemcpyAsync(units.data(), units_d.p, sizeof(int32_t) * (size_t)slices, hipMemcpyDeviceToHost, ctx->stream));
+  KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  int64_t total = 0;
+  int umax = 0;
+  for (int32_t u : units) { total += u; umax = u > umax ? u : umax; }
+  const double ref_bytes = 9.0 * (double)A->nnz + 4.0 * (double)m;    // the CSR stream this copy replaces (the one build_sell_form compares with)
+  if (512.0 * (double)total > kSellMaxPad * ref_bytes + 65536.0) return KHIP_OK;
+  const bool uniform = (double)umax * (double)slices <= kSellUniformPad * (double)total + 8.0;
+  if (uniform) total = (int64_t)umax * slices;
+  if (total >= ((int64_t)1 << 32)) return KHIP_OK;
+  bool keep = false;
+  struct Guard { khip_csr *A; bool &keep; ~Guard() { if (!keep) { csr_free_sell(A); A->sell_ent_state = -1; } } } guard{A, keep};
+  if (!uniform) {
+    std::vector<uint32_t> off((size_t)slices + 1);
+    uint32_t run = 0;
+    for (int64_t s = 0; s < slices; ++s) { off[(size_t)s] = run; run += (uint32_t)units[(size_t)s]; }
+    off[(size_t)slices] = run;
+    KHIP_CHECK_HIP(hipMalloc(&A->sell_off, sizeof(uint32_t) * ((size_t)slices + 1)));
+    KHIP_CHECK_HIP(hipMemcpyAsync(A->sell_off, off.data(), sizeof(uint32_t) * ((size_t)slices + 1), hipMemcpyHostToDevice, ctx->stream));
+    KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));                                  // `off` dies with this scope
+  }
+  KHIP_CHECK_HIP(hipMalloc(&A->sell, sizeof(unsigned long long) * 64 * (size_t)(total + 1)));
+  KHIP_CHECK_HIP(hipMalloc(&A->sell_ent_tab, sizeof(tab)));
+  KHIP_CHECK_HIP(hipMalloc(&map_d.p, 65536));
+  KHIP_CHECK_HIP(hipMemcpyAsync(A->sell_ent_tab, &tab, sizeof(tab), hipMemcpyHostToDevice, ctx->stream));
+  KHIP_CHECK_HIP(hipMemcpyAsync(map_d.p, pairmap.data(), 65536, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(ent_fill_kernel, dim3((unsigned)((slices * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, A->rowptr, A->col, A->val,
+                     (const uint8_t *)A->code, m, slices, A->sell_off, uniform ? umax : 0, (const unsigned long long *)vals_d.p, V,
+                     (const uint8_t *)map_d.p, (const int32_t *)A->sell_ent_tab, (const double *)((const int32_t *)A->sell_ent_tab + 256),
+                     A->sell, flags);
+  KHIP_CHECK_HIP(hipGetLastError());
+  KHIP_CHECK_HIP(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+  KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));                  // also keeps `tab` / `pairmap` alive until the uploads are done
+  if (h[1]) return KHIP_OK;                                           // an entry did not match the table it was coded with
+  keep = true;
+  A->sell_units = uniform ? umax : 0;
+  A->sell_total_units = total;
+  A->sell_pair = 0;
+  A->sell_entries = P;
+  A->sell_ent_state = 1;
+  A->sell_state = 1;
   return KHIP_OK;
 }
 

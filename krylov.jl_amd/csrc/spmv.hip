@@ -443,15 +443,52 @@ __global__ __launch_bounds__(kBlock) void spmv_code_kernel(SpmvArgs a, RedArgs r
 // C4: narrow codes -- eight 4-bit codes per row in one 32-bit word indexed by the row, the slices hold values only
 // PAIR: rows of at most 8 entries, the code word and the values of a row in 16-byte pairs (element e of lane l = words 2e, 2e + 1)
 // PAIRG: the general pair layout -- an even number of head words (codes or columns), then an even number of value words; any row length
-template <bool DOT, bool COMP, bool DIST, bool NTM, bool COLS32, bool C4, bool PAIR, bool PAIRG>
+// ENT: entry-coded slices (colcode.hip csr_build_sell_entries) -- code words only, a byte is the rank of the pair (column - row, value)
+//      in the handle's dictionary; offset and value come out of LDS.  One word per lane (rows of at most 8 entries), else 16-byte pairs
+
+// eight entries of an entry-coded row: eight lookups, the eight gathers issued together, then the products in stored order
+template <bool DIST>
+__device__ __forceinline__ double ent_step(const SpmvArgs &a, int32_t row, unsigned long long cw, const int32_t *s_off, const double *s_val, double acc) {
+  double vv[8], xx[8];
+  int32_t cc[8];
+  bool on[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) { const int c = (int)((cw >> (8 * u)) & 0xFFull); on[u] = c != 0xFF; cc[u] = row + s_off[c]; vv[u] = s_val[c]; }
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    xx[u] = 0.0;
+    if (on[u]) xx[u] = gather_x<DIST>(a, cc[u]);
+  }
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    if (on[u]) {
+      const double prod = vv[u] * xx[u];
+      acc = acc + prod;
+    }
+  }
+  return acc;
+}
+
+// the first code words of a row: the one word of a one-word slice (in .x), else the first 16-byte pair
+template <bool NTM>
+__device__ __forceinline__ dbl2 ent_first(const SpmvArgs &a, int64_t rowl, int64_t o0, int T) {
+  dbl2 ce = dbl2{0.0, 0.0};
+  if (T == 1) ce.x = __longlong_as_double((long long)ld<NTM>(a.sell + (size_t)o0 * 64 + (rowl & 63)));
+  else if (T > 1) ce = ld<NTM>(reinterpret_cast<const dbl2 *>(a.sell + (size_t)o0 * 64) + (rowl & 63));
+  return ce;
+}
+
+template <bool DOT, bool COMP, bool DIST, bool NTM, bool COLS32, bool C4, bool PAIR, bool PAIRG, bool ENT = false>
 __global__ __launch_bounds__(kBlock) void spmv_sell_kernel(SpmvArgs a, RedArgs ra) {
   if (seq_skip(a.stop_seq, a.seq)) return;
   const int ROWS = a.stage_rows;
   extern __shared__ __attribute__((aligned(16))) unsigned char s_stage[];
   // [block_publish scratch][diagonal table, 256 entries]: the scratch must not overlay the table, no barrier separates the row walks
-  // of different waves from the publish
+  // of different waves from the publish.  ENT: [scratch][offsets, 256 x int32][values, 256 x double] -- two arrays, a lookup is one
+  // 4-byte and one 8-byte LDS read
   const size_t pub = (DOT && a.blk_pub) ? sizeof(dd) * (size_t)kBlock * (a.dot_sq ? 2u : 1u) : 0u;
   int32_t *s_tab = reinterpret_cast<int32_t *>(s_stage + pub);
+  double *s_val = reinterpret_cast<double *>(s_stage + pub + 256 * sizeof(int32_t));
   const int tid = threadIdx.x;
   const int64_t nrows = a.row_hi - a.row_lo - a.hole_len;
   const int64_t nrb = (nrows + ROWS - 1) / ROWS;
@@ -462,7 +499,30 @@ __global__ __launch_bounds__(kBlock) void spmv_sell_kernel(SpmvArgs a, RedArgs r
   dd dacc[2];
   dacc[0] = dd{0.0, 0.0};
   dacc[1] = dd{0.0, 0.0};
-  if (!COLS32) {
+  // ENT: the row walk is one dependent chain, code words -> table (LDS) -> gathers, and a workgroup lives for a few such chains only.
+  // The first code words of this lane's row in row block rb are therefore loaded one block ahead: the first block's before the
+  // table is fetched (they do not depend on it), every later block's beside the gathers of the block before it.
+  dbl2 ent_next = dbl2{0.0, 0.0};
+  auto ent_prefetch = [&](int64_t rb) {
+    if (rb >= rb_end || tid >= ROWS) return;
+    int64_t rn = a.row_lo + rb * ROWS;
+    if (rn >= a.hole_lo) rn += a.hole_len;
+    rn += tid;
+    if (rn >= a.row_hi) return;
+    const int64_t sn = rn >> 6;
+    int64_t on;
+    int Tn;
+    if (a.sell_units) { on = sn * a.sell_units; Tn = a.sell_units; }
+    else { const uint32_t b0 = a.sell_off[sn], b1 = a.sell_off[sn + 1]; on = (int64_t)b0; Tn = (int)(b1 - b0); }
+    ent_next = ent_first<NTM>(a, rn, on, Tn);
+  };
+  if (ENT) {                                  // all 256 slots exist in the handle's table (zero behind the last pair: 0xFF reads slot 255)
+    const int32_t *eo = static_cast<const int32_t *>(a.sell_ent);
+    const double *ev = reinterpret_cast<const double *>(eo + 256);
+    ent_prefetch(rb_begin);
+    for (int i = tid; i < 256; i += kBlock) { s_tab[i] = eo[i]; s_val[i] = ev[i]; }
+    __syncthreads();
+  } else if (!COLS32) {
     for (int i = tid; i < 256; i += kBlock) s_tab[i] = i < a.code_T ? a.code_tab[i] : 0;
     __syncthreads();
   }
@@ -484,7 +544,15 @@ __global__ __launch_bounds__(kBlock) void spmv_sell_kernel(SpmvArgs a, RedArgs r
       const unsigned long long *base = a.sell + (size_t)o0 * 64 + (rowl & 63);
       double acc = 0.0, wv = 0.0;
       if (DOT) wv = a.dotw[rowl];                 // in flight beside the row's entries (2.06 -> 1.97 ms fused at 512^3, profiles/r06ap/aq)
-      if (PAIR) {                                // T = 8 or 10 words: four or five 16-byte loads bring the whole row
+      if (ENT) {                                 // T words of eight entry codes and nothing else
+        dbl2 ce = ent_next;                      // loaded one row block ahead
+        ent_prefetch(rb + 1);                    // ... and the next block's, beside this block's gathers
+        const dbl2 *pb = reinterpret_cast<const dbl2 *>(a.sell + (size_t)o0 * 64) + (rowl & 63);
+        for (int w = 0; w < T; ++w) {
+          if (w >= 2 && (w & 1) == 0) ce = ld<NTM>(pb + (size_t)(w >> 1) * 64);
+          acc = ent_step<DIST>(a, row, (unsigned long long)__double_as_longlong((w & 1) ? ce.y : ce.x), s_tab, s_val, acc);
+        }
+      } else if (PAIR) {                         // T = 8 or 10 words: four or five 16-byte loads bring the whole row
         const dbl2 *pb = reinterpret_cast<const dbl2 *>(a.sell + (size_t)o0 * 64) + (rowl & 63);
         dbl2 el[5];
 #pragma unroll
@@ -1098,9 +1166,10 @@ static void launch_code_cfg(khip_ctx *ctx, const SpmvArgs &a, const RedArgs &ra,
 
 static void launch_sell_cfg(khip_ctx *ctx, const SpmvArgs &a, const RedArgs &ra, unsigned grid, bool dot, bool comp, bool dist) {
   const size_t pub = dot && a.blk_pub ? sizeof(dd) * (size_t)kBlock * (a.dot_sq ? 2u : 1u) : 0u;
-  const size_t lds = pub + 4u * 256u;
+  const size_t lds = pub + 4u * 256u + (a.sell_ent ? 8u * 256u : 0u);
 #define KHIP_SELL(DOT, COMP, DIST, NTM, COLS32, C4) \
-  do { if (a.sell_pair == 1) hipLaunchKernelGGL((spmv_sell_kernel<DOT, COMP, DIST, NTM, false, false, true, false>), dim3(grid), dim3(kBlock), lds, ctx->stream, a, ra); \
+  do { if (a.sell_ent) hipLaunchKernelGGL((spmv_sell_kernel<DOT, COMP, DIST, NTM, false, false, false, false, true>), dim3(grid), dim3(kBlock), lds, ctx->stream, a, ra); \
+       else if (a.sell_pair == 1) hipLaunchKernelGGL((spmv_sell_kernel<DOT, COMP, DIST, NTM, false, false, true, false>), dim3(grid), dim3(kBlock), lds, ctx->stream, a, ra); \
        else if (a.sell_pair == 2) hipLaunchKernelGGL((spmv_sell_kernel<DOT, COMP, DIST, NTM, COLS32, false, false, true>), dim3(grid), dim3(kBlock), lds, ctx->stream, a, ra); \
        else hipLaunchKernelGGL((spmv_sell_kernel<DOT, COMP, DIST, NTM, COLS32, C4, false, false>), dim3(grid), dim3(kBlock), lds, ctx->stream, a, ra); } while (0)
 #define KHIP_L(DOT, COMP, DIST) \
@@ -1232,6 +1301,11 @@ SpmvPlan spmv_plan(khip_ctx *ctx, const khip_csr *A, bool build) {
     if (rows != 256 && rows != 128 && rows != 64 && rows != 32) rows = 256;
     const bool coded = try_codes && A->code_state == 1;
     // sliced form of the coded operator (csr_build_sell)
+    // ... entry-coded where the handle allows (spmv_sell_entries: 1 = the size rule of the codes, 2 = any size); a refusal is kept on
+    // the handle (sell_ent_state = -1) and the copy with values is built instead
+    const bool try_ent = t.spmv_sell_entries && (t.spmv_sell_entries != 1 || big);
+    if (build && coded && t.spmv_sell && A->code_bits == 8 && A->sell_state == 0 && try_ent && A->sell_ent_state == 0)
+      optional_build(csr_build_sell_entries(ctx, Am));
     if (build && coded && t.spmv_sell && A->code_bits == 8 && A->sell_state == 0) optional_build(csr_build_sell(ctx, Am));
     if (coded && t.spmv_sell && A->sell_state == 1) p.form = SpmvForm::Sliced;      // no window: one row per lane whatever the row length
     else {
@@ -1311,7 +1385,7 @@ int launch_spmv(khip_ctx *ctx, const khip_csr *A, const double *x, double *y, in
   a.nnz_bound = A->nnz + kPad;
   a.fake_gather = 0; a.stream_nt = 0;
   a.code = nullptr; a.code_tab = nullptr; a.code_T = 0; a.stage_rows = 256;
-  a.sell = nullptr; a.sell_off = nullptr; a.sell_units = 0; a.sell_cols = 0; a.sell_c4 = nullptr; a.sell_pair = 0;
+  a.sell = nullptr; a.sell_off = nullptr; a.sell_units = 0; a.sell_cols = 0; a.sell_c4 = nullptr; a.sell_pair = 0; a.sell_ent = nullptr;
   a.blk_pub = ctx->tune.spmv_blk_pub;
   a.dcode = nullptr; a.dbase = nullptr; a.desc_ptr = nullptr; a.desc_pos = nullptr; a.desc_col = nullptr;
   a.blockptr = (A->blockptr && (row_lo & 255) == 0) ? A->blockptr : nullptr;
@@ -1409,6 +1483,7 @@ int launch_spmv(khip_ctx *ctx, const khip_csr *A, const double *x, double *y, in
     if (form == SpmvForm::Sliced || form == SpmvForm::Coded) { a.code = A->code; a.code_tab = A->code_tab; a.code_T = A->code_T; }
     if (form == SpmvForm::Sliced) {
       a.sell = A->sell; a.sell_off = A->sell_off; a.sell_units = A->sell_units; a.sell_cols = 0; a.sell_c4 = A->sell_c4; a.sell_pair = A->sell_pair;
+      a.sell_ent = A->sell_ent_state == 1 ? A->sell_ent_tab : nullptr;
       launch_sell_cfg(ctx, a, ra, grid, dot, comp, dist);
     } else if (form == SpmvForm::Sliced32) {
       a.sell = A->sell32; a.sell_off = A->sell32_off; a.sell_units = A->sell32_units; a.sell_cols = 1; a.sell_pair = A->sell32_pair; a.sell_c4 = nullptr;

@@ -55,6 +55,7 @@ struct SpmvArgs {
   int sell_cols;             // 0: code words (eight 1-byte codes), 1: column words (two int32 columns)
   int sell_pair;             // the words of a row interleaved in 16-byte pairs (rows of at most 8 entries, one code word)
   const uint32_t *sell_c4;   // narrow codes: eight 4-bit codes per row in one word indexed by the row (the slices hold values only); null otherwise
+  const void *sell_ent;      // entry-coded slices (csr_build_sell_entries): the dictionary, int32 offset[256] then double value[256]; the slices hold code words only; null otherwise
   // block-delta column stream (coldelta.hip): col = dbase[block] + dcode[k]; all-ones code = escape
   const void *dcode;         // uint8_t[nnz + pad] or uint16_t[nnz + pad]
   const int32_t *dbase;      // base column of every row block

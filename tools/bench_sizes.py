@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """CG iterations/s on get_div_grad(n1^3) for a ladder of sizes and fusion levels (1 GPU): the latency -> bandwidth
-transition.  JSON lines."""
+transition.  JSON lines.  Arguments key=value set context options first (e.g. spmv_sell_entries=2)."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import krylov_jl_amd as K
 ctx = K.Context(0)
+for kv in sys.argv[1:]:
+    k, v = kv.split("=")
+    ctx.set_option(k, int(v))
 for n1 in (32, 64, 96, 128, 192, 256, 384, 512):
     n = n1 ** 3
     A = K.CsrMatrix.stencil(ctx, "poisson", n1)
