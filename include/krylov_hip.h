@@ -597,6 +597,39 @@ int khip_bilq_last_path(khip_bilq_workspace *ws);
 double           *khip_bilq_vector(khip_bilq_workspace *ws, const char *name);
 size_t            khip_bilq_workspace_bytes(khip_bilq_workspace *ws);   /* 8n doubles without M, N and warm start */
 
+/* ---- qmr! (src/qmr.jl:124-406), real Float64: square nonsymmetric systems by the same two-sided Lanczos process as bilq!, with the
+ * quasi-minimal residual iterate and the residual bound |ζbarₖ₊₁| √τₖ₊₁.  QmrWorkspace (src/krylov_workspaces.jl): uₖ₋₁, uₖ, q, vₖ₋₁,
+ * vₖ, p, x, wₖ₋₂, wₖ₋₁ (9 vectors of n doubles), + Δx with a warm start, + t with M, + s with N (allocated lazily, counted by
+ * stats.allocation_timer).  The adjoint travels as its own operator, as for bilq!.  options.radius, linesearch, restart,
+ * reorthogonalization and variant are ignored.  The fused loops rotate the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and (wₖ₋₂, wₖ₋₁) instead
+ * of copying or swapping, and khip_qmr_vector returns a name's pointer by its current role: after k iterations every name holds what
+ * the reference's variable of that name holds ("w_prev" = wₖ, "w_prev2" = wₖ₋₁), in whichever buffer. */
+typedef struct khip_qmr_workspace khip_qmr_workspace;
+typedef struct {
+  const khip_operator *Mt, *Nt; /* adjoints of M, N; NULL = the operator is applied as its own adjoint: right for a diagonal (Jacobi) one only, the caller's duty otherwise */
+} khip_qmr_params;
+khip_qmr_params khip_qmr_default_params(void);   /* Mt = Nt = NULL */
+int khip_qmr_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_qmr_workspace **out);   /* m != n: KHIP_ERR_INVALID "System must be square" */
+/* QmrWorkspace on the caller's nine vectors; every pointer must be distinct.  adopt_vector names: "dx" (Δx: warm_start! fills it on
+ * the caller's side and hands it over, then khip_qmr_warm_start(ws, dx) only sets the flag), "t" (needed with M), "s" (needed with N) */
+int khip_qmr_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *u_prev, double *u, double *q, double *v_prev, double *v,
+                             double *p, double *x, double *w_prev2, double *w_prev, khip_qmr_workspace **out);
+int khip_qmr_workspace_adopt_vector(khip_qmr_workspace *ws, const char *name, double *ptr);
+int khip_qmr_workspace_destroy(khip_qmr_workspace *ws);
+int khip_qmr_warm_start(khip_qmr_workspace *ws, const double *x0);
+/* qmr!(ws, A, b; c, M, N, atol, rtol, itmax, timemax, verbose, history, callback).  At = A' is required (NULL: KHIP_ERR_INVALID);
+ * c == NULL means c = b; M / N == NULL mean the identity, otherwise q <- M A N v and p <- Nt At Mt u.
+ * Loops (khip_qmr_last_path): 2 = device-resident (A and At CSR handles, M = N = I, no callback, verbose = 0), 1 = host-driven on the
+ * same kernels (same bits as 2), 0 = one launch per primitive (options.fused = 0). */
+int khip_qmr_solve(khip_qmr_workspace *ws, const khip_operator *A, const khip_operator *At, const khip_operator *M,
+                   const khip_operator *N, const double *b, const double *c, const khip_options *opts, const khip_qmr_params *params);
+double           *khip_qmr_solution(khip_qmr_workspace *ws);
+const khip_stats *khip_qmr_stats(khip_qmr_workspace *ws);
+int khip_qmr_last_path(khip_qmr_workspace *ws);
+/* named work vectors: "u_prev", "u", "q", "v_prev", "v", "p", "x", "w_prev2", "w_prev", "dx", "t", "s" (NULL while not allocated) */
+double           *khip_qmr_vector(khip_qmr_workspace *ws, const char *name);
+size_t            khip_qmr_workspace_bytes(khip_qmr_workspace *ws);   /* 9n doubles without M, N and warm start */
+
 int khip_gmres_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, int memory, khip_gmres_workspace **out);
 /* GmresWorkspace on the caller's x, w and basis V_host[0 .. memory) (device pointers in a HOST array; `V::Vector{S}`,
  * src/krylov_workspaces.jl:2857-2873).  adopt_vector names: "x", "w", "p", "q", "dx".  adopt_basis replaces the whole list

@@ -526,6 +526,67 @@ function Krylov.bilq!(ws::BilqWs, A::HIPCsr, b::HIPVector; c::HIPVector = b, tra
   return ws
 end
 
+# ------------------------------------------------------------------------------------------------ qmr!  (src/qmr.jl:124-406)
+struct QmrParams                    # khip_qmr_params: the adjoints of M and N (NULL: the operator itself)
+  Mt::Ptr{Operator}; Nt::Ptr{Operator}
+end
+const QmrWs = QmrWorkspace{Float64,Float64,HIPVector}
+function qmr_handle(ws::QmrWs)
+  get!(HANDLES, ws) do
+    r = Ref{Ptr{Cvoid}}()
+    ck(ccall((:khip_qmr_workspace_adopt, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                                                     Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Ptr{Cvoid}}),
+             CTX[].h, ws.m, ws.n, ws.uₖ₋₁.ptr, ws.uₖ.ptr, ws.q.ptr, ws.vₖ₋₁.ptr, ws.vₖ.ptr, ws.p.ptr, ws.x.ptr, ws.wₖ₋₂.ptr, ws.wₖ₋₁.ptr, r))
+    h = r[]
+    finalizer(_ -> ccall((:khip_qmr_workspace_destroy, lib), Cint, (Ptr{Cvoid},), h), ws)
+    h
+  end
+end
+qmr_adopt(h, name, v::HIPVector) = ck(ccall((:khip_qmr_workspace_adopt_vector, lib), Cint, (Ptr{Cvoid}, Cstring, Ptr{Cdouble}), h, name, dptr(v)))
+
+# As for bilq!: the adjoint is `A'`, built once per matrix and cached in `A.adj`; M and N are I or the library's Jacobi operator
+# (its own adjoint, so Mt = Nt = NULL is right); ILU(0) is refused rather than run as N A' M in place of N' A' M'.
+# After the solve only ws.x and ws.stats are defined: the library rotates the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and (wₖ₋₂, wₖ₋₁) among the adopted vectors.
+function Krylov.qmr!(ws::QmrWs, A::HIPCsr, b::HIPVector; c::HIPVector = b, M = I, N = I, ldiv::Bool = false,
+                     atol::Float64 = √eps(Float64), rtol::Float64 = √eps(Float64), itmax::Int = 0, timemax::Float64 = Inf,
+                     verbose::Int = 0, history::Bool = false, callback = nothing, iostream::IO = Krylov.kstdout, fused::Int = 2)
+  for (name, P) in (("M", M), ("N", N))
+    (P isa HIPOperator && P.kind !== :jacobi) &&
+      error("qmr!: $name = $(P.kind) is not its own adjoint and its transposed solve is not available: use I or KrylovHIP.jacobi(A)")
+  end
+  if ldiv || !self_adjoint_precond(M) || !self_adjoint_precond(N) || !native_log(verbose, iostream)
+    GENERIC_SOLVES[] += 1
+    return invoke(Krylov.qmr!, Tuple{QmrWs,Any,AbstractVector{Float64}}, ws, A, b; c, M, N, ldiv, atol, rtol, itmax, timemax,
+                  verbose, history, callback = callback === nothing ? (w -> false) : callback, iostream)
+  end
+  m, n = size(A)                                                                            # :130-133
+  (m == ws.m && n == ws.n) || error("(workspace.m, workspace.n) = ($(ws.m), $(ws.n)) is inconsistent with size(A) = ($m, $n)")
+  m == n || error("System must be square")
+  length(b) == m || error("Inconsistent problem size")
+  Krylov.allocate_if(M !== I, ws, :t, HIPVector, ws.x)                                       # :151-152
+  Krylov.allocate_if(N !== I, ws, :s, HIPVector, ws.x)
+  At = A'
+  h = qmr_handle(ws)
+  for (name, v) in (("t", ws.t), ("s", ws.s), ("dx", ws.Δx))
+    qmr_adopt(h, name, v)
+  end
+  ws.warm_start && ck(ccall((:khip_qmr_warm_start, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h, ws.Δx.ptr))
+  sp = ccall((:khip_qmr_stats, lib), Ptr{Stats}, (Ptr{Cvoid},), h)
+  cbf, cbd, box = callback_args(user_callback(callback), ws, sp, history)
+  opts = Ref(Options(; atol, rtol, itmax, timemax, history, fused, verbose, log_fd = logfd(iostream), callback = cbf, callback_data = cbd))
+  prm = Ref(QmrParams(C_NULL, C_NULL))
+  opA = Ref(Operator(A));  opAt = Ref(Operator(At))
+  rc = GC.@preserve ws A At b c M N opts prm opA opAt box ccall((:khip_qmr_solve, lib), Cint,
+         (Ptr{Cvoid}, Ref{Operator}, Ref{Operator}, Ptr{Operator}, Ptr{Operator}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Options}, Ptr{Cvoid}),
+         h, opA, opAt, opref(M), opref(N), b.ptr, c.ptr, opts, prm)
+  st = fill_stats!(ws.stats, sp, history)
+  NATIVE_SOLVES[] += 1;  LAST_PATH[] = ccall((:khip_qmr_last_path, lib), Cint, (Ptr{Cvoid},), h)
+  ws.warm_start = false
+  finish_callback(box)
+  rc == 0 || failed(st)
+  return ws
+end
+
 # ------------------------------------------------------------------------------------------------ cg_lanczos_shift!  (src/cg_lanczos_shift.jl:107-284)
 struct LanczosShiftParams           # khip_cg_lanczos_shift_params: shifts (host array), nshifts, check_curvature
   shifts::Ptr{Cdouble}; nshifts::Cint; check_curvature::Cint

@@ -242,6 +242,9 @@ end
     x, stats = bilq(U_gpu, S(bu_cpu))                                # needs A' (khip_csr_transpose)
     @test norm(bu_cpu - U_cpu * Vector(x)) ≤ 1e-5 * norm(bu_cpu)
     At = U_gpu'; bilq(U_gpu, S(bu_cpu)); @test U_gpu' === At          # the second solve reuses the transposed operator
+    x, stats = native(2) do; qmr(U_gpu, S(bu_cpu)); end              # the same process, the quasi-minimal residual iterate
+    @test norm(bu_cpu - U_cpu * Vector(x)) ≤ 1e-5 * norm(bu_cpu)
+    @test U_gpu' === At
   end
 
   @testset "solver -- $FC" begin                                     # test/gpu/gpu.jl test_solver

@@ -66,6 +66,10 @@ class CBilqParams(C.Structure):
     _fields_ = [("transfer_to_bicg", C.c_int), ("Mt", C.POINTER(COperator)), ("Nt", C.POINTER(COperator))]
 
 
+class CQmrParams(C.Structure):
+    _fields_ = [("Mt", C.POINTER(COperator)), ("Nt", C.POINTER(COperator))]
+
+
 class CStats(C.Structure):
     _fields_ = [("niter", C.c_int), ("solved", C.c_int), ("inconsistent", C.c_int), ("indefinite", C.c_int),
                 ("npcCount", C.c_int), ("timer", C.c_double), ("status", C.c_char * 96),
@@ -260,6 +264,19 @@ SIGNATURES = {
     "khip_bilq_last_path": (_int, [_vp]),
     "khip_bilq_vector": (_vp, [_vp, C.c_char_p]),
     "khip_bilq_workspace_bytes": (_sz, [_vp]),
+    "khip_qmr_default_params": (CQmrParams, []),
+    "khip_qmr_workspace_create": (_int, [_vp, _i64, _i64, c_void_pp]),
+    "khip_qmr_workspace_adopt": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_void_pp]),
+    "khip_qmr_workspace_adopt_vector": (_int, [_vp, C.c_char_p, _vp]),
+    "khip_qmr_workspace_destroy": (_int, [_vp]),
+    "khip_qmr_warm_start": (_int, [_vp, _vp]),
+    "khip_qmr_solve": (_int, [_vp, C.POINTER(COperator), C.POINTER(COperator), C.POINTER(COperator), C.POINTER(COperator), _vp, _vp,
+                              C.POINTER(COptions), C.POINTER(CQmrParams)]),
+    "khip_qmr_solution": (_vp, [_vp]),
+    "khip_qmr_stats": (C.POINTER(CStats), [_vp]),
+    "khip_qmr_last_path": (_int, [_vp]),
+    "khip_qmr_vector": (_vp, [_vp, C.c_char_p]),
+    "khip_qmr_workspace_bytes": (_sz, [_vp]),
     "khip_block_gmres_workspace_bytes": (_sz, [_vp, C.POINTER(C.c_size_t)]),
     "khip_test_gen_banded_random_host": (_int, [_i64, _int, _int, C.c_uint64, _int, _int, _i64, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_double_p, C.POINTER(_i64)]),
     "khip_test_small_dense": (_int, [_int, _int, _int, _int, c_double_p, c_double_p, c_double_p]),
@@ -1535,6 +1552,32 @@ class BilqWorkspace(_Workspace):
         return DeviceVector(self.ctx, self.n, ptr=p, owner=self) if p else None
 
 
+class QmrWorkspace(_Workspace):
+    """QmrWorkspace(m, n, S) (src/krylov_workspaces.jl): uₖ₋₁, uₖ, q, vₖ₋₁, vₖ, p, x, wₖ₋₂, wₖ₋₁; Δx, t, s stay empty until needed.  The
+    fused loops rotate the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and (wₖ₋₂, wₖ₋₁), and `vector(name)` follows the role (khip_qmr_vector):
+    after k iterations a name holds what the reference's variable of that name holds."""
+    _prefix = "qmr"
+    VECTORS = ("u_prev", "u", "q", "v_prev", "v", "p", "x", "w_prev2", "w_prev")
+
+    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
+        self.ctx, self.m, self.n = ctx, m, n
+        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
+        self._h = C.c_void_p()
+        if self.adopted:
+            t0 = time.perf_counter()
+            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(n) for k in self.VECTORS}
+            self._alloc_s = time.perf_counter() - t0
+            _ck(lib().khip_qmr_workspace_adopt(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
+        else:
+            _ck(lib().khip_qmr_workspace_create(ctx._h, m, n, C.byref(self._h)))
+
+    def vector(self, name: str):
+        if name == "x":
+            return self.x
+        p = lib().khip_qmr_vector(self._h, name.encode())
+        return DeviceVector(self.ctx, self.n, ptr=p, owner=self) if p else None
+
+
 def _finish(ws, rc):
     ws._timer_extra = 0.0          # an entry point that did work of its own before the solve adds it afterwards
     if rc != 0:
@@ -1616,10 +1659,10 @@ def cg_lanczos_shift_(ws: CgLanczosShiftWorkspace, A, b: DeviceVector, shifts, M
     return _finish(ws, rc)
 
 
-def _adjoint_of(A):
+def _adjoint_of(A, solver: str = "bilq"):
     """A' of a CsrMatrix, built once (khip_csr_transpose) and kept on the object; any other operator must bring its own."""
     if not isinstance(A, CsrMatrix):
-        raise KhipError(-1, "bilq: a matrix-free A needs its adjoint passed as At")
+        raise KhipError(-1, f"{solver}: a matrix-free A needs its adjoint passed as At")
     At = getattr(A, "_adjoint", None)
     if At is None:
         At = A.transpose()
@@ -1627,13 +1670,13 @@ def _adjoint_of(A):
     return At
 
 
-def _bilq_precond_adjoint(name: str, op, adjoint):
-    """The adjoint bilq! applies for the preconditioner `op` (M or N): the one given, else `op` itself where that is right -- the
+def _bilq_precond_adjoint(name: str, op, adjoint, solver: str = "bilq"):
+    """The adjoint bilq! or qmr! (`solver`) applies for the preconditioner `op` (M or N): the one given, else `op` itself where that is right -- the
     identity (None) and Jacobi (diagonal).  ILU(0) of a nonsymmetric A or a callable is not its own adjoint: without an explicit
     adjoint the solve would run N A' M in place of N' A' M' and still report convergence, so it is refused."""
     if op is None or adjoint is not None or isinstance(op, Jacobi):
         return adjoint
-    raise KhipError(-1, f"bilq: {name} = {type(op).__name__} is not known to be its own adjoint: pass {name}t (the operator "
+    raise KhipError(-1, f"{solver}: {name} = {type(op).__name__} is not known to be its own adjoint: pass {name}t (the operator "
                         f"y <- {name}' x), or use a Jacobi {name}")
 
 
@@ -1664,6 +1707,31 @@ def bilq_(ws: BilqWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, 
     return _finish(ws, rc)
 
 
+def qmr_(ws: QmrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, M=None, N=None, At=None, Mt=None, Nt=None, **kw):
+    """qmr!(workspace, A, b; c, M, N, ldiv, atol, rtol, itmax, timemax, verbose, history, callback, iostream)
+    (src/qmr.jl:124-406).  At: the adjoint of A (default: A.transpose(), cached on A); Mt / Nt: the adjoints of M / N, required
+    unless the operator is a Jacobi (its own adjoint).  Returns the workspace."""
+    keep = []
+    Mt = _bilq_precond_adjoint("M", M, Mt, solver="qmr")
+    Nt = _bilq_precond_adjoint("N", N, Nt, solver="qmr")
+    if len(b) != ws.n:
+        raise KhipError(-1, "Inconsistent problem size")
+    if At is None:
+        At = _adjoint_of(A, solver="qmr")
+    ws._allocate_if(M is not None, "t")                                                   # src/qmr.jl:151-152
+    ws._allocate_if(N is not None, "s")
+    opts = _make_options(keep=keep, ws=ws, **kw)
+    prm = lib().khip_qmr_default_params()
+    if Mt is not None:
+        prm.Mt = C.cast(_make_operator(ws.ctx, Mt, ws.n, keep), C.POINTER(COperator))
+    if Nt is not None:
+        prm.Nt = C.cast(_make_operator(ws.ctx, Nt, ws.n, keep), C.POINTER(COperator))
+    rc = lib().khip_qmr_solve(ws._h, _make_operator(ws.ctx, A, ws.n, keep), _make_operator(ws.ctx, At, ws.n, keep),
+                              _make_operator(ws.ctx, M, ws.n, keep), _make_operator(ws.ctx, N, ws.n, keep), _p(b), _p(c),
+                              C.byref(opts), C.byref(prm))
+    return _finish(ws, rc)
+
+
 def _local_rows(A):
     return A.m if isinstance(A, CsrMatrix) else None
 
@@ -1691,6 +1759,8 @@ FORWARDED_DEFAULTS = {
                              verbose=0, history=False, callback=default_callback, iostream=None),
     "bilq": dict(c=None, transfer_to_bicg=True, M=None, N=None, ldiv=False, atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0,
                  timemax=math.inf, verbose=0, history=False, callback=default_callback, iostream=None),
+    "qmr": dict(c=None, M=None, N=None, ldiv=False, atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0, timemax=math.inf, verbose=0,
+                history=False, callback=default_callback, iostream=None),
 }
 WORKSPACE_KWARGS = {"gmres": dict(memory=20), "block_gmres": dict(memory=5)}      # kwargs_workspace_gmres, _block_gmres
 # kwargs_workspace_minres (src/minres.jl:159): kept apart from WORKSPACE_KWARGS, whose contents tests/test_abi.py pins
@@ -1712,7 +1782,8 @@ def _forward(method: str, kw: dict) -> dict:
 def krylov_workspace(method: str, *args, ctx: Context | None = None, **kw):
     """krylov_workspace(Val(method), m, n, S; memory) / (Val(method), A, b; memory) (src/interface.jl:117-141, 237-244)."""
     cls = {"cg": CgWorkspace, "gmres": GmresWorkspace, "bicgstab": BicgstabWorkspace, "block_gmres": BlockGmresWorkspace,
-           "minres": MinresWorkspace, "cg_lanczos_shift": CgLanczosShiftWorkspace, "bilq": BilqWorkspace}[method]
+           "minres": MinresWorkspace, "cg_lanczos_shift": CgLanczosShiftWorkspace, "bilq": BilqWorkspace,
+           "qmr": QmrWorkspace}[method]
     if method == "cg_lanczos_shift":                                            # (A, b, nshifts) / (m, n, nshifts)
         if isinstance(args[1], DeviceVector):
             A, b, nshifts = args
@@ -1808,6 +1879,11 @@ def minres(A, b: DeviceVector, x0=None, **kw):
 def bilq(A, b: DeviceVector, x0=None, **kw):
     """Out-of-place bilq(A, b[, x0]; kwargs...) -> (x, stats, workspace) (src/bilq.jl:118-126); A' is taken once and kept on A."""
     return krylov_solve("bilq", A, b, x0, **kw)
+
+
+def qmr(A, b: DeviceVector, x0=None, **kw):
+    """Out-of-place qmr(A, b[, x0]; kwargs...) -> (x, stats, workspace) (src/qmr.jl:124-132); A' is taken once and kept on A."""
+    return krylov_solve("qmr", A, b, x0, **kw)
 
 
 def cg_lanczos_shift(A, b: DeviceVector, shifts, **kw):
@@ -2262,4 +2338,5 @@ def block_gmres(A, B, X0=None, ctx=None, **kw):
 
 _INPLACE.update({CgWorkspace: ("cg", cg_), GmresWorkspace: ("gmres", gmres_), BicgstabWorkspace: ("bicgstab", bicgstab_),
                  BlockGmresWorkspace: ("block_gmres", block_gmres_), MinresWorkspace: ("minres", minres_), BilqWorkspace: ("bilq", bilq_),
+                 QmrWorkspace: ("qmr", qmr_),
                  CgLanczosShiftWorkspace: ("cg_lanczos_shift", cg_lanczos_shift_)})

@@ -16,7 +16,7 @@ namespace khip {
 
 enum Epilogue { EPI_NONE = 0, EPI_CG_STEP1 = 1, EPI_CG_STEP2 = 2, EPI_BICG_A = 3, EPI_BICG_B = 4, EPI_BICG_C = 5, EPI_CGCG = 6,
                EPI_MINRES_A = 7, EPI_MINRES_B = 8, EPI_MINRES_C = 9, EPI_LZSHIFT_A = 10, EPI_LZSHIFT_B = 11,
-               EPI_BILQ_A = 12, EPI_BILQ_B = 13, EPI_BILQ_C = 14 };
+               EPI_BILQ_A = 12, EPI_BILQ_B = 13, EPI_BILQ_C = 14, EPI_QMR_A = 15, EPI_QMR_B = 16, EPI_QMR_C = 17 };
 
 struct CgDevState {
   double gamma;        // r.z of the current iterate              (src/cg.jl:162, 257)
@@ -290,10 +290,15 @@ __host__ __device__ inline void sym_givens(double a, double b, double &c, double
 // residual estimates of the LQ and CG points and the stopping tests.  The same three steps run on the host (loops 0 and 1) and as
 // the epilogues of the three reductions of an iteration (device-resident loop): one source, the reference's IEEE operations in its
 // order, so loops 1 and 2 produce the same bits.  Field names follow the reference.
-struct BilqDevState {
-  // coefficients the vector kernels read
-  double gamma, beta;            // γₖ, βₖ: P1                                   (:244-245)
-  double alpha;                  // αₖ: P2                                       (:247-250)
+// The coefficients of the two-sided Lanczos process that P1 and P2 (bilanczos_passes.hpp) read: the common leading part of the states
+// of bilq! and qmr!, which run the same biorthogonalisation (src/bilq.jl:234-252 = src/qmr.jl:238-258).
+struct BiLanczosCoef {
+  double gamma, beta;            // γₖ, βₖ: P1                                   (src/bilq.jl:244-245, src/qmr.jl:248-249)
+  double alpha;                  // αₖ: P2                                       (src/bilq.jl:247-250, src/qmr.jl:251-254)
+};
+
+struct BilqDevState : BiLanczosCoef {
+  // coefficients the vector kernels read (γₖ, βₖ, αₖ: BiLanczosCoef)
   double beta_next, gamma_next;  // βₖ₊₁, γₖ₊₁: the divisors of P3               (:253-254, :329-330)
   double pq;                     // pᴴq                                          (:252)
   double zc, zs, neg_c, sn;      // ζₖ₋₁cₖ, ζₖ₋₁sₖ, -cₖ, sₖ: the x and d̅ updates (:316-321)
@@ -380,6 +385,83 @@ __host__ __device__ inline bool bilq_step_c(BilqDevState &s, double vv_next, dou
   s.breakdown = (!s.solved_lq && !s.solved_cg && s.pq == 0.0) ? 1 : 0;
   s.iter = k;
   return s.solved_lq || s.solved_cg || s.breakdown;
+}
+
+// qmr! (src/qmr.jl:124-406), real Float64: the scalars of the two-sided Lanczos process, of the QR factorisation of Tₖ₊₁.ₖ, the
+// residual bound |ζbarₖ₊₁| √τₖ₊₁ and the stopping tests.  As for bilq!: the same three steps run on the host (loops 0 and 1) and as
+// the epilogues of the three reductions of an iteration (device-resident loop), so loops 1 and 2 produce the same bits.
+struct QmrDevState : BiLanczosCoef {
+  // coefficients the vector kernels read (γₖ, βₖ, αₖ: BiLanczosCoef)
+  double beta_next, gamma_next;  // βₖ₊₁, γₖ₊₁: the divisors of P3               (:257-258, :345-346)
+  double pq;                     // pᴴq                                          (:256)
+  double neg_eps, neg_lambda;    // -ϵₖ₋₂, -λₖ₋₁: kscal! and the first kaxpy! of wₖ (:329, :331)
+  double delta, inv_delta;       // δₖ: kdivcopy!(w₁, v₁, δ₁) (:318); one(T) / δₖ: kdiv!(wₖ, δₖ) = kscal!(one(T) / δₖ) (:325, :333)
+  double zeta;                   // ζₖ: x = x + ζₖ wₖ                             (:338)
+  // constants of the solve
+  double eps_tol;                // ε = atol + rtol ‖r₀‖                          (:205)
+  // recurrences
+  double c_km2, c_km1, s_km2, s_km1;   // cₖ₋₂, cₖ₋₁, sₖ₋₂, sₖ₋₁
+  double epsilon, lambda;        // ϵₖ₋₂, λₖ₋₁
+  double zbar, zbar_next;        // ζbarₖ, ζbarₖ₊₁
+  double tau;                    // τₖ
+  double rNorm;
+  long long stop_seq, iter, hist_base, hist_cap;
+  double *hist;                  // device history window (null: no history)
+  int solved, breakdown;
+};
+
+// after αₖ = ⟨uₖ, q⟩ (:251)
+__host__ __device__ inline void qmr_step_a(QmrDevState &s, double uq) { s.alpha = uq; }
+
+// after pᴴq = ⟨p, q⟩: βₖ₊₁, γₖ₊₁, the two previous reflections, the new one, ζₖ and ζbarₖ₊₁ (:256-312); k = iter
+__host__ __device__ inline void qmr_step_b(QmrDevState &s, double pq, long long k) {
+  s.pq = pq;
+  s.beta_next = sqrt(fabs(pq));
+  s.gamma_next = pq / s.beta_next;
+  double lbar = 0.0, dbar;       // λbarₖ₋₁, δbarₖ
+  if (k >= 3) {
+    s.epsilon = s.s_km2 * s.gamma;
+    lbar = -s.c_km2 * s.gamma;
+  }
+  if (k >= 2) {
+    if (k == 2) lbar = s.gamma;
+    s.lambda = s.c_km1 * lbar + s.s_km1 * s.alpha;
+    dbar = s.s_km1 * lbar - s.c_km1 * s.alpha;
+    s.s_km2 = s.s_km1;
+    s.c_km2 = s.c_km1;
+  } else {
+    dbar = s.alpha;
+  }
+  double c, sn;
+  sym_givens(dbar, s.beta_next, c, sn, s.delta);
+  s.zeta = c * s.zbar;
+  s.zbar_next = sn * s.zbar;
+  s.s_km1 = sn;
+  s.c_km1 = c;
+  s.neg_eps = -s.epsilon;
+  s.neg_lambda = -s.lambda;
+  s.inv_delta = 1.0 / s.delta;
+}
+
+// after ‖vₖ₊₁‖² = ⟨vₖ₊₁, vₖ₊₁⟩ (:350-376): τₖ₊₁, the residual bound, the history entry, the shifts and the tests; true when the
+// loop stops (tired / overtimed / the callback are the driver's)
+__host__ __device__ inline bool qmr_step_c(QmrDevState &s, double vv_next, long long k) {
+  const double tau_next = s.tau + vv_next;
+  s.rNorm = fabs(s.zbar_next) * sqrt(tau_next);
+  if (s.hist) {
+    const long long idx = k - 1 - s.hist_base;
+    if (idx >= 0 && idx < s.hist_cap) s.hist[idx] = s.rNorm;
+  }
+  s.zbar = s.zbar_next;
+  s.beta = s.beta_next;
+  s.gamma = s.gamma_next;
+  s.tau = tau_next;
+  const bool resid_decrease_mach = (s.rNorm + 1.0 <= 1.0);
+  const bool resid_decrease_lim = (s.rNorm <= s.eps_tol);
+  s.solved = (resid_decrease_lim || resid_decrease_mach) ? 1 : 0;
+  s.breakdown = (!s.solved && s.pq == 0.0) ? 1 : 0;
+  s.iter = k;
+  return s.solved || s.breakdown;
 }
 
 __device__ __forceinline__ bool seq_skip(const long long *stop_seq, long long seq) {
@@ -476,6 +558,14 @@ __device__ inline void solver_epilogue(int epi, void *state, const double *v, lo
   } else if (epi == EPI_BILQ_C) {                  // v = (v_k.v_k+1, v_k+1.v_k+1)   :334-371
     BilqDevState *st = static_cast<BilqDevState *>(state);
     if (bilq_step_c(*st, v[0], sqrt(v[1]), st->iter + 1)) st->stop_seq = seq + 1;
+  } else if (epi == EPI_QMR_A) {                   // v[0] = u.q                 src/qmr.jl:251
+    qmr_step_a(*static_cast<QmrDevState *>(state), v[0]);
+  } else if (epi == EPI_QMR_B) {                   // v[0] = p.q                 :256-312
+    QmrDevState *st = static_cast<QmrDevState *>(state);
+    qmr_step_b(*st, v[0], st->iter + 1);
+  } else if (epi == EPI_QMR_C) {                   // v[0] = v_k+1.v_k+1         :350-376
+    QmrDevState *st = static_cast<QmrDevState *>(state);
+    if (qmr_step_c(*st, v[0], st->iter + 1)) st->stop_seq = seq + 1;
   } else if (epi == EPI_BICG_A) {                  // v[0] = c.v                 src/bicgstab.jl:223
     BicgDevState *st = static_cast<BicgDevState *>(state);
     st->alpha = st->rho / v[0];
