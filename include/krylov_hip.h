@@ -630,6 +630,44 @@ int khip_qmr_last_path(khip_qmr_workspace *ws);
 double           *khip_qmr_vector(khip_qmr_workspace *ws, const char *name);
 size_t            khip_qmr_workspace_bytes(khip_qmr_workspace *ws);   /* 9n doubles without M, N and warm start */
 
+/* ---- bilqr! (src/bilqr.jl:116-484), real Float64: the adjoint pair A x = b and Aᴴ y = c from ONE two-sided Lanczos process, the
+ * BiLQ iterate (with the BiCG transfer) for the primal system and the QMR iterate for the dual one.  There is no M or N.
+ * BilqrWorkspace (src/krylov_workspaces.jl): uₖ₋₁, uₖ, q, vₖ₋₁, vₖ, p, x, y, d̅, wₖ₋₃, wₖ₋₂ ("u_prev", "u", "q", "v_prev", "v", "p", "x",
+ * "y", "dbar", "w_prev3", "w_prev2"); Δx and Δy ("dx", "dy") stay empty until a warm start.  The fused loops rotate the roles of
+ * (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and (wₖ₋₃, wₖ₋₂) instead of copying or swapping, and khip_bilqr_vector returns a name's pointer by its current
+ * role: after k iterations every name holds what the reference's variable of that name holds, in whichever buffer. */
+typedef struct khip_bilqr_workspace khip_bilqr_workspace;
+typedef struct {
+  int transfer_to_bicg;         /* transfer from the BiLQ point to the BiCG point when it exists (default 1) */
+} khip_bilqr_params;
+khip_bilqr_params khip_bilqr_default_params(void);   /* transfer_to_bicg = 1 */
+int khip_bilqr_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_bilqr_workspace **out);   /* m != n: KHIP_ERR_INVALID "Systems must be square" */
+/* BilqrWorkspace on the caller's eleven vectors; every pointer must be distinct.  adopt_vector names: "dx" and "dy" (Δx, Δy:
+ * warm_start! fills them on the caller's side and hands them over, then khip_bilqr_warm_start(ws, dx, dy) only sets the flag) */
+int khip_bilqr_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *u_prev, double *u, double *q, double *v_prev, double *v,
+                               double *p, double *x, double *y, double *dbar, double *w_prev3, double *w_prev2,
+                               khip_bilqr_workspace **out);
+int khip_bilqr_workspace_adopt_vector(khip_bilqr_workspace *ws, const char *name, double *ptr);
+int khip_bilqr_workspace_destroy(khip_bilqr_workspace *ws);
+int khip_bilqr_warm_start(khip_bilqr_workspace *ws, const double *x0, const double *y0);   /* both are required */
+/* bilqr!(ws, A, b, c; transfer_to_bicg, atol, rtol, itmax, timemax, verbose, history, callback).  At = A' and c are required (NULL:
+ * KHIP_ERR_INVALID).  Loops (khip_bilqr_last_path): 2 = device-resident (A and At CSR handles, no callback, verbose = 0), 1 =
+ * host-driven on the same kernels (same bits as 2), 0 = one launch per primitive (options.fused = 0). */
+int khip_bilqr_solve(khip_bilqr_workspace *ws, const khip_operator *A, const khip_operator *At, const double *b, const double *c,
+                     const khip_options *opts, const khip_bilqr_params *params);
+double           *khip_bilqr_solution_x(khip_bilqr_workspace *ws);
+double           *khip_bilqr_solution_y(khip_bilqr_workspace *ws);
+/* AdjointStats does not fit khip_stats: there solved = solved_primal && solved_dual, residuals = the primal history and status = the
+ * first bytes of the full status, cut at a UTF-8 character boundary (four of the reference's strings are longer than status[96]) */
+const khip_stats *khip_bilqr_stats(khip_bilqr_workspace *ws);
+/* the whole AdjointStats; the arrays and the string belong to the workspace until its next solve; any out pointer may be NULL */
+int khip_bilqr_adjoint_stats(khip_bilqr_workspace *ws, int *solved_primal, int *solved_dual, const double **residuals_primal,
+                             int *nprimal, const double **residuals_dual, int *ndual, const char **status);
+int khip_bilqr_last_path(khip_bilqr_workspace *ws);
+/* named work vectors: "u_prev", "u", "q", "v_prev", "v", "p", "x", "y", "dbar", "w_prev3", "w_prev2", "dx", "dy" (NULL while not allocated) */
+double           *khip_bilqr_vector(khip_bilqr_workspace *ws, const char *name);
+size_t            khip_bilqr_workspace_bytes(khip_bilqr_workspace *ws);   /* 11n doubles without warm start */
+
 int khip_gmres_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, int memory, khip_gmres_workspace **out);
 /* GmresWorkspace on the caller's x, w and basis V_host[0 .. memory) (device pointers in a HOST array; `V::Vector{S}`,
  * src/krylov_workspaces.jl:2857-2873).  adopt_vector names: "x", "w", "p", "q", "dx".  adopt_basis replaces the whole list

@@ -19,6 +19,10 @@ extern "C" {
  * (test/test_aux.jl:3-117) are checked against the copies the product runs: sym_givens (src/krylov_utils.jl:21-51),
  * roots_quadratic (:110-152), to_boundary with M = I (:375-402; x, d device vectors, the dots run on the device). */
 int khip_test_sym_givens(double a, double b, double *c, double *s, double *rho);
+/* bilqr!'s termination status (src/bilqr.jl:451-469) for the flags of `mask` -- bits: 0 solved_lq_tol, 1 solved_lq_mach, 2 solved_cg_tol,
+ * 3 solved_cg_mach, 4 solved_qr_tol, 5 solved_qr_mach, 6 tired, 7 breakdown, 8 user-requested exit, 9 overtimed -- whole (*full) and as
+ * khip_stats.status holds it (cut96: char[96], cut at a UTF-8 character boundary).  Host only. */
+int khip_test_bilqr_status(int mask, char *cut96, const char **full);
 int khip_test_roots_quadratic(double q2, double q1, double q0, int nitref, double *root1, double *root2);
 int khip_test_to_boundary(khip_ctx *ctx, int64_t n, const double *x, const double *d, double radius, int flip,
                           double *sigma1, double *sigma2);

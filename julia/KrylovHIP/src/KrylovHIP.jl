@@ -587,6 +587,79 @@ function Krylov.qmr!(ws::QmrWs, A::HIPCsr, b::HIPVector; c::HIPVector = b, M = I
   return ws
 end
 
+# ------------------------------------------------------------------------------------------------ bilqr!  (src/bilqr.jl:116-484)
+struct BilqrParams                  # khip_bilqr_params: transfer_to_bicg
+  transfer_to_bicg::Cint
+end
+const BilqrWs = BilqrWorkspace{Float64,Float64,HIPVector}
+function bilqr_handle(ws::BilqrWs)
+  get!(HANDLES, ws) do
+    r = Ref{Ptr{Cvoid}}()
+    ck(ccall((:khip_bilqr_workspace_adopt, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                                                       Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                                                       Ptr{Cdouble}, Ref{Ptr{Cvoid}}),
+             CTX[].h, ws.m, ws.n, ws.uₖ₋₁.ptr, ws.uₖ.ptr, ws.q.ptr, ws.vₖ₋₁.ptr, ws.vₖ.ptr, ws.p.ptr, ws.x.ptr, ws.y.ptr, ws.d̅.ptr, ws.wₖ₋₃.ptr, ws.wₖ₋₂.ptr, r))
+    h = r[]
+    finalizer(_ -> ccall((:khip_bilqr_workspace_destroy, lib), Cint, (Ptr{Cvoid},), h), ws)
+    h
+  end
+end
+bilqr_adopt(h, name, v::HIPVector) = ck(ccall((:khip_bilqr_workspace_adopt_vector, lib), Cint, (Ptr{Cvoid}, Cstring, Ptr{Cdouble}), h, name, dptr(v)))
+# AdjointStats from khip_bilqr_adjoint_stats: both histories, both flags and the FULL status (khip_stats.status[96] cannot hold four
+# of the reference's strings); niter and timer from khip_stats
+function fill_adjoint_stats!(stats::Krylov.AdjointStats{Float64}, h::Ptr{Cvoid}, sp::Ptr{Stats}, history::Bool)
+  st = unsafe_load(sp)
+  sprim, sdual, np, nd = Ref{Cint}(0), Ref{Cint}(0), Ref{Cint}(0), Ref{Cint}(0)
+  rp, rd, status = Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL)
+  ck(ccall((:khip_bilqr_adjoint_stats, lib), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cint}, Ref{Ptr{Cvoid}}, Ref{Cint}, Ref{Ptr{Cvoid}},
+                                                    Ref{Cint}, Ref{Ptr{Cvoid}}), h, sprim, sdual, rp, np, rd, nd, status))
+  Krylov.reset!(stats)
+  history && np[] > 0 && append!(stats.residuals_primal, unsafe_wrap(Array, Ptr{Float64}(rp[]), Int(np[])))
+  history && nd[] > 0 && append!(stats.residuals_dual, unsafe_wrap(Array, Ptr{Float64}(rd[]), Int(nd[])))
+  stats.niter = st.niter;  stats.solved_primal = sprim[] != 0;  stats.solved_dual = sdual[] != 0
+  stats.timer = st.timer;  stats.status = unsafe_string(Ptr{UInt8}(status[]))
+  return st
+end
+# a user's callback reads both histories: they are brought over before it runs (the shared trampoline knows stats.residuals only)
+bilqr_callback(cb, h, sp, history) = cb === nothing ? nothing : (w -> (fill_adjoint_stats!(w.stats, h, sp, history); cb(w)))
+
+# The adjoint is `A'`, built once per matrix and cached in `A.adj`.  bilqr! has no M or N.  After the solve only ws.x, ws.y and
+# ws.stats are defined: the library rotates the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and (wₖ₋₃, wₖ₋₂) among the adopted vectors.
+function Krylov.bilqr!(ws::BilqrWs, A::HIPCsr, b::HIPVector, c::HIPVector; transfer_to_bicg::Bool = true,
+                       atol::Float64 = √eps(Float64), rtol::Float64 = √eps(Float64), itmax::Int = 0, timemax::Float64 = Inf,
+                       verbose::Int = 0, history::Bool = false, callback = nothing, iostream::IO = Krylov.kstdout, fused::Int = 2)
+  if !native_log(verbose, iostream)
+    GENERIC_SOLVES[] += 1
+    return invoke(Krylov.bilqr!, Tuple{BilqrWs,Any,AbstractVector{Float64},AbstractVector{Float64}}, ws, A, b, c; transfer_to_bicg, atol, rtol,
+                  itmax, timemax, verbose, history, callback = callback === nothing ? (w -> false) : callback, iostream)
+  end
+  m, n = size(A)                                                                            # :122-126
+  (m == ws.m && n == ws.n) || error("(workspace.m, workspace.n) = ($(ws.m), $(ws.n)) is inconsistent with size(A) = ($m, $n)")
+  m == n || error("Systems must be square")
+  length(b) == m || error("Inconsistent problem size")
+  length(c) == n || error("Inconsistent problem size")
+  At = A'
+  h = bilqr_handle(ws)
+  for (name, v) in (("dx", ws.Δx), ("dy", ws.Δy))
+    bilqr_adopt(h, name, v)
+  end
+  ws.warm_start && ck(ccall((:khip_bilqr_warm_start, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), h, ws.Δx.ptr, ws.Δy.ptr))
+  sp = ccall((:khip_bilqr_stats, lib), Ptr{Stats}, (Ptr{Cvoid},), h)
+  cbf, cbd, box = callback_args(bilqr_callback(user_callback(callback), h, sp, history), ws, sp, false)
+  opts = Ref(Options(; atol, rtol, itmax, timemax, history, fused, verbose, log_fd = logfd(iostream), callback = cbf, callback_data = cbd))
+  prm = Ref(BilqrParams(transfer_to_bicg))
+  opA = Ref(Operator(A));  opAt = Ref(Operator(At))
+  rc = GC.@preserve ws A At b c opts prm opA opAt box ccall((:khip_bilqr_solve, lib), Cint,
+         (Ptr{Cvoid}, Ref{Operator}, Ref{Operator}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Options}, Ptr{Cvoid}),
+         h, opA, opAt, b.ptr, c.ptr, opts, prm)
+  st = fill_adjoint_stats!(ws.stats, h, sp, history)
+  NATIVE_SOLVES[] += 1;  LAST_PATH[] = ccall((:khip_bilqr_last_path, lib), Cint, (Ptr{Cvoid},), h)
+  ws.warm_start = false
+  finish_callback(box)
+  rc == 0 || failed(st)
+  return ws
+end
+
 # ------------------------------------------------------------------------------------------------ cg_lanczos_shift!  (src/cg_lanczos_shift.jl:107-284)
 struct LanczosShiftParams           # khip_cg_lanczos_shift_params: shifts (host array), nshifts, check_curvature
   shifts::Ptr{Cdouble}; nshifts::Cint; check_curvature::Cint

@@ -245,6 +245,9 @@ end
     x, stats = native(2) do; qmr(U_gpu, S(bu_cpu)); end              # the same process, the quasi-minimal residual iterate
     @test norm(bu_cpu - U_cpu * Vector(x)) ≤ 1e-5 * norm(bu_cpu)
     @test U_gpu' === At
+    x, y, stats = native(2) do; bilqr(U_gpu, S(bu_cpu), S(bu_cpu)); end   # one process for A x = b and A' y = c
+    @test norm(bu_cpu - U_cpu * Vector(x)) ≤ 1e-5 * norm(bu_cpu) && norm(bu_cpu - U_cpu' * Vector(y)) ≤ 1e-5 * norm(bu_cpu)
+    @test U_gpu' === At
   end
 
   @testset "solver -- $FC" begin                                     # test/gpu/gpu.jl test_solver
@@ -259,3 +262,5 @@ end
     @test Krylov.ktypeof(dv) <: S
   end
 end
+
+include("bilqr.jl")                                                  # bilqr! against the generic method, its breakdowns and statuses

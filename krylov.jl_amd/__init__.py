@@ -70,6 +70,10 @@ class CQmrParams(C.Structure):
     _fields_ = [("Mt", C.POINTER(COperator)), ("Nt", C.POINTER(COperator))]
 
 
+class CBilqrParams(C.Structure):
+    _fields_ = [("transfer_to_bicg", C.c_int)]
+
+
 class CStats(C.Structure):
     _fields_ = [("niter", C.c_int), ("solved", C.c_int), ("inconsistent", C.c_int), ("indefinite", C.c_int),
                 ("npcCount", C.c_int), ("timer", C.c_double), ("status", C.c_char * 96),
@@ -277,6 +281,22 @@ SIGNATURES = {
     "khip_qmr_last_path": (_int, [_vp]),
     "khip_qmr_vector": (_vp, [_vp, C.c_char_p]),
     "khip_qmr_workspace_bytes": (_sz, [_vp]),
+    "khip_bilqr_default_params": (CBilqrParams, []),
+    "khip_bilqr_workspace_create": (_int, [_vp, _i64, _i64, c_void_pp]),
+    "khip_bilqr_workspace_adopt": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_void_pp]),
+    "khip_bilqr_workspace_adopt_vector": (_int, [_vp, C.c_char_p, _vp]),
+    "khip_bilqr_workspace_destroy": (_int, [_vp]),
+    "khip_bilqr_warm_start": (_int, [_vp, _vp, _vp]),
+    "khip_bilqr_solve": (_int, [_vp, C.POINTER(COperator), C.POINTER(COperator), _vp, _vp, C.POINTER(COptions),
+                                C.POINTER(CBilqrParams)]),
+    "khip_bilqr_solution_x": (_vp, [_vp]),
+    "khip_bilqr_solution_y": (_vp, [_vp]),
+    "khip_bilqr_stats": (C.POINTER(CStats), [_vp]),
+    "khip_bilqr_adjoint_stats": (_int, [_vp, C.POINTER(_int), C.POINTER(_int), C.POINTER(c_double_p), C.POINTER(_int),
+                                        C.POINTER(c_double_p), C.POINTER(_int), C.POINTER(C.c_char_p)]),
+    "khip_bilqr_last_path": (_int, [_vp]),
+    "khip_bilqr_vector": (_vp, [_vp, C.c_char_p]),
+    "khip_bilqr_workspace_bytes": (_sz, [_vp]),
     "khip_block_gmres_workspace_bytes": (_sz, [_vp, C.POINTER(C.c_size_t)]),
     "khip_test_gen_banded_random_host": (_int, [_i64, _int, _int, C.c_uint64, _int, _int, _i64, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_double_p, C.POINTER(_i64)]),
     "khip_test_small_dense": (_int, [_int, _int, _int, _int, c_double_p, c_double_p, c_double_p]),
@@ -291,6 +311,7 @@ SIGNATURES = {
     "khip_test_set_halo_self": (_int, [_vp, _int]),
     "khip_test_vec_plan": (_int, [_i64, C.POINTER(C.c_uint64), _int, _int, _int, _int, _int, _int, C.POINTER(_i64)]),
     "khip_test_sym_givens": (_int, [C.c_double, C.c_double, c_double_p, c_double_p, c_double_p]),
+    "khip_test_bilqr_status": (_int, [_int, C.c_char_p, C.POINTER(C.c_char_p)]),
     "khip_test_roots_quadratic": (_int, [C.c_double, C.c_double, C.c_double, _int, c_double_p, c_double_p]),
     "khip_test_to_boundary": (_int, [_vp, _i64, _vp, _vp, C.c_double, _int, c_double_p, c_double_p]),
     "khip_block_gmres_workspace_create": (_int, [_vp, _i64, _i64, _int, _int, c_void_pp]),
@@ -1055,6 +1076,29 @@ class SimpleStats:
         return f"SimpleStats(niter={self.niter}, solved={self.solved}, status={self.status!r})"
 
 
+class AdjointStats:
+    """AdjointStats (src/krylov_stats.jl): one history and one flag per system; `status` is the reference's full string, which
+    khip_stats.status cannot always hold (khip_bilqr_adjoint_stats).  `solved` and `residuals` are the C struct's summary: both
+    sides solved, the primal history."""
+
+    def __init__(self, st: CStats, solved_primal, solved_dual, residuals_primal, residuals_dual, status):
+        self.niter = st.niter
+        self.solved_primal = bool(solved_primal)
+        self.solved_dual = bool(solved_dual)
+        self.solved = bool(st.solved)
+        self.residuals_primal = residuals_primal
+        self.residuals_dual = residuals_dual
+        self.residuals = residuals_primal
+        self.timer = st.timer
+        self.allocation_timer = st.allocation_timer
+        self.status = status
+        self.error = st.error.decode("utf-8")
+
+    def __repr__(self):
+        return (f"AdjointStats(niter={self.niter}, solved_primal={self.solved_primal}, solved_dual={self.solved_dual}, "
+                f"status={self.status!r})")
+
+
 _ILU_PATH_FIELDS = ("fast", "wide", "packed", "packed_pad0", "long_row_blocks", "long_face_blocks", "max_faces", "max_row",
                     "max_levels", "max_width", "rows_cap", "lds", "workgroups", "blocks")
 
@@ -1578,6 +1622,72 @@ class QmrWorkspace(_Workspace):
         return DeviceVector(self.ctx, self.n, ptr=p, owner=self) if p else None
 
 
+class BilqrWorkspace(_Workspace):
+    """BilqrWorkspace(m, n, S) (src/krylov_workspaces.jl:1818-1836): uₖ₋₁, uₖ, q, vₖ₋₁, vₖ, p, x, y, d̅, wₖ₋₃, wₖ₋₂; Δx and Δy stay empty
+    until a warm start.  The fused loops rotate the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and (wₖ₋₃, wₖ₋₂), and `vector(name)` follows the role
+    (khip_bilqr_vector): after k iterations a name holds what the reference's variable of that name holds."""
+    _prefix = "bilqr"
+    VECTORS = ("u_prev", "u", "q", "v_prev", "v", "p", "x", "y", "dbar", "w_prev3", "w_prev2")
+
+    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
+        self.ctx, self.m, self.n = ctx, m, n
+        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
+        self._h = C.c_void_p()
+        if self.adopted:
+            t0 = time.perf_counter()
+            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(n) for k in self.VECTORS}
+            self._alloc_s = time.perf_counter() - t0
+            _ck(lib().khip_bilqr_workspace_adopt(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
+        else:
+            _ck(lib().khip_bilqr_workspace_create(ctx._h, m, n, C.byref(self._h)))
+
+    @property
+    def x(self) -> DeviceVector:
+        if self.adopted:
+            return self._vec["x"]
+        return DeviceVector(self.ctx, self.n, ptr=lib().khip_bilqr_solution_x(self._h), owner=self)
+
+    @property
+    def y(self) -> DeviceVector:
+        if self.adopted:
+            return self._vec["y"]
+        return DeviceVector(self.ctx, self.n, ptr=lib().khip_bilqr_solution_y(self._h), owner=self)
+
+    def vector(self, name: str):
+        if name in ("x", "y"):
+            return getattr(self, name)
+        p = lib().khip_bilqr_vector(self._h, name.encode())
+        return DeviceVector(self.ctx, self.n, ptr=p, owner=self) if p else None
+
+    @property
+    def stats(self) -> AdjointStats:
+        sp, sd, np_, nd = _int(), _int(), _int(), _int()
+        rp, rd, status = c_double_p(), c_double_p(), C.c_char_p()
+        _ck(lib().khip_bilqr_adjoint_stats(self._h, C.byref(sp), C.byref(sd), C.byref(rp), C.byref(np_), C.byref(rd), C.byref(nd),
+                                           C.byref(status)))
+        st = AdjointStats(lib().khip_bilqr_stats(self._h).contents, sp.value, sd.value,
+                          np.array([rp[i] for i in range(np_.value)]), np.array([rd[i] for i in range(nd.value)]),
+                          (status.value or b"").decode("utf-8"))
+        if self.adopted:
+            st.allocation_timer += self._alloc_s
+        st.timer += getattr(self, "_timer_extra", 0.0)
+        return st
+
+    def warm_start_(self, x0: DeviceVector, y0: DeviceVector | None = None):
+        """warm_start!(workspace, x0, y0) (src/workspace_accessors.jl): Δx and Δy are allocated on first need; both are required."""
+        if y0 is None or x0 is None:
+            raise KhipError(-1, "bilqr: warm_start needs x0 and y0")
+        if self.adopted:
+            self._allocate_if(True, "dx")
+            self._allocate_if(True, "dy")
+            kcopy_(self.n, self._vec["dx"], x0)
+            kcopy_(self.n, self._vec["dy"], y0)
+            _ck(lib().khip_bilqr_warm_start(self._h, self._vec["dx"].ptr, self._vec["dy"].ptr))     # same pointers: only the flag
+        else:
+            _ck(lib().khip_bilqr_warm_start(self._h, _p(x0), _p(y0)))
+        return self
+
+
 def _finish(ws, rc):
     ws._timer_extra = 0.0          # an entry point that did work of its own before the solve adds it afterwards
     if rc != 0:
@@ -1732,6 +1842,25 @@ def qmr_(ws: QmrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, M=
     return _finish(ws, rc)
 
 
+def bilqr_(ws: BilqrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, transfer_to_bicg=True, **kw):
+    """bilqr!(workspace, A, b, c; transfer_to_bicg, atol, rtol, itmax, timemax, verbose, history, callback, iostream)
+    (src/bilqr.jl:116-484): x of A x = b by BiLQ and y of A' y = c by QMR from one two-sided Lanczos process.  At: the adjoint of A
+    (default: A.transpose(), cached on A).  Returns the workspace."""
+    keep = []
+    if c is None:
+        raise KhipError(-1, "bilqr: c (the right-hand side of the dual system) is required")
+    if len(b) != ws.n or len(c) != ws.n:
+        raise KhipError(-1, "Inconsistent problem size")
+    if At is None:
+        At = _adjoint_of(A, solver="bilqr")
+    opts = _make_options(keep=keep, ws=ws, **kw)
+    prm = lib().khip_bilqr_default_params()
+    prm.transfer_to_bicg = int(bool(transfer_to_bicg))
+    rc = lib().khip_bilqr_solve(ws._h, _make_operator(ws.ctx, A, ws.n, keep), _make_operator(ws.ctx, At, ws.n, keep), _p(b), _p(c),
+                                C.byref(opts), C.byref(prm))
+    return _finish(ws, rc)
+
+
 def _local_rows(A):
     return A.m if isinstance(A, CsrMatrix) else None
 
@@ -1761,6 +1890,8 @@ FORWARDED_DEFAULTS = {
                  timemax=math.inf, verbose=0, history=False, callback=default_callback, iostream=None),
     "qmr": dict(c=None, M=None, N=None, ldiv=False, atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0, timemax=math.inf, verbose=0,
                 history=False, callback=default_callback, iostream=None),
+    "bilqr": dict(transfer_to_bicg=True, atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0, timemax=math.inf, verbose=0, history=False,
+                  callback=default_callback, iostream=None),
 }
 WORKSPACE_KWARGS = {"gmres": dict(memory=20), "block_gmres": dict(memory=5)}      # kwargs_workspace_gmres, _block_gmres
 # kwargs_workspace_minres (src/minres.jl:159): kept apart from WORKSPACE_KWARGS, whose contents tests/test_abi.py pins
@@ -1783,7 +1914,7 @@ def krylov_workspace(method: str, *args, ctx: Context | None = None, **kw):
     """krylov_workspace(Val(method), m, n, S; memory) / (Val(method), A, b; memory) (src/interface.jl:117-141, 237-244)."""
     cls = {"cg": CgWorkspace, "gmres": GmresWorkspace, "bicgstab": BicgstabWorkspace, "block_gmres": BlockGmresWorkspace,
            "minres": MinresWorkspace, "cg_lanczos_shift": CgLanczosShiftWorkspace, "bilq": BilqWorkspace,
-           "qmr": QmrWorkspace}[method]
+           "qmr": QmrWorkspace, "bilqr": BilqrWorkspace}[method]
     if method == "cg_lanczos_shift":                                            # (A, b, nshifts) / (m, n, nshifts)
         if isinstance(args[1], DeviceVector):
             A, b, nshifts = args
@@ -1884,6 +2015,22 @@ def bilq(A, b: DeviceVector, x0=None, **kw):
 def qmr(A, b: DeviceVector, x0=None, **kw):
     """Out-of-place qmr(A, b[, x0]; kwargs...) -> (x, stats, workspace) (src/qmr.jl:124-132); A' is taken once and kept on A."""
     return krylov_solve("qmr", A, b, x0, **kw)
+
+
+def bilqr(A, b: DeviceVector, c: DeviceVector, x0=None, y0=None, **kw):
+    """Out-of-place bilqr(A, b, c[, x0, y0]; kwargs...) -> (x, y, stats, workspace) (src/bilqr.jl:16-26); A' is taken once and kept
+    on A.  The workspace's creation and the warm start are charged to `timemax` and `stats.timer`, as krylov_solve does."""
+    wkw = {k: kw.pop(k) for k in list(kw) if k in ("adopt", "vectors")}
+    t0 = time.perf_counter()
+    ws = BilqrWorkspace(b.ctx, len(b), len(b), **wkw)
+    if x0 is not None or y0 is not None:
+        ws.warm_start_(x0, y0)
+    elapsed = time.perf_counter() - t0
+    full = _forward("bilqr", kw)
+    full["timemax"] = full["timemax"] - elapsed
+    bilqr_(ws, A, b, c, **full)
+    ws._timer_extra = elapsed
+    return ws.x, ws.y, ws.stats, ws
 
 
 def cg_lanczos_shift(A, b: DeviceVector, shifts, **kw):
@@ -2339,4 +2486,5 @@ def block_gmres(A, B, X0=None, ctx=None, **kw):
 _INPLACE.update({CgWorkspace: ("cg", cg_), GmresWorkspace: ("gmres", gmres_), BicgstabWorkspace: ("bicgstab", bicgstab_),
                  BlockGmresWorkspace: ("block_gmres", block_gmres_), MinresWorkspace: ("minres", minres_), BilqWorkspace: ("bilq", bilq_),
                  QmrWorkspace: ("qmr", qmr_),
+                 BilqrWorkspace: ("bilqr", bilqr_),
                  CgLanczosShiftWorkspace: ("cg_lanczos_shift", cg_lanczos_shift_)})

@@ -16,7 +16,8 @@ namespace khip {
 
 enum Epilogue { EPI_NONE = 0, EPI_CG_STEP1 = 1, EPI_CG_STEP2 = 2, EPI_BICG_A = 3, EPI_BICG_B = 4, EPI_BICG_C = 5, EPI_CGCG = 6,
                EPI_MINRES_A = 7, EPI_MINRES_B = 8, EPI_MINRES_C = 9, EPI_LZSHIFT_A = 10, EPI_LZSHIFT_B = 11,
-               EPI_BILQ_A = 12, EPI_BILQ_B = 13, EPI_BILQ_C = 14, EPI_QMR_A = 15, EPI_QMR_B = 16, EPI_QMR_C = 17 };
+               EPI_BILQ_A = 12, EPI_BILQ_B = 13, EPI_BILQ_C = 14, EPI_QMR_A = 15, EPI_QMR_B = 16, EPI_QMR_C = 17,
+               EPI_BILQR_A = 18, EPI_BILQR_B = 19, EPI_BILQR_C = 20 };
 
 struct CgDevState {
   double gamma;        // r.z of the current iterate              (src/cg.jl:162, 257)
@@ -464,6 +465,153 @@ __host__ __device__ inline bool qmr_step_c(QmrDevState &s, double vv_next, long 
   return s.solved || s.breakdown;
 }
 
+// bilqr! (src/bilqr.jl:116-484), real Float64: ONE two-sided Lanczos process that advances the BiLQ iterate of A x = b (with the
+// BiCG transfer) and the QMR iterate of Aᴴ y = c.  As for bilq! and qmr!: the same three steps run on the host (loops 0 and 1) and as
+// the epilogues of the three reductions of an iteration (device-resident loop), so loops 1 and 2 produce the same bits.  The primal
+// block is frozen once solved_primal is set, the dual block once solved_dual is set; the LQ factorisation and the shifts go on.
+struct BilqrDevState : BiLanczosCoef {
+  // coefficients the vector kernels read (γₖ, βₖ, αₖ: BiLanczosCoef)
+  double beta_next, gamma_next;  // βₖ₊₁, γₖ₊₁: the divisors of P3               (:239-240, :416-417)
+  double pq;                     // pᴴq                                          (:238)
+  double zc, zs, neg_c, sn;      // ζₖ₋₁cₖ, ζₖ₋₁sₖ, -cₖ, sₖ: the x and d̅ updates (:305-310)
+  double neg_eps3, neg_lambda2;  // -ϵₖ₋₃, -λₖ₋₂: kscal! and the second kaxpy! of wₖ₋₁ (:371, :376, :379)
+  double delta, inv_delta;       // δₖ₋₁: kdivcopy!(w₁, u₁, δ₁) (:365); one(T) / δₖ₋₁: kdiv! = kscal!(one(T) / δₖ₋₁) (:372, :380)
+  double psi;                    // ψₖ₋₁: t = t + ψₖ₋₁ wₖ₋₁                       (:391)
+  // constants of the solve
+  double bNorm, eps_L, eps_Q;    // ‖r₀‖, εL = atol + rtol ‖r₀‖, εQ = atol + rtol ‖s₀‖ (:156, :167-168)
+  // recurrences
+  double cs, cs_prev, sn_prev;   // cₖ, cₖ₋₁, sₖ₋₁
+  double lambda, epsilon;        // λₖ₋₁, ϵₖ₋₂
+  double lambda2, eps3;          // λₖ₋₂, ϵₖ₋₃
+  double dbar, dbar_prev;        // δbarₖ, δbarₖ₋₁
+  double zeta_m1, zeta_m2, zbar; // ζₖ₋₁, ζₖ₋₂, ζbarₖ
+  double eta;                    // ηₖ
+  double norm_v;                 // ‖vₖ‖
+  double psibar, psibar_prev;    // ψbarₖ, ψbarₖ₋₁
+  double tau;                    // τₖ
+  double uu;                     // ‖uₖ‖², carried from the previous iteration's P3 (‖u₁‖² from the set-up) to :398
+  double rNorm_lq, rNorm_cg, sNorm;
+  long long stop_seq, iter, hist_base, hist_cap;
+  long long nhist_p, nhist_d;    // the last iteration that pushed to the primal / dual history: each side stops when it is solved
+  double *hist_p, *hist_d;       // device history windows (null: no history)
+  int transfer_to_bicg, breakdown;
+  int solved_lq, solved_cg, solved_primal, solved_dual;
+  int solved_lq_tol, solved_lq_mach, solved_cg_tol, solved_cg_mach, solved_qr_tol, solved_qr_mach;
+};
+
+// after αₖ = ⟨uₖ, q⟩ (:233)
+__host__ __device__ inline void bilqr_step_a(BilqrDevState &s, double uq) { s.alpha = uq; }
+
+// after pᴴq = ⟨p, q⟩: βₖ₊₁, γₖ₊₁, the LQ update, ζₖ₋₁ and ηₖ of an unsolved primal side, ψₖ₋₁ and ψbarₖ of an unsolved dual side
+// (:238-294, :350-359) and the coefficients P3 reads; k = iter
+__host__ __device__ inline void bilqr_step_b(BilqrDevState &s, double pq, long long k) {
+  s.pq = pq;
+  s.beta_next = sqrt(fabs(pq));
+  s.gamma_next = pq / s.beta_next;
+  if (k == 1) {
+    s.dbar = s.alpha;
+  } else if (k == 2) {
+    sym_givens(s.dbar_prev, s.gamma, s.cs, s.sn, s.delta);
+    s.lambda = s.cs * s.beta + s.sn * s.alpha;
+    s.dbar = s.sn * s.beta - s.cs * s.alpha;
+  } else {
+    sym_givens(s.dbar_prev, s.gamma, s.cs, s.sn, s.delta);
+    s.epsilon = s.sn_prev * s.beta;
+    s.lambda = -s.cs_prev * s.cs * s.beta + s.sn * s.alpha;
+    s.dbar = -s.cs_prev * s.sn * s.beta - s.cs * s.alpha;
+  }
+  if (!s.solved_primal) {
+    if (k == 1) s.eta = s.beta;
+    if (k == 2) {
+      const double eta_prev = s.eta;
+      s.zeta_m1 = eta_prev / s.delta;
+      s.eta = -s.lambda * s.zeta_m1;
+    }
+    if (k >= 3) {
+      s.zeta_m2 = s.zeta_m1;
+      const double eta_prev = s.eta;
+      s.zeta_m1 = eta_prev / s.delta;
+      s.eta = -s.epsilon * s.zeta_m2 - s.lambda * s.zeta_m1;
+    }
+    s.zc = s.zeta_m1 * s.cs;
+    s.zs = s.zeta_m1 * s.sn;
+    s.neg_c = -s.cs;
+  }
+  if (!s.solved_dual) {
+    if (k == 1) {
+      s.psibar = s.gamma;
+    } else {
+      s.psi = s.cs * s.psibar_prev;
+      s.psibar = s.sn * s.psibar_prev;
+    }
+    s.neg_eps3 = -s.eps3;
+    s.neg_lambda2 = -s.lambda2;
+    s.inv_delta = 1.0 / s.delta;
+  }
+}
+
+// after ⟨vₖ, q⟩, ‖q‖ and ‖uₖ₊₁‖² (:313-347, :394-435): the residual estimates of the sides still unsolved, their history entries, the
+// shifts and the tests; true when the loop stops (tired / overtimed / the callback are the driver's).  βₖ₊₁ = 0 divides as in the
+// reference: the estimates become NaN and no test holds.
+__host__ __device__ inline bool bilqr_step_c(BilqrDevState &s, double vq, double q_norm, double uu_next, long long k) {
+  const double epsM = 2.220446049250313e-16;
+  if (!s.solved_primal) {
+    const double vv_next = vq / s.beta_next;
+    const double norm_next = q_norm / s.beta_next;
+    if (k == 1) {
+      s.rNorm_lq = s.bNorm;
+    } else {
+      const double mu = s.beta * (s.sn_prev * s.zeta_m2 - s.cs_prev * s.cs * s.zeta_m1) + s.alpha * s.sn * s.zeta_m1;
+      const double omega = s.beta_next * s.sn * s.zeta_m1;
+      const double theta = mu * omega * vv_next;
+      s.rNorm_lq = sqrt(mu * mu * (s.norm_v * s.norm_v) + omega * omega * (norm_next * norm_next) + 2 * theta);
+    }
+    if (s.hist_p) {
+      const long long idx = k - 1 - s.hist_base;
+      if (idx >= 0 && idx < s.hist_cap) s.hist_p[idx] = s.rNorm_lq;
+    }
+    s.nhist_p = k;
+    s.norm_v = norm_next;
+    const bool cg_point = s.transfer_to_bicg && (fabs(s.dbar) > epsM);
+    if (cg_point) {
+      s.zbar = s.eta / s.dbar;
+      const double rho = s.beta_next * (s.sn * s.zeta_m1 - s.cs * s.zbar);
+      s.rNorm_cg = fabs(rho) * norm_next;
+    }
+    s.solved_lq_tol = (s.rNorm_lq <= s.eps_L) ? 1 : 0;
+    s.solved_lq_mach = (s.rNorm_lq + 1.0 <= 1.0) ? 1 : 0;
+    s.solved_lq = (s.solved_lq_tol || s.solved_lq_mach) ? 1 : 0;
+    s.solved_cg_tol = (cg_point && s.rNorm_cg <= s.eps_L) ? 1 : 0;
+    s.solved_cg_mach = (cg_point && s.rNorm_cg + 1.0 <= 1.0) ? 1 : 0;
+    s.solved_cg = (s.solved_cg_tol || s.solved_cg_mach) ? 1 : 0;
+    s.solved_primal = (s.solved_lq || s.solved_cg) ? 1 : 0;
+  }
+  if (!s.solved_dual) {
+    s.psibar_prev = s.psibar;
+    s.tau = s.tau + s.uu;
+    s.sNorm = fabs(s.psibar) * sqrt(s.tau);
+    if (s.hist_d) {
+      const long long idx = k - 1 - s.hist_base;
+      if (idx >= 0 && idx < s.hist_cap) s.hist_d[idx] = s.sNorm;
+    }
+    s.nhist_d = k;
+    s.solved_qr_tol = (s.sNorm <= s.eps_Q) ? 1 : 0;
+    s.solved_qr_mach = (s.sNorm + 1.0 <= 1.0) ? 1 : 0;
+    s.solved_dual = (s.solved_qr_tol || s.solved_qr_mach) ? 1 : 0;
+  }
+  s.uu = uu_next;
+  if (k >= 3) s.eps3 = s.epsilon;
+  if (k >= 2) s.lambda2 = s.lambda;
+  s.dbar_prev = s.dbar;
+  s.cs_prev = s.cs;
+  s.sn_prev = s.sn;
+  s.gamma = s.gamma_next;
+  s.beta = s.beta_next;
+  s.breakdown = (!s.solved_lq && !s.solved_cg && s.pq == 0.0) ? 1 : 0;
+  s.iter = k;
+  return (s.solved_primal && s.solved_dual) || s.breakdown;
+}
+
 __device__ __forceinline__ bool seq_skip(const long long *stop_seq, long long seq) {
   return stop_seq != nullptr && seq >= *stop_seq;
 }
@@ -566,6 +714,14 @@ __device__ inline void solver_epilogue(int epi, void *state, const double *v, lo
   } else if (epi == EPI_QMR_C) {                   // v[0] = v_k+1.v_k+1         :350-376
     QmrDevState *st = static_cast<QmrDevState *>(state);
     if (qmr_step_c(*st, v[0], st->iter + 1)) st->stop_seq = seq + 1;
+  } else if (epi == EPI_BILQR_A) {                 // v[0] = u.q                 src/bilqr.jl:233
+    bilqr_step_a(*static_cast<BilqrDevState *>(state), v[0]);
+  } else if (epi == EPI_BILQR_B) {                 // v[0] = p.q                 :238-294, :350-359
+    BilqrDevState *st = static_cast<BilqrDevState *>(state);
+    bilqr_step_b(*st, v[0], st->iter + 1);
+  } else if (epi == EPI_BILQR_C) {                 // v = (v_k.q, q.q, u_k+1.u_k+1, 0)   :313-347, :394-435
+    BilqrDevState *st = static_cast<BilqrDevState *>(state);
+    if (bilqr_step_c(*st, v[0], sqrt(v[1]), v[2], st->iter + 1)) st->stop_seq = seq + 1;
   } else if (epi == EPI_BICG_A) {                  // v[0] = c.v                 src/bicgstab.jl:223
     BicgDevState *st = static_cast<BicgDevState *>(state);
     st->alpha = st->rho / v[0];

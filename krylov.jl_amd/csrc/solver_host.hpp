@@ -157,10 +157,16 @@ void set_history(MinresDevState &s, double *w) {
   s.hist_ar = w ? w + kHistWindowMax : nullptr;
   s.hist_acond = w ? w + 2 * kHistWindowMax : nullptr;
 }
+void set_history(BilqrDevState &s, double *w) {
+  s.hist_p = w;
+  s.hist_d = w ? w + kHistWindowMax : nullptr;
+}
 
-// entries of column c of a history row that belong to a state's history (cg_lanczos_shift!: each shift's history is a prefix)
+// entries of column c of a history row (cg_lanczos_shift!: each shift's history is a prefix) or of stream c (bilqr!: each side's
+// history ends with the iteration that solved it) that belong to a state's history
 template <class S> long long hist_rows(const S &, int) { return std::numeric_limits<long long>::max(); }
 long long hist_rows(const LanczosShiftDevState &s, int c) { return s.nhist[c]; }
+long long hist_rows(const BilqrDevState &s, int c) { return c == 0 ? s.nhist_p : s.nhist_d; }
 
 struct DeviceLoopArgs {
   int64_t itmax;
@@ -236,8 +242,9 @@ struct DeviceLoop {
       for (int s = 0; s < streams; ++s) {
         KHIP_CHECK_HIP(hipMemcpy(win.data(), hist + (size_t)s * kHistWindowMax * width, sizeof(double) * (size_t)cnt * width,
                                  hipMemcpyDeviceToHost));
-        if (!a.columns) {
-          a.drain_to[s]->insert(a.drain_to[s]->end(), win.begin(), win.end());
+        if (!a.columns) {                                         // stream s up to its own last entry (all of cnt but for bilqr!)
+          const long long rows = std::max<long long>(0, std::min<long long>(cnt, hist_rows(st, s) - hist_base));
+          a.drain_to[s]->insert(a.drain_to[s]->end(), win.begin(), win.begin() + rows);
           continue;
         }
         for (size_t c = 0; c < width; ++c) {
