@@ -110,6 +110,17 @@ int khip_test_spmm_last_launch(const khip_ctx *ctx, int64_t *out24);
 int khip_test_vec_plan(int64_t n, const uint64_t *ptrs, int nptrs, int extra_aligned, int u, int nt_min_elems, int compensated,
                        int scalar_path_nt, int64_t *out7);
 
+/* test-only: the three kernels only gmres! reaches (variant = 1 / 2 and the look-ahead), launched the way the solver launches them
+ * (tests/test_gpu_gram_schmidt_exact.py).  V_host: k device pointers in host memory.
+ * khip_test_multi_dot: out_host[i] = V_i . q for i < k, through (k + 3) & ~3 slots of the device scalar ring (multi_dot4_kernel,
+ * four outputs per launch); q may be one of the V_i.
+ * khip_test_multi_axpy_dev: x <- x - sum_j coef[j] V_j in the order j = 0 .. k - 1 (multi_axpy_dev_kernel); the coefficients are
+ * copied into ring slots on the context's stream and the kernel reads them there.  k <= 256.
+ * khip_test_divcopy_dev: y = x / sqrt(sumsq) (divcopy_dev_kernel), sumsq read from a ring slot. */
+int khip_test_multi_dot(khip_ctx *ctx, int64_t n, int k, const double *const *V_host, const double *q, double *out_host);
+int khip_test_multi_axpy_dev(khip_ctx *ctx, int64_t n, int k, const double *coef_host, const double *const *V_host, double *x);
+int khip_test_divcopy_dev(khip_ctx *ctx, int64_t n, double sumsq, const double *x, double *y);
+
 #ifdef __cplusplus
 }
 #endif

@@ -310,6 +310,9 @@ SIGNATURES = {
     "khip_test_spmm_last_launch": (_int, [_vp, C.POINTER(_i64)]),
     "khip_test_set_halo_self": (_int, [_vp, _int]),
     "khip_test_vec_plan": (_int, [_i64, C.POINTER(C.c_uint64), _int, _int, _int, _int, _int, _int, C.POINTER(_i64)]),
+    "khip_test_multi_dot": (_int, [_vp, _i64, _int, c_void_pp, _vp, c_double_p]),
+    "khip_test_multi_axpy_dev": (_int, [_vp, _i64, _int, c_double_p, c_void_pp, _vp]),
+    "khip_test_divcopy_dev": (_int, [_vp, _i64, C.c_double, _vp, _vp]),
     "khip_test_sym_givens": (_int, [C.c_double, C.c_double, c_double_p, c_double_p, c_double_p]),
     "khip_test_bilqr_status": (_int, [_int, C.c_char_p, C.POINTER(C.c_char_p)]),
     "khip_test_roots_quadratic": (_int, [C.c_double, C.c_double, C.c_double, _int, c_double_p, c_double_p]),
@@ -776,6 +779,33 @@ def multi_axpy_(n, y, V, x):
     coef = (C.c_double * max(k, 1))(*[float(c) for c in y])
     _ck(lib().khip_multi_axpy(x.ctx._h, n, k, coef, ptrs, _p(x)))
     return x
+
+
+def test_multi_dot(n, V, q):
+    """TEST-ONLY (khip_test_multi_dot): [V_i . q] through multi_dot4_kernel and the device scalar ring, as gmres! variant = 1 does."""
+    k = len(V)
+    ptrs = (C.c_void_p * max(k, 1))(*[_p(v) for v in V])
+    out = (C.c_double * max(k, 1))()
+    _ck(lib().khip_test_multi_dot(q.ctx._h, n, k, ptrs, _p(q), out))
+    return [out[i] for i in range(k)]
+
+
+def test_multi_axpy_dev_(n, coef, V, x):
+    """TEST-ONLY (khip_test_multi_axpy_dev): x <- x - sum_j coef[j] V_j with the coefficients read from the device scalar ring."""
+    k = len(V)
+    ptrs = (C.c_void_p * max(k, 1))(*[_p(v) for v in V])
+    c = (C.c_double * max(k, 1))(*[float(t) for t in coef])
+    _ck(lib().khip_test_multi_axpy_dev(x.ctx._h, n, k, c, ptrs, _p(x)))
+    return x
+
+
+def test_divcopy_dev_(n, sumsq, x, y):
+    """TEST-ONLY (khip_test_divcopy_dev): y = x / sqrt(sumsq), sumsq read from the device scalar ring (gmres! look-ahead)."""
+    _ck(lib().khip_test_divcopy_dev(x.ctx._h, n, float(sumsq), _p(x), _p(y)))
+    return y
+
+
+test_multi_dot.__test__ = test_multi_axpy_dev_.__test__ = test_divcopy_dev_.__test__ = False     # not pytest items
 
 
 # --------------------------------------------------------------------------- CSR operator

@@ -799,4 +799,35 @@ int khip_multi_axpy(khip_ctx *ctx, int64_t n, int k, const double *y_host, const
   return launch_multi_axpy(ctx, n, k, y_host, V_host, x);
 }
 
+// test-only (include/krylov_hip_test.h): the kernels only gmres! reaches, launched as solvers.cpp launches them -- the scalars they
+// read or write live in slots of the device ring taken with take_slots, on the context's stream
+int khip_test_multi_dot(khip_ctx *ctx, int64_t n, int k, const double *const *V_host, const double *q, double *out_host) {
+  KHIP_REQUIRE(ctx && n >= 0 && k >= 0 && (k == 0 || (V_host && out_host)) && (n == 0 || k == 0 || q), "test_multi_dot: bad argument");
+  KHIP_REQUIRE(((k + 3) & ~3) <= kResultSlots, "test_multi_dot: k exceeds the device scalar ring");
+  if (k == 0) return KHIP_OK;
+  const int slot = take_slots(ctx, (k + 3) & ~3);
+  KHIP_TRY(launch_multi_dot(ctx, n, k, V_host, q, slot));
+  return fetch_results(ctx, slot, k, out_host);
+}
+
+int khip_test_multi_axpy_dev(khip_ctx *ctx, int64_t n, int k, const double *coef_host, const double *const *V_host, double *x) {
+  KHIP_REQUIRE(ctx && n >= 0 && k >= 0 && (k == 0 || (coef_host && V_host)) && (n == 0 || x), "test_multi_axpy_dev: bad argument");
+  KHIP_REQUIRE(k <= kResultSlots, "test_multi_axpy_dev: k exceeds the device scalar ring");
+  if (k == 0) return KHIP_OK;
+  const int slot = take_slots(ctx, k);
+  KHIP_CHECK_HIP(hipMemcpyAsync(ctx->results + slot, coef_host, sizeof(double) * (size_t)k, hipMemcpyHostToDevice, ctx->stream));
+  KHIP_TRY(launch_multi_axpy_dev(ctx, n, k, ctx->results + slot, V_host, x));
+  KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));          // coef_host is the caller's: read before this returns
+  return KHIP_OK;
+}
+
+int khip_test_divcopy_dev(khip_ctx *ctx, int64_t n, double sumsq, const double *x, double *y) {
+  KHIP_REQUIRE(ctx && n >= 0 && (n == 0 || (x && y)), "test_divcopy_dev: bad argument");
+  const int slot = take_slots(ctx, 1);
+  KHIP_CHECK_HIP(hipMemcpyAsync(ctx->results + slot, &sumsq, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  KHIP_TRY(launch_divcopy_dev(ctx, n, ctx->results + slot, x, y));
+  KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));          // sumsq is on this frame: read before this returns
+  return KHIP_OK;
+}
+
 }  // extern "C"

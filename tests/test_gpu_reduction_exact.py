@@ -140,22 +140,25 @@ def test_fused_blas1_reductions(K, ctx, parity_log, n):
     assert ok, info
 
 
-@pytest.mark.parametrize("n,k", [(1000, 1), (4099, 4), (100003, 5), (200001, 30)])
-def test_mgs_coefficients_and_norm(K, ctx, parity_log, n, k):
-    """mgs_ chains h_i = V_i . q_i with q_{i+1} = fma(-h_i, V_i, q_i) on the device; the q_i it saw are replayed with kaxpy_
-    (the same fma) and the replay must end on the kernel's own q bit for bit, which pins the operands of every coefficient."""
-    tally = Tally(parity_log, "blas1")
-    rng = np.random.default_rng(k)
+def _mgs_data(n, k, cond, seed):
+    rng = np.random.default_rng(seed)
     q0 = rng.standard_normal(n)
-    V = [er.gen_dot(n, {1: 1e16, 4: 1e8, 5: 1e4, 30: 1e16}[k], rng, "blocks", y=q0)[0]]    # h_0 ill-conditioned
+    V = [er.gen_dot(n, cond, rng, "blocks", y=q0)[0]]                                       # h_0 ill-conditioned
     for i in range(1, k):
         v = rng.standard_normal(n)
         V.append(v / np.linalg.norm(v))
-    dV = [ctx.array(v) for v in V]
-    dq = ctx.array(q0)
+    return q0, V
+
+
+def _mgs_check(K, ctx, tally, n, q0, V, mis=False):
+    """one mgs_ call on fresh device copies, replayed with kaxpy_: every coefficient within the Dot2 bound of the exact dot of
+    the operands it saw, the replay's q equal to the kernel's q bit for bit, the norm within 1 ulp -> (h as returned, q)"""
+    k = len(V)
+    dV = [_dev(ctx, v, mis) for v in V]
+    dq = _dev(ctx, q0, mis)
     h, nrm = K.mgs_(n, dV, dq)
     qf = dq.to_host()
-    rq = ctx.array(q0)
+    rq = _dev(ctx, q0, mis)
     for i in range(k):
         qi = rq.to_host()
         ok, info = tally.dot(f"mgs.h{i}", h[i], V[i], qi, er.absum(V[i], qi) / max(abs(er.exact_dot(V[i], qi)), 1e-300))
@@ -164,6 +167,72 @@ def test_mgs_coefficients_and_norm(K, ctx, parity_log, n, k):
     assert np.array_equal(rq.to_host(), qf)
     en = er.exact_norm(qf)
     assert abs(nrm - en) <= ulp(en), (nrm, en)
+    return h, nrm, qf
+
+
+@pytest.mark.parametrize("n,k", [(1000, 1), (4099, 4), (100003, 5), (200001, 30)])
+def test_mgs_coefficients_and_norm(K, ctx, parity_log, n, k):
+    """mgs_ chains h_i = V_i . q_i with q_{i+1} = fma(-h_i, V_i, q_i) on the device; the q_i it saw are replayed with kaxpy_
+    (the same fma) and the replay must end on the kernel's own q bit for bit, which pins the operands of every coefficient."""
+    tally = Tally(parity_log, "blas1")
+    q0, V = _mgs_data(n, k, {1: 1e16, 4: 1e8, 5: 1e4, 30: 1e16}[k], k)
+    _mgs_check(K, ctx, tally, n, q0, V)
+
+
+@pytest.mark.parametrize("n,k", [(1000, 1), (4099, 4), (513, 5)])
+def test_mgs_on_misaligned_vectors(K, ctx, parity_log, n, k):
+    """q and every V_i at 8 (mod 16): the 8-byte instantiation of reduce_kernel<RED_AXPYDEV>"""
+    tally = Tally(parity_log, "blas1")
+    q0, V = _mgs_data(n, k, {1: 1e16, 4: 1e8, 5: 1e4}[k], 50 + k)
+    _mgs_check(K, ctx, tally, n, q0, V, mis=True)
+
+
+@pytest.mark.parametrize("mgs_keep", [0, 1, 2])
+@pytest.mark.parametrize("red_u", [1, 4])
+@pytest.mark.parametrize("nt", ["default", 1])
+@pytest.mark.parametrize("mis", [False, True])
+def test_mgs_under_every_knob(K, ctx, opts, parity_log, mgs_keep, red_u, nt, mis):
+    """the KEEP instantiation (mgs_keep = 1 with non-temporal accesses on aligned vectors), nothing streamed (2), four accesses
+    per lane (red_u = 4): the same pins at n = 4099, k = 5"""
+    tally = Tally(parity_log, "blas1")
+    opts(mgs_keep=mgs_keep, red_u=red_u)
+    if nt == 1:
+        opts(nt_min_elems=1)
+    q0, V = _mgs_data(4099, 5, 1e8, 77)
+    _mgs_check(K, ctx, tally, 4099, q0, V, mis=mis)
+
+
+def _quiet_tally():
+    return Tally(lambda **kw: None, "blas1")
+
+
+@pytest.mark.parametrize("k", [255, 256])
+@pytest.mark.parametrize("mis", [False, True])
+def test_mgs_at_the_ring_boundary(K, ctx, k, mis):
+    """khip_mgs at n = 257: k + 1 == 256 slots fills the device scalar ring exactly (the cascade), k + 1 == 257 does not fit
+    (the fallback sequence of khip_dot / khip_axpy)"""
+    q0, V = _mgs_data(257, k, 1e8, 300 + k)
+    _mgs_check(K, ctx, _quiet_tally(), 257, q0, V, mis=mis)
+
+
+def test_mgs_wraps_the_ring_between_calls(K, ctx):
+    """three consecutive calls of 101 slots each: wherever the ring stood, one of them starts over at slot 0"""
+    for call in range(3):
+        q0, V = _mgs_data(257, 100, 1e8, 400 + call)
+        _mgs_check(K, ctx, _quiet_tally(), 257, q0, V)
+
+
+def test_mgs_accumulates_into_the_callers_coefficients(K, ctx):
+    """accumulate = 1 (reorthogonalisation) with the ring exactly full: h_out[i] = h_in[i] + h_i in one rounding, q as without"""
+    n, k = 257, 255
+    q0, V = _mgs_data(n, k, 1e8, 500)
+    h, nrm, qf = _mgs_check(K, ctx, _quiet_tally(), n, q0, V)
+    acc = np.random.default_rng(501).standard_normal(k).tolist()
+    dV = [ctx.array(v) for v in V]
+    dq = ctx.array(q0)
+    h2, nrm2 = K.mgs_(n, dV, dq, accumulate_into=acc)
+    assert h2 == [a + b for a, b in zip(acc, h)] and nrm2 == nrm
+    assert np.array_equal(dq.to_host(), qf)
 
 
 # --------------------------------------------------------------------------------------------------------------- SpMV

@@ -424,6 +424,15 @@ def test_gmres_look_ahead_equals_plain_sequence(K, ctx, oracle):
     ref = oracle.gmres(A, bh, memory=10, restart=True, history=True)
     _, st, _ = K.gmres(dA, b, memory=10, restart=True, history=True, fused=2)
     assert st.niter == ref.niter
+    # divcopy_dev_kernel at the odd tail element and on its 8-byte path: adopted vectors carved at element offset 0 / 1
+    from test_gpu_vec_dispatch import _solve
+    for n in (511, 513):
+        for first in (0, 1):
+            for kw in (dict(), dict(restart=True)):
+                (x1,), (h1,), it1, s1 = _solve(K, ctx, "gmres", n, first, 1, **kw)
+                (x2,), (h2,), it2, s2 = _solve(K, ctx, "gmres", n, first, 2, **kw)
+                assert (it2, s2) == (it1, s1) and it1 == 6, (n, first, kw, it1, it2)
+                assert x2.tobytes() == x1.tobytes() and h2.tobytes() == h1.tobytes(), (n, first, kw)
 
 
 def test_gmres_edge_cases(K, ctx, oracle):
