@@ -1600,76 +1600,52 @@ class CgLanczosShiftWorkspace(_Workspace):
         raise KhipError(-4, "cg_lanczos_shift! has no warm start")
 
 
-class BilqWorkspace(_Workspace):
+class _BiLanczosWorkspace(_Workspace):
+    """What the workspaces of bilq!, qmr! and bilqr! share: VECTORS come with the workspace (caller-owned: `vectors=` or fresh ones,
+    handed to khip_*_workspace_adopt in that order; library-owned with adopt=False), the others stay empty until needed.  The
+    fused loops rotate the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and of the solver's w vectors, and `vector(name)` follows the role
+    (khip_*_vector): after k iterations a name holds what the reference's variable of that name holds."""
+    VECTORS = ()
+    SOLUTIONS = ("x",)
+
+    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
+        self.ctx, self.m, self.n = ctx, m, n
+        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
+        self._h = C.c_void_p()
+        if self.adopted:
+            t0 = time.perf_counter()
+            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(n) for k in self.VECTORS}
+            self._alloc_s = time.perf_counter() - t0
+            _ck(self._fn("workspace_adopt")(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
+        else:
+            _ck(self._fn("workspace_create")(ctx._h, m, n, C.byref(self._h)))
+
+    def vector(self, name: str):
+        if name in self.SOLUTIONS:
+            return getattr(self, name)
+        p = self._fn("vector")(self._h, name.encode())
+        return DeviceVector(self.ctx, self.n, ptr=p, owner=self) if p else None
+
+
+class BilqWorkspace(_BiLanczosWorkspace):
     """BilqWorkspace(m, n, S) (src/krylov_workspaces.jl): uₖ₋₁, uₖ, q, vₖ₋₁, vₖ, p, x, d̅; Δx, t, s stay empty until needed.  After a
-    solve only x and the stats are defined: the fused loops rotate the roles of (vₖ₋₁, vₖ) and (uₖ₋₁, uₖ), and `vector(name)` follows
-    the role (khip_bilq_vector)."""
+    solve only x and the stats are defined."""
     _prefix = "bilq"
     VECTORS = ("u_prev", "u", "q", "v_prev", "v", "p", "x", "dbar")
 
-    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
-        self.ctx, self.m, self.n = ctx, m, n
-        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
-        self._h = C.c_void_p()
-        if self.adopted:
-            t0 = time.perf_counter()
-            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(n) for k in self.VECTORS}
-            self._alloc_s = time.perf_counter() - t0
-            _ck(lib().khip_bilq_workspace_adopt(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
-        else:
-            _ck(lib().khip_bilq_workspace_create(ctx._h, m, n, C.byref(self._h)))
 
-    def vector(self, name: str):
-        if name == "x":
-            return self.x
-        p = lib().khip_bilq_vector(self._h, name.encode())
-        return DeviceVector(self.ctx, self.n, ptr=p, owner=self) if p else None
-
-
-class QmrWorkspace(_Workspace):
-    """QmrWorkspace(m, n, S) (src/krylov_workspaces.jl): uₖ₋₁, uₖ, q, vₖ₋₁, vₖ, p, x, wₖ₋₂, wₖ₋₁; Δx, t, s stay empty until needed.  The
-    fused loops rotate the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and (wₖ₋₂, wₖ₋₁), and `vector(name)` follows the role (khip_qmr_vector):
-    after k iterations a name holds what the reference's variable of that name holds."""
+class QmrWorkspace(_BiLanczosWorkspace):
+    """QmrWorkspace(m, n, S) (src/krylov_workspaces.jl): uₖ₋₁, uₖ, q, vₖ₋₁, vₖ, p, x, wₖ₋₂, wₖ₋₁; Δx, t, s stay empty until needed."""
     _prefix = "qmr"
     VECTORS = ("u_prev", "u", "q", "v_prev", "v", "p", "x", "w_prev2", "w_prev")
 
-    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
-        self.ctx, self.m, self.n = ctx, m, n
-        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
-        self._h = C.c_void_p()
-        if self.adopted:
-            t0 = time.perf_counter()
-            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(n) for k in self.VECTORS}
-            self._alloc_s = time.perf_counter() - t0
-            _ck(lib().khip_qmr_workspace_adopt(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
-        else:
-            _ck(lib().khip_qmr_workspace_create(ctx._h, m, n, C.byref(self._h)))
 
-    def vector(self, name: str):
-        if name == "x":
-            return self.x
-        p = lib().khip_qmr_vector(self._h, name.encode())
-        return DeviceVector(self.ctx, self.n, ptr=p, owner=self) if p else None
-
-
-class BilqrWorkspace(_Workspace):
+class BilqrWorkspace(_BiLanczosWorkspace):
     """BilqrWorkspace(m, n, S) (src/krylov_workspaces.jl:1818-1836): uₖ₋₁, uₖ, q, vₖ₋₁, vₖ, p, x, y, d̅, wₖ₋₃, wₖ₋₂; Δx and Δy stay empty
-    until a warm start.  The fused loops rotate the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and (wₖ₋₃, wₖ₋₂), and `vector(name)` follows the role
-    (khip_bilqr_vector): after k iterations a name holds what the reference's variable of that name holds."""
+    until a warm start."""
     _prefix = "bilqr"
     VECTORS = ("u_prev", "u", "q", "v_prev", "v", "p", "x", "y", "dbar", "w_prev3", "w_prev2")
-
-    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
-        self.ctx, self.m, self.n = ctx, m, n
-        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
-        self._h = C.c_void_p()
-        if self.adopted:
-            t0 = time.perf_counter()
-            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(n) for k in self.VECTORS}
-            self._alloc_s = time.perf_counter() - t0
-            _ck(lib().khip_bilqr_workspace_adopt(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
-        else:
-            _ck(lib().khip_bilqr_workspace_create(ctx._h, m, n, C.byref(self._h)))
+    SOLUTIONS = ("x", "y")
 
     @property
     def x(self) -> DeviceVector:
@@ -1682,12 +1658,6 @@ class BilqrWorkspace(_Workspace):
         if self.adopted:
             return self._vec["y"]
         return DeviceVector(self.ctx, self.n, ptr=lib().khip_bilqr_solution_y(self._h), owner=self)
-
-    def vector(self, name: str):
-        if name in ("x", "y"):
-            return getattr(self, name)
-        p = lib().khip_bilqr_vector(self._h, name.encode())
-        return DeviceVector(self.ctx, self.n, ptr=p, owner=self) if p else None
 
     @property
     def stats(self) -> AdjointStats:
@@ -1820,56 +1790,45 @@ def _bilq_precond_adjoint(name: str, op, adjoint, solver: str = "bilq"):
                         f"y <- {name}' x), or use a Jacobi {name}")
 
 
+def _bilq_qmr_solve(ws, prm, A, b, c, M, N, At, Mt, Nt, kw):
+    """What bilq_ and qmr_ share: the adjoints (At defaults to A.transpose(), Mt / Nt to a Jacobi M / N itself), the size check, t
+    and s on first need (src/bilq.jl:145-146, src/qmr.jl:151-152), Mt / Nt into the solver's params `prm`, and the call."""
+    keep = []
+    solver = ws._prefix
+    Mt = _bilq_precond_adjoint("M", M, Mt, solver=solver)
+    Nt = _bilq_precond_adjoint("N", N, Nt, solver=solver)
+    if len(b) != ws.n:
+        raise KhipError(-1, "Inconsistent problem size")
+    if At is None:
+        At = _adjoint_of(A, solver=solver)
+    ws._allocate_if(M is not None, "t")
+    ws._allocate_if(N is not None, "s")
+    opts = _make_options(keep=keep, ws=ws, **kw)
+    if Mt is not None:
+        prm.Mt = C.cast(_make_operator(ws.ctx, Mt, ws.n, keep), C.POINTER(COperator))
+    if Nt is not None:
+        prm.Nt = C.cast(_make_operator(ws.ctx, Nt, ws.n, keep), C.POINTER(COperator))
+    rc = ws._fn("solve")(ws._h, _make_operator(ws.ctx, A, ws.n, keep), _make_operator(ws.ctx, At, ws.n, keep),
+                         _make_operator(ws.ctx, M, ws.n, keep), _make_operator(ws.ctx, N, ws.n, keep), _p(b), _p(c),
+                         C.byref(opts), C.byref(prm))
+    return _finish(ws, rc)
+
+
 def bilq_(ws: BilqWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, transfer_to_bicg=True, M=None, N=None, At=None,
           Mt=None, Nt=None, **kw):
     """bilq!(workspace, A, b; c, transfer_to_bicg, M, N, ldiv, atol, rtol, itmax, timemax, verbose, history, callback, iostream)
     (src/bilq.jl:118-407).  At: the adjoint of A (default: A.transpose(), cached on A); Mt / Nt: the adjoints of M / N, required
     unless the operator is a Jacobi (its own adjoint).  Returns the workspace."""
-    keep = []
-    Mt = _bilq_precond_adjoint("M", M, Mt)
-    Nt = _bilq_precond_adjoint("N", N, Nt)
-    if len(b) != ws.n:
-        raise KhipError(-1, "Inconsistent problem size")
-    if At is None:
-        At = _adjoint_of(A)
-    ws._allocate_if(M is not None, "t")                                                   # src/bilq.jl:145-146
-    ws._allocate_if(N is not None, "s")
-    opts = _make_options(keep=keep, ws=ws, **kw)
     prm = lib().khip_bilq_default_params()
     prm.transfer_to_bicg = int(bool(transfer_to_bicg))
-    if Mt is not None:
-        prm.Mt = C.cast(_make_operator(ws.ctx, Mt, ws.n, keep), C.POINTER(COperator))
-    if Nt is not None:
-        prm.Nt = C.cast(_make_operator(ws.ctx, Nt, ws.n, keep), C.POINTER(COperator))
-    rc = lib().khip_bilq_solve(ws._h, _make_operator(ws.ctx, A, ws.n, keep), _make_operator(ws.ctx, At, ws.n, keep),
-                               _make_operator(ws.ctx, M, ws.n, keep), _make_operator(ws.ctx, N, ws.n, keep), _p(b), _p(c),
-                               C.byref(opts), C.byref(prm))
-    return _finish(ws, rc)
+    return _bilq_qmr_solve(ws, prm, A, b, c, M, N, At, Mt, Nt, kw)
 
 
 def qmr_(ws: QmrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, M=None, N=None, At=None, Mt=None, Nt=None, **kw):
     """qmr!(workspace, A, b; c, M, N, ldiv, atol, rtol, itmax, timemax, verbose, history, callback, iostream)
     (src/qmr.jl:124-406).  At: the adjoint of A (default: A.transpose(), cached on A); Mt / Nt: the adjoints of M / N, required
     unless the operator is a Jacobi (its own adjoint).  Returns the workspace."""
-    keep = []
-    Mt = _bilq_precond_adjoint("M", M, Mt, solver="qmr")
-    Nt = _bilq_precond_adjoint("N", N, Nt, solver="qmr")
-    if len(b) != ws.n:
-        raise KhipError(-1, "Inconsistent problem size")
-    if At is None:
-        At = _adjoint_of(A, solver="qmr")
-    ws._allocate_if(M is not None, "t")                                                   # src/qmr.jl:151-152
-    ws._allocate_if(N is not None, "s")
-    opts = _make_options(keep=keep, ws=ws, **kw)
-    prm = lib().khip_qmr_default_params()
-    if Mt is not None:
-        prm.Mt = C.cast(_make_operator(ws.ctx, Mt, ws.n, keep), C.POINTER(COperator))
-    if Nt is not None:
-        prm.Nt = C.cast(_make_operator(ws.ctx, Nt, ws.n, keep), C.POINTER(COperator))
-    rc = lib().khip_qmr_solve(ws._h, _make_operator(ws.ctx, A, ws.n, keep), _make_operator(ws.ctx, At, ws.n, keep),
-                              _make_operator(ws.ctx, M, ws.n, keep), _make_operator(ws.ctx, N, ws.n, keep), _p(b), _p(c),
-                              C.byref(opts), C.byref(prm))
-    return _finish(ws, rc)
+    return _bilq_qmr_solve(ws, lib().khip_qmr_default_params(), A, b, c, M, N, At, Mt, Nt, kw)
 
 
 def bilqr_(ws: BilqrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, transfer_to_bicg=True, **kw):

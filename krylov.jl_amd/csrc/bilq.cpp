@@ -14,17 +14,15 @@
 // written where vₖ₋₁ was).  Every elementwise value uses the expression of the primitive it replaces (fma for kaxpy!, fma(a, x, b y)
 // for kaxpby!, / for kdivcopy!): the fused loops agree with the primitive sequence bit for bit on elementwise values and to the
 // reductions' one ulp otherwise; loops 1 and 2 run the same kernels and the same scalar code and produce the same bits.
-#include <chrono>
-#include <utility>
-
-#include "bilanczos_passes.hpp"   // P1, P2 and their launchers, shared with qmr.cpp
+// This file owns P3, the set-up scalars, the LQ part of a primitive iteration and the status strings; the loops are bilanczos.hpp's.
+#include "bilanczos.hpp"   // P1, P2 and the driver of the three loops, shared with qmr.cpp and bilqr.cpp
 
 using namespace khip;
 
 namespace khip {   // (named, not anonymous: stable kernel names in traces)
 
 // ---------------------------------------------------------------------------------------------------------- kernels ----
-// (P1 and P2: bilanczos_passes.hpp.)
+// (P1 and P2: bilanczos.hpp.)
 // Each thread owns one VEC-vector of every stream; the odd tail element (VEC = 2, n odd) goes to thread 0 of block 0.
 // Cache hints, one rule: a load is non-temporal when it is the LAST read of that data (the vector is dead or overwritten
 // afterwards: v_prev, u_prev, q, p, x, d̅); vₖ and uₖ are read again up to the next iteration's P1 (as vₖ₋₁, uₖ₋₁) and stay
@@ -134,9 +132,50 @@ struct khip_bilq_workspace {
 
 namespace {
 
-void verbose_row(const khip_options &o, long long iter, double alpha, double rNorm, double t0) {     // src/bilq.jl:201, :374
-  klogf(o.log_fd, "%5lld  %8.1e  %7.1e  %.2fs\n", iter, alpha, rNorm, now_s() - t0);
-}
+// uₖ₋₁, uₖ, q, vₖ₋₁, vₖ, p, x, d̅ come with the workspace; Δx, t, s stay empty until needed (src/krylov_workspaces.jl, BilqWorkspace)
+using W = khip_bilq_workspace;
+constexpr WsVec<W> kVectors[] = {{"u_prev", &W::u_prev, Core}, {"u", &W::u, Core}, {"q", &W::q, Core}, {"v_prev", &W::v_prev, Core},
+                                 {"v", &W::v, Core},           {"p", &W::p, Core}, {"x", &W::x, Core}, {"dbar", &W::dbar, Core},
+                                 {"dx", &W::dx, Lazy},         {"t", &W::t, Lazy}, {"s", &W::s, Lazy}};
+
+// what bilq! adds to the two-sided Lanczos driver (bilanczos.hpp)
+struct Bilq : BiLanczosPolicy<BilqDevState, W> {
+  static constexpr Epilogue kEpiA = EPI_BILQ_A, kEpiB = EPI_BILQ_B, kEpiC = EPI_BILQ_C;
+  static constexpr int kP3Sums = 2;                                                    // vₖ.vₖ₊₁, vₖ₊₁.vₖ₊₁
+  double *x, *dbar;
+  static void step_a(State &s, double uq) { bilq_step_a(s, uq); }
+  static void step_b(State &s, double pq, int64_t k) { bilq_step_b(s, pq, k); }
+  static void step_c(State &s, const double *sums, int64_t k) { bilq_step_c(s, sums[0], std::sqrt(sums[1]), k); }
+  static bool stopped(const State &s) { return s.solved_lq || s.solved_cg || s.breakdown; }
+  int p3(khip_ctx *ctx, int64_t n, const State *dev, const BiLanczosRoles &r, int64_t k, int slot) const {
+    return launch_p3(ctx, n, dev, x, dbar, r.v, r.u, r.q, r.p, r.v_prev, r.u_prev, k == 1, slot);
+  }
+  void push_history(W *ws, const State &s) const { ws->box.push(s.rNorm_lq); }
+  static void row(const khip_options &o, long long iter, double alpha, double rNorm, double t0) {   // src/bilq.jl:201, :374
+    klogf(o.log_fd, "%5lld  %8.1e  %7.1e  %.2fs\n", iter, alpha, rNorm, now_s() - t0);
+  }
+  void verbose_row(const khip_options &o, long long k, const State &s, double t0) const { row(o, k, s.alpha, s.rNorm_lq, t0); }
+  // the LQ update, the shift, then vₖ.vₖ₊₁ and ‖vₖ₊₁‖ on the shifted vectors (src/bilq.jl:310-345)
+  int primitive_tail(BiLanczos<Bilq> &L, int64_t k, double pq) const {
+    W *ws = L.ws;
+    khip_ctx *ctx = L.ctx;
+    const int64_t n = L.n;
+    State &s = L.s;
+    if (k == 1) {
+      K(khip_copy(ctx, n, dbar, L.r.v));
+    } else {
+      K(khip_axpy(ctx, n, s.zc, dbar, x));
+      K(khip_axpy(ctx, n, s.zs, L.r.v, x));
+      K(khip_axpby(ctx, n, s.neg_c, L.r.v, s.sn, dbar));
+    }
+    K(L.shift(pq));
+    double vv, norm_next;
+    K(khip_dot(ctx, n, L.r.v_prev, L.r.v, &vv));
+    K(khip_nrm2(ctx, n, L.r.v, &norm_next));
+    bilq_step_c(s, vv, norm_next, k);
+    return KHIP_OK;
+  }
+};
 
 }  // namespace
 
@@ -155,13 +194,8 @@ int khip_bilq_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_bilq_wo
   KHIP_REQUIRE(m == n, "System must be square");
   khip_bilq_workspace *ws = new khip_bilq_workspace();
   ws->ctx = ctx; ws->m = m; ws->n = n;
-  (void)take_alloc_seconds();
-  // uₖ₋₁, uₖ, q, vₖ₋₁, vₖ, p, x, d̅ allocated; Δx, t, s stay empty until needed (src/krylov_workspaces.jl, BilqWorkspace)
-  int rc = KHIP_OK;
-  for (double **slot : {&ws->u_prev, &ws->u, &ws->q, &ws->v_prev, &ws->v, &ws->p, &ws->x, &ws->dbar})
-    if (!rc) rc = alloc_vec(ctx, n, slot);
+  const int rc = ws_create_core(ws, kVectors);
   if (rc) { khip_bilq_workspace_destroy(ws); return rc; }
-  ws->box.st.allocation_timer = take_alloc_seconds();
   *out = ws;
   return KHIP_OK;
 }
@@ -170,311 +204,91 @@ int khip_bilq_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *u_pre
                               double *p, double *x, double *dbar, khip_bilq_workspace **out) {
   KHIP_REQUIRE(ctx && out && m >= 0 && n >= 0, "bilq_workspace_adopt: bad argument");
   KHIP_REQUIRE(m == n, "System must be square");
-  KHIP_REQUIRE(n == 0 || (u_prev && u && q && v_prev && v && p && x && dbar),
-               "bilq_workspace_adopt: u_prev, u, q, v_prev, v, p, x, dbar must be device vectors of n entries");
-  const double *all[8] = {u_prev, u, q, v_prev, v, p, x, dbar};
-  for (int i = 0; i < 8; ++i)
-    for (int j = i + 1; j < 8; ++j)
-      KHIP_REQUIRE(n == 0 || all[i] != all[j], "bilq_workspace_adopt: u_prev, u, q, v_prev, v, p, x, dbar must be distinct");
   khip_bilq_workspace *ws = new khip_bilq_workspace();
   ws->ctx = ctx; ws->m = m; ws->n = n;
-  ws->u_prev = u_prev; ws->u = u; ws->q = q; ws->v_prev = v_prev; ws->v = v; ws->p = p; ws->x = x; ws->dbar = dbar;
-  for (const double *ptr : all) ws->borrowed.add(ptr);
+  const int rc = ws_adopt_core(ws, kVectors, "bilq_workspace_adopt", {u_prev, u, q, v_prev, v, p, x, dbar});
+  if (rc) { delete ws; return rc; }
   *out = ws;
   return KHIP_OK;
 }
 
 int khip_bilq_workspace_adopt_vector(khip_bilq_workspace *ws, const char *name, double *ptr) {
-  KHIP_REQUIRE(ws && name, "bilq_workspace_adopt_vector: null argument");
-  using S = NamedSlot;
-  return adopt_named(ws->ctx, ws->borrowed, {{"u_prev", &ws->u_prev, S::Fixed}, {"u", &ws->u, S::Fixed}, {"q", &ws->q, S::Fixed},
-                     {"v_prev", &ws->v_prev, S::Fixed}, {"v", &ws->v, S::Fixed}, {"p", &ws->p, S::Fixed}, {"x", &ws->x, S::Fixed},
-                     {"dbar", &ws->dbar, S::Fixed}, {"dx", &ws->dx, S::Optional}, {"t", &ws->t, S::Optional},
-                     {"s", &ws->s, S::Optional}},
-                     "bilq_workspace_adopt_vector", "vector", name, ptr);
+  return ws_adopt_vector(ws, kVectors, "bilq_workspace_adopt_vector", name, ptr);
 }
 
 int khip_bilq_workspace_destroy(khip_bilq_workspace *ws) {
   if (!ws) return KHIP_OK;
-  for (double *ptr : {ws->u_prev, ws->u, ws->q, ws->v_prev, ws->v, ws->p, ws->x, ws->dbar, ws->dx, ws->t, ws->s})
-    free_unless_borrowed(ws->ctx, ws->borrowed, ptr);
+  ws_free_vectors(ws, kVectors);
   ws->loop.release();
   delete ws;
   return KHIP_OK;
 }
 
-int khip_bilq_warm_start(khip_bilq_workspace *ws, const double *x0) {
-  KHIP_REQUIRE(ws && x0, "bilq_warm_start: null argument");
-  if (!ws->dx) KHIP_TRY(alloc_vec(ws->ctx, ws->n, &ws->dx));
-  if (x0 != ws->dx) KHIP_TRY(khip_copy(ws->ctx, ws->n, ws->dx, x0));
-  ws->warm_start = true;
-  return KHIP_OK;
-}
-
+int khip_bilq_warm_start(khip_bilq_workspace *ws, const double *x0) { return ws_warm_start(ws, x0, "bilq_warm_start"); }
 double *khip_bilq_solution(khip_bilq_workspace *ws) { return ws ? ws->x : nullptr; }
 const khip_stats *khip_bilq_stats(khip_bilq_workspace *ws) { return ws ? &ws->box.st : nullptr; }
 int khip_bilq_last_path(khip_bilq_workspace *ws) { return ws ? ws->box.path : -1; }
-double *khip_bilq_vector(khip_bilq_workspace *ws, const char *name) {
-  if (!ws || !name) return nullptr;
-  struct { const char *k; double *p; } tab[] = {{"u_prev", ws->u_prev}, {"u", ws->u}, {"q", ws->q}, {"v_prev", ws->v_prev},
-                                                {"v", ws->v}, {"p", ws->p}, {"x", ws->x}, {"dbar", ws->dbar}, {"dx", ws->dx},
-                                                {"t", ws->t}, {"s", ws->s}};
-  for (auto &e : tab) if (strcmp(e.k, name) == 0) return e.p;
-  return nullptr;
-}
-size_t khip_bilq_workspace_bytes(khip_bilq_workspace *ws) {
-  if (!ws) return 0;
-  size_t cnt = 0;
-  for (double *ptr : {ws->u_prev, ws->u, ws->q, ws->v_prev, ws->v, ws->p, ws->x, ws->dbar, ws->dx, ws->t, ws->s}) cnt += ptr ? 1 : 0;
-  return cnt * sizeof(double) * (size_t)ws->n;
-}
+double *khip_bilq_vector(khip_bilq_workspace *ws, const char *name) { return ws_vector(ws, kVectors, name); }
+size_t khip_bilq_workspace_bytes(khip_bilq_workspace *ws) { return ws_bytes(ws, kVectors); }
 
 int khip_bilq_solve(khip_bilq_workspace *ws, const khip_operator *A, const khip_operator *At, const khip_operator *M,
                     const khip_operator *N, const double *b, const double *c, const khip_options *opts_in,
                     const khip_bilq_params *params_in) {
   KHIP_REQUIRE(ws && A && b, "bilq_solve: null argument");
-  khip_ctx *ctx = ws->ctx;
-  const khip_options o = opts_in ? *opts_in : khip_default_options();
   const khip_bilq_params prm = params_in ? *params_in : khip_bilq_default_params();
-  const double t0 = now_s();
-  const double timemax = timemax_of(o);
-  const int64_t n = ws->n;
-  khip_stats *st = &ws->box.st;
+  BiLanczos<Bilq> L(ws, A, At, M, N, prm.Mt, prm.Nt, opts_in);
+  khip_ctx *ctx = L.ctx;
+  const khip_options &o = L.o;
+  const int64_t n = L.n;
+  BilqDevState &s = L.s;
   const double atol = tol_or_default(o.atol), rtol = tol_or_default(o.rtol);
-  const int verbose = o.verbose;
-  const bool history = o.history != 0;
-  (void)take_alloc_seconds();
 
-  if (!At) return ws->box.fail(KHIP_ERR_INVALID, "bilq_solve: At (the adjoint of A) is required");
-  for (const khip_operator *op : {A, At}) {                                                              // :124-126
-    if (!(op->csr && !op->apply)) continue;
-    int64_t am, an;
-    khip_csr_shape(op->csr, &am, &an, nullptr);
-    if (am != ws->m || (an != ws->n && !op->csr->dist)) {             // a row-partitioned handle counts global columns
-      char msg[160];
-      snprintf(msg, sizeof(msg), "(workspace.m, workspace.n) = (%lld, %lld) is inconsistent with size(A) = (%lld, %lld)",
-               (long long)ws->m, (long long)ws->n, (long long)am, (long long)an);
-      return ws->box.fail(KHIP_ERR_INVALID, msg);
-    }
-  }
-  if (ws->m != ws->n) return ws->box.fail(KHIP_ERR_INVALID, "System must be square");
-  if (verbose > 0) klogf(o.log_fd, "BILQ: system of size %lld\n", (long long)n);                         // :128
-  const bool MisI = (M == nullptr), NisI = (N == nullptr);
-  const khip_operator *Mt = prm.Mt ? prm.Mt : M, *Nt = prm.Nt ? prm.Nt : N;
-  if (!MisI && !ws->t) K(alloc_vec(ctx, n, &ws->t));                                                     // :145-146
-  if (!NisI && !ws->s) K(alloc_vec(ctx, n, &ws->s));
+  if (int rc = L.check("bilq", "System must be square")) return rc;                                        // :124-126
+  if (o.verbose > 0) klogf(o.log_fd, "BILQ: system of size %lld\n", (long long)n);                       // :128
+  K(L.allocate_ts());                                                                                     // :145-146
   if (!c) c = b;
   const bool warm_start = ws->warm_start;
   ws->box.reset();
-  double *x = ws->x, *dbar = ws->dbar, *q = ws->q, *p = ws->p;
-  double *v = ws->v, *v_prev = ws->v_prev, *u = ws->u, *u_prev = ws->u_prev;
-  auto finish = [&](void) {
-    st->timer = now_s() - t0;
-    ws->warm_start = false;
-    st->allocation_timer += take_alloc_seconds();
-    ws->box.publish();
-  };
+  double *x = L.pol.x = ws->x, *dbar = L.pol.dbar = ws->dbar;
 
   // set-up, the same primitives on every path (:158-215)
-  const double *r0 = b;
-  if (warm_start) {
-    K(apply_op(ctx, A, ws->dx, q));
-    K(khip_axpby(ctx, n, 1.0, b, -1.0, q));
-    r0 = q;
-  }
-  if (!MisI) {
-    K(apply_op(ctx, M, r0, ws->t));
-    r0 = ws->t;
-  }
+  const double *r0;
+  K(L.residual(b, warm_start, &r0));
   K(khip_fill(ctx, n, x, 0.0));
   double bNorm;
   K(khip_nrm2(ctx, n, r0, &bNorm));
-  if (history) ws->box.push(bNorm);
+  if (L.history) ws->box.push(bNorm);
   ws->box.path = o.fused ? 1 : 0;
-  auto early = [&](int solved, const char *status) {
-    st->niter = 0; st->solved = solved; st->inconsistent = 0;
-    snprintf(st->status, sizeof(st->status), "%s", status);
-    if (warm_start) K(khip_axpy(ctx, n, 1.0, ws->dx, x));
-    finish();
-    return (int)KHIP_OK;
-  };
-  if (bNorm == 0) return early(1, "x is a zero-residual solution");                                      // :172-181
-  const int64_t itmax = o.itmax == 0 ? 2 * global_rows(ctx, A, n) : o.itmax;
+  if (bNorm == 0) return L.end(1, "x is a zero-residual solution", warm_start, true);                    // :172-181
+  L.itmax = o.itmax == 0 ? 2 * global_rows(ctx, A, n) : o.itmax;
   double cb;
   K(khip_dot(ctx, n, c, r0, &cb));
-  if (cb == 0) return early(0, "Breakdown b\xe1\xb4\xb4" "c = 0");                                       // :188-197
-  BilqDevState s;
-  memset(&s, 0, sizeof(s));
+  if (cb == 0) return L.end(0, "Breakdown b\xe1\xb4\xb4" "c = 0", warm_start, true);                     // :188-197
   s.bNorm = bNorm;
   s.eps_tol = atol + rtol * bNorm;
-  if (verbose > 0) {
+  if (o.verbose > 0) {
     klogf(o.log_fd, "%5s        %s     %s  %5s\n", "k", "\xce\xb1\xe2\x82\x96", "\xe2\x80\x96r\xe2\x82\x96\xe2\x80\x96", "timer");
-    if (kdisplay(0, verbose)) verbose_row(o, 0, cb, bNorm, t0);
+    if (kdisplay(0, o.verbose)) Bilq::row(o, 0, cb, bNorm, L.t0);
   }
-  s.beta = std::sqrt(std::fabs(cb));
-  s.gamma = cb / s.beta;
-  K(khip_fill(ctx, n, v_prev, 0.0));
-  K(khip_fill(ctx, n, u_prev, 0.0));
-  K(khip_divcopy(ctx, n, v, r0, s.beta));
-  K(khip_divcopy(ctx, n, u, c, s.gamma));
+  K(L.start(cb, r0, c));
   s.cs = s.cs_prev = -1.0;
   K(khip_fill(ctx, n, dbar, 0.0));
   s.norm_v = bNorm / s.beta;
   s.transfer_to_bicg = prm.transfer_to_bicg ? 1 : 0;
   s.stop_seq = kSeqNever;
   s.solved_lq = (bNorm <= s.eps_tol) ? 1 : 0;
-  bool tired = 0 >= itmax, user_exit = false, overtimed = false;
-  int64_t iter = 0;
-  auto running = [&] { return !(s.solved_lq || s.solved_cg || tired || s.breakdown || user_exit || overtimed); };
-  // q <- M A N v and p <- N' A' M' u (:234-242)
-  auto products = [&](const double *vk, const double *uk, double *qk, double *pk) -> int {
-    if (!NisI) KHIP_TRY(apply_op_no_epilogue(ctx, N, vk, ws->s));
-    KHIP_TRY(apply_op_no_epilogue(ctx, A, NisI ? vk : ws->s, MisI ? qk : ws->t));
-    if (!MisI) KHIP_TRY(apply_op_no_epilogue(ctx, M, ws->t, qk));
-    if (!MisI) KHIP_TRY(apply_op_no_epilogue(ctx, Mt, uk, ws->t));
-    KHIP_TRY(apply_op_no_epilogue(ctx, At, MisI ? uk : ws->t, NisI ? pk : ws->s));
-    if (!NisI) KHIP_TRY(apply_op_no_epilogue(ctx, Nt, ws->s, pk));
-    return KHIP_OK;
-  };
-  // the end of an iteration on the host-driven loops (:347, :367-374)
-  auto host_tail = [&](int64_t k) {
-    if (history) ws->box.push(s.rNorm_lq);
-    if (o.callback) {
-      ws->box.publish();                          // the callback reads stats.residuals
-      user_exit = o.callback(ws, o.callback_data) != 0;
-    }
-    tired = k >= itmax;
-    overtimed = time_limit_reached(ctx, now_s() - t0, timemax);
-    if (kdisplay(k, verbose)) verbose_row(o, k, s.alpha, s.rNorm_lq, t0);
-  };
 
-  const bool csr_pair = A->csr && !A->apply && At->csr && !At->apply;
-  const bool device_loop = o.fused >= 2 && csr_pair && MisI && NisI && !o.callback && verbose <= 0;
-  ws->box.path = (device_loop && running()) ? 2 : (o.fused ? 1 : 0);   // a loop that never starts reports 1, as the early returns do
+  K(L.iterate());                                                                                         // :226-375
 
-  if (ws->box.path == 0) {
-    // ---------------------------------------------------------------- the reference's primitive sequence (:226-375) ----
-    while (running()) {
-      const int64_t k = ++iter;
-      K(products(v, u, q, p));
-      K(khip_axpy(ctx, n, -s.gamma, v_prev, q));
-      K(khip_axpy(ctx, n, -s.beta, u_prev, p));
-      double uq;
-      K(khip_dot(ctx, n, u, q, &uq));
-      bilq_step_a(s, uq);
-      K(khip_axpy(ctx, n, -s.alpha, v, q));
-      K(khip_axpy(ctx, n, -s.alpha, u, p));
-      double pq;
-      K(khip_dot(ctx, n, p, q, &pq));
-      bilq_step_b(s, pq, k);
-      if (k == 1) {
-        K(khip_copy(ctx, n, dbar, v));
-      } else {
-        K(khip_axpy(ctx, n, s.zc, dbar, x));
-        K(khip_axpy(ctx, n, s.zs, v, x));
-        K(khip_axpby(ctx, n, s.neg_c, v, s.sn, dbar));
-      }
-      K(khip_copy(ctx, n, v_prev, v));
-      K(khip_copy(ctx, n, u_prev, u));
-      if (pq != 0) {
-        K(khip_divcopy(ctx, n, v, q, s.beta_next));
-        K(khip_divcopy(ctx, n, u, p, s.gamma_next));
-      }
-      double vv, norm_next;
-      K(khip_dot(ctx, n, v_prev, v, &vv));
-      K(khip_nrm2(ctx, n, v, &norm_next));
-      bilq_step_c(s, vv, norm_next, k);
-      host_tail(k);
-    }
-  } else if (ws->box.path == 1) {
-    // ---------------------------------------------------------------- host-driven loop on the fused kernels ----------
-    K(ws->loop.alloc());
-    s.hist = nullptr;
-    while (running()) {
-      const int64_t k = ++iter;
-      K(products(v, u, q, p));
-      K(ws->loop.upload(ctx, s));
-      int slot = take_slots(ctx, 1);
-      K(launch_p1(ctx, n, ws->loop.dev, v_prev, u_prev, u, q, p, slot));
-      double uq;
-      K(fetch_results(ctx, slot, 1, &uq));
-      bilq_step_a(s, uq);
-      K(ws->loop.upload(ctx, s));
-      slot = take_slots(ctx, 1);
-      K(launch_p2(ctx, n, ws->loop.dev, v, u, q, p, slot));
-      double pq;
-      K(fetch_results(ctx, slot, 1, &pq));
-      bilq_step_b(s, pq, k);
-      K(ws->loop.upload(ctx, s));
-      slot = take_slots(ctx, 2);
-      K(launch_p3(ctx, n, ws->loop.dev, x, dbar, v, u, q, p, v_prev, u_prev, k == 1, slot));
-      double r[2];
-      K(fetch_results(ctx, slot, 2, r));
-      std::swap(v, v_prev);                        // vₖ₋₁ <- vₖ ; vₖ <- vₖ₊₁ (:325-330) as a rotation of the roles
-      std::swap(u, u_prev);
-      bilq_step_c(s, r[0], std::sqrt(r[1]), k);
-      host_tail(k);
-    }
-  } else {
-    // ---------------------------------------------------------------- device-resident loop -----------------------------
-    double *vc = v, *vp = v_prev, *uc = u, *up = u_prev;
-    auto step = [&](BilqDevState *dev, long long j) {
-      const int64_t k = j + 1;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 1, EPI_NONE, nullptr};
-      int rc = spmv_any(ctx, A->csr, vc, q, -1);                                          // q = A vₖ
-      if (rc == KHIP_OK) rc = spmv_any(ctx, At->csr, uc, p, -1);                          // p = A' uₖ
-      if (rc != KHIP_OK) return rc;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 2, EPI_BILQ_A, dev};
-      int slot = take_slots(ctx, 1);
-      rc = launch_p1(ctx, n, dev, vp, up, uc, q, p, slot);                               // P1 ; u.q -> α
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-      if (rc != KHIP_OK) return rc;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 3, EPI_BILQ_B, dev};
-      slot = take_slots(ctx, 1);
-      rc = launch_p2(ctx, n, dev, vc, uc, q, p, slot);                                   // P2 ; p.q -> the LQ update
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-      if (rc != KHIP_OK) return rc;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 4, EPI_BILQ_C, dev};
-      slot = take_slots(ctx, 2);
-      rc = launch_p3(ctx, n, dev, x, dbar, vc, uc, q, p, vp, up, k == 1, slot);          // P3 ; the two dots -> tests
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 2);
-      ctx->ctl = SeqCtl{};
-      if (rc != KHIP_OK) return rc;
-      std::swap(vc, vp);
-      std::swap(uc, up);
-      return KHIP_OK;
-    };
-    // a finite timemax: the first chunk is ONE iteration, so that a limit already used up stops after iteration 1 as the
-    // host-driven loop does
-    const DeviceLoopArgs loop_args{itmax, t0, timemax, history, {&ws->box.residuals, nullptr, nullptr},
-                                   timemax < 1e300 ? 1 : kDevChunk};
-    K(ws->loop.run(ctx, s, loop_args, step, &s, &overtimed));
-    iter = s.iter;
-    tired = iter >= itmax;
-    // the host rotated the roles for every iteration it enqueued; the device ran s.iter of them
-    if (iter & 1) { std::swap(v, v_prev); std::swap(u, u_prev); }
-  }
-  ws->v = v; ws->v_prev = v_prev; ws->u = u; ws->u_prev = u_prev;
-  if (verbose > 0) klogf(o.log_fd, "\n");
   if (s.solved_cg) K(khip_axpy(ctx, n, s.zbar, dbar, x));                                                // :380-382
   const char *status = "unknown";                                                                         // :385-390
-  if (tired) status = "maximum number of iterations exceeded";
+  if (L.tired) status = "maximum number of iterations exceeded";
   if (s.breakdown) status = "Breakdown \xe2\x9f\xa8u\xe2\x82\x96\xe2\x82\x8a\xe2\x82\x81,v\xe2\x82\x96\xe2\x82\x8a\xe2\x82\x81\xe2\x9f\xa9 = 0";
   if (s.solved_lq) status = "solution x\xe1\xb4\xb8 good enough given atol and rtol";
   if (s.solved_cg) status = "solution x\xe1\xb6\x9c good enough given atol and rtol";
-  if (user_exit) status = "user-requested exit";
-  if (overtimed) status = "time limit exceeded";
-  if (!NisI) {                                                                                            // :393-396
-    K(khip_copy(ctx, n, ws->s, x));
-    K(apply_op(ctx, N, ws->s, x));
-  }
-  if (warm_start) K(khip_axpy(ctx, n, 1.0, ws->dx, x));
-  st->niter = (int)iter;
-  st->solved = (s.solved_lq || s.solved_cg) ? 1 : 0;
-  st->inconsistent = 0;
-  snprintf(st->status, sizeof(st->status), "%s", status);
-  finish();
-  return KHIP_OK;
+  if (L.user_exit) status = "user-requested exit";
+  if (L.overtimed) status = "time limit exceeded";
+  return L.end((s.solved_lq || s.solved_cg) ? 1 : 0, status, warm_start);                                // :393-396
 }
 
 }  // extern "C"

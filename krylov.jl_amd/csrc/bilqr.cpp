@@ -7,8 +7,8 @@
 //   2  the device-resident loop (default; A and A' both CSR handles): the scalar recurrences and stopping tests run as the
 //      epilogues of the three reductions of an iteration (bilqr_step_a/b/c, solver_device.hpp), iterations are enqueued ahead.
 // One iteration on the fused paths, after q = A vₖ and p = A' uₖ, with both sides unsolved:
-//   P1   q = fma(-γₖ, vₖ₋₁, q) ; p = fma(-βₖ, uₖ₋₁, p) ; uₖ.q                          (bilanczos_passes.hpp)      56n bytes
-//   P2   q = fma(-αₖ, vₖ, q) ; p = fma(-αₖ, uₖ, p) ; p.q                               (bilanczos_passes.hpp)      48n bytes
+//   P1   q = fma(-γₖ, vₖ₋₁, q) ; p = fma(-βₖ, uₖ₋₁, p) ; uₖ.q                          (bilanczos.hpp)             56n bytes
+//   P2   q = fma(-αₖ, vₖ, q) ; p = fma(-αₖ, uₖ, p) ; p.q                               (bilanczos.hpp)             48n bytes
 //   P3   x = fma(ζₖ₋₁sₖ, vₖ, fma(ζₖ₋₁cₖ, d̅, x)) ; d̅ = fma(-cₖ, vₖ, sₖ d̅) ;
 //        wₖ₋₁ = (uₖ₋₁ - λₖ₋₂ wₖ₋₂ - ϵₖ₋₃ wₖ₋₃) / δₖ₋₁ ; y = fma(ψₖ₋₁, wₖ₋₁, y) ;
 //        vₖ₊₁ = q / βₖ₊₁ ; uₖ₊₁ = p / γₖ₊₁ ; vₖ.q ; q.q ; uₖ₊₁.uₖ₊₁                                                 120n bytes
@@ -23,11 +23,11 @@
 // scalar step divides, so that βₖ₊₁ = 0 gives the reference's NaN.  ‖uₖ₊₁‖² is the third sum: the scalar step keeps it and adds it to
 // τ in the NEXT iteration (:398), as qmr! carries ‖vₖ₊₁‖²; ‖u₁‖² comes from one dot at set-up.  The finish kernel exists for 1, 2 and
 // 4 sums: a fourth, zero, is published beside the three.
-#include <chrono>
+// This file owns P3, the set-up of both systems, the LQ and QR parts of a primitive iteration and the status strings; the loops are
+// bilanczos.hpp's.
 #include <string>
-#include <utility>
 
-#include "bilanczos_passes.hpp"   // P1, P2 and their launchers, shared with bilq.cpp and qmr.cpp
+#include "bilanczos.hpp"   // P1, P2 and the driver of the three loops, shared with bilq.cpp and qmr.cpp
 
 using namespace khip;
 
@@ -199,14 +199,89 @@ struct khip_bilqr_workspace {
 
 namespace {
 
+// uₖ₋₁, uₖ, q, vₖ₋₁, vₖ, p, x, y, d̅, wₖ₋₃, wₖ₋₂ come with the workspace; Δx, Δy stay empty until a warm start
+// (src/krylov_workspaces.jl, BilqrWorkspace)
+using W = khip_bilqr_workspace;
+constexpr WsVec<W> kVectors[] = {{"u_prev", &W::u_prev, Core},   {"u", &W::u, Core},   {"q", &W::q, Core}, {"v_prev", &W::v_prev, Core},
+                                 {"v", &W::v, Core},             {"p", &W::p, Core},   {"x", &W::x, Core}, {"y", &W::y, Core},
+                                 {"dbar", &W::dbar, Core},       {"w_prev3", &W::w_prev3, Core},
+                                 {"w_prev2", &W::w_prev2, Core}, {"dx", &W::dx, Lazy}, {"dy", &W::dy, Lazy}};
+
 // "%7s" of the reference pads characters; ✗ ✗ ✗ ✗ is seven of them                                        (src/bilqr.jl:439-441)
 const char *const kCrosses = "\xe2\x9c\x97 \xe2\x9c\x97 \xe2\x9c\x97 \xe2\x9c\x97";
 
-void verbose_row(const khip_options &o, long long iter, const BilqrDevState &s, double t0) {
-  if (s.solved_primal && !s.solved_dual) klogf(o.log_fd, "%5lld  %s  %7.1e  %.2fs\n", iter, kCrosses, s.sNorm, now_s() - t0);
-  if (!s.solved_primal && s.solved_dual) klogf(o.log_fd, "%5lld  %7.1e  %s  %.2fs\n", iter, s.rNorm_lq, kCrosses, now_s() - t0);
-  if (!s.solved_primal && !s.solved_dual) klogf(o.log_fd, "%5lld  %7.1e  %7.1e  %.2fs\n", iter, s.rNorm_lq, s.sNorm, now_s() - t0);
-}
+// what bilqr! adds to the two-sided Lanczos driver (bilanczos.hpp)
+struct Bilqr : BiLanczosPolicy<BilqrDevState, W> {
+  static constexpr Epilogue kEpiA = EPI_BILQR_A, kEpiB = EPI_BILQR_B, kEpiC = EPI_BILQR_C;
+  static constexpr int kP3Sums = ::kP3Sums;
+  double *x, *dbar, *y, *w3, *w2;                                                      // wₖ₋₃, wₖ₋₂ by their current role
+  bool primal = true, dual = true;                  // host-driven loops: the sides that were unsolved when the iteration began
+  static void step_a(State &s, double uq) { bilqr_step_a(s, uq); }
+  static void step_b(State &s, double pq, int64_t k) { bilqr_step_b(s, pq, k); }
+  static void step_c(State &s, const double *sums, int64_t k) { bilqr_step_c(s, sums[0], std::sqrt(sums[1]), sums[2], k); }
+  static bool stopped(const State &s) { return (s.solved_primal && s.solved_dual) || s.breakdown; }
+  void begin_iteration(const State &s) { primal = !s.solved_primal; dual = !s.solved_dual; }
+  int fused_start(khip_ctx *ctx, int64_t n, const BiLanczosRoles &r, State &s) { return khip_dot(ctx, n, r.u, r.u, &s.uu); }   // ‖u₁‖²
+  // u_prev twice: read as uₖ₋₁ and written as uₖ₊₁
+  int p3(khip_ctx *ctx, int64_t n, const State *dev, const BiLanczosRoles &r, int64_t k, int slot) const {
+    return launch_p3(ctx, n, dev, x, dbar, y, w3, w2, k == 2 ? w2 : w3, r.v, r.u, r.u_prev, r.q, r.p, r.v_prev, r.u_prev,
+                     k < 4 ? (int)k : 4, slot);
+  }
+  // wₖ₋₁ was written over wₖ₋₃ (src/bilqr.jl:383-386); enqueued ahead, a dual side that is solved no longer touches either buffer
+  void rotate(int64_t k, bool host_driven) { if (k >= 3 && (dual || !host_driven)) std::swap(w3, w2); }
+  void fix_after_device_loop(const State &s) { if (s.nhist_d >= 3 && (s.nhist_d & 1)) std::swap(w3, w2); }   // the dual block ran nhist_d times
+  void store(W *ws) const { ws->w_prev3 = w3; ws->w_prev2 = w2; }
+  static std::vector<double> *dual_history(W *ws) { return &ws->residuals_dual; }
+  void push_history(W *ws, const State &s) const {                                     // :327, :402
+    if (primal) ws->box.push(s.rNorm_lq);
+    if (dual) ws->residuals_dual.push_back(s.sNorm);
+  }
+  void verbose_row(const khip_options &o, long long iter, const State &s, double t0) const {
+    if (s.solved_primal && !s.solved_dual) klogf(o.log_fd, "%5lld  %s  %7.1e  %.2fs\n", iter, kCrosses, s.sNorm, now_s() - t0);
+    if (!s.solved_primal && s.solved_dual) klogf(o.log_fd, "%5lld  %7.1e  %s  %.2fs\n", iter, s.rNorm_lq, kCrosses, now_s() - t0);
+    if (!s.solved_primal && !s.solved_dual) klogf(o.log_fd, "%5lld  %7.1e  %7.1e  %.2fs\n", iter, s.rNorm_lq, s.sNorm, now_s() - t0);
+  }
+  // the LQ update with vₖ.q and ‖q‖, the QR update with ‖uₖ‖², both BEFORE the shift (src/bilqr.jl:296-418)
+  int primitive_tail(BiLanczos<Bilqr> &L, int64_t k, double pq) {
+    W *ws = L.ws;
+    khip_ctx *ctx = L.ctx;
+    const int64_t n = L.n;
+    State &s = L.s;
+    const BiLanczosRoles &r = L.r;
+    double vq = 0.0, q_norm = 0.0;
+    if (primal) {                                                                                         // :296-315
+      if (k == 1) {
+        K(khip_copy(ctx, n, dbar, r.v));
+      } else {
+        K(khip_axpy(ctx, n, s.zc, dbar, x));
+        K(khip_axpy(ctx, n, s.zs, r.v, x));
+        K(khip_axpby(ctx, n, s.neg_c, r.v, s.sn, dbar));
+      }
+      K(khip_dot(ctx, n, r.v, r.q, &vq));
+      K(khip_nrm2(ctx, n, r.q, &q_norm));
+    }
+    if (dual) {                                                                                           // :361-398
+      double *w = nullptr;
+      if (k == 2) {
+        w = w2;
+        K(khip_divcopy(ctx, n, w, r.u_prev, s.delta));
+      }
+      if (k >= 3) {
+        w = w3;
+        if (k >= 4) K(khip_scal(ctx, n, s.neg_eps3, w));
+        K(khip_axpy(ctx, n, 1.0, r.u_prev, w));
+        K(khip_axpy(ctx, n, s.neg_lambda2, w2, w));
+        K(khip_div(ctx, n, w, s.delta));
+        rotate(k, true);                                                                                  // @kswap!(wₖ₋₃, wₖ₋₂)
+      }
+      if (k >= 2) K(khip_axpy(ctx, n, s.psi, w, y));
+      K(khip_dot(ctx, n, r.u, r.u, &s.uu));                                                               // kdotr(n, uₖ, uₖ), :398
+    }
+    K(L.shift(pq));                                                                                       // :410-418
+    bilqr_step_c(s, vq, q_norm, 0.0, k);            // ‖uₖ₊₁‖² is not carried here: the next iteration takes its own kdotr
+    return KHIP_OK;
+  }
+};
 
 // the first bytes of `full` that fit `cap` (with the terminator), cut at a UTF-8 character boundary
 void copy_status(char *dst, size_t cap, const std::string &full) {
@@ -263,14 +338,8 @@ int khip_bilqr_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_bilqr_
   KHIP_REQUIRE(m == n, "Systems must be square");
   khip_bilqr_workspace *ws = new khip_bilqr_workspace();
   ws->ctx = ctx; ws->m = m; ws->n = n;
-  (void)take_alloc_seconds();
-  // uₖ₋₁, uₖ, q, vₖ₋₁, vₖ, p, x, y, d̅, wₖ₋₃, wₖ₋₂ allocated; Δx, Δy stay empty until a warm start (src/krylov_workspaces.jl, BilqrWorkspace)
-  int rc = KHIP_OK;
-  for (double **slot : {&ws->u_prev, &ws->u, &ws->q, &ws->v_prev, &ws->v, &ws->p, &ws->x, &ws->y, &ws->dbar, &ws->w_prev3,
-                        &ws->w_prev2})
-    if (!rc) rc = alloc_vec(ctx, n, slot);
+  const int rc = ws_create_core(ws, kVectors);
   if (rc) { khip_bilqr_workspace_destroy(ws); return rc; }
-  ws->box.st.allocation_timer = take_alloc_seconds();
   *out = ws;
   return KHIP_OK;
 }
@@ -280,37 +349,21 @@ int khip_bilqr_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *u_pr
                                khip_bilqr_workspace **out) {
   KHIP_REQUIRE(ctx && out && m >= 0 && n >= 0, "bilqr_workspace_adopt: bad argument");
   KHIP_REQUIRE(m == n, "Systems must be square");
-  KHIP_REQUIRE(n == 0 || (u_prev && u && q && v_prev && v && p && x && y && dbar && w_prev3 && w_prev2),
-               "bilqr_workspace_adopt: u_prev, u, q, v_prev, v, p, x, y, dbar, w_prev3, w_prev2 must be device vectors of n entries");
-  const double *all[11] = {u_prev, u, q, v_prev, v, p, x, y, dbar, w_prev3, w_prev2};
-  for (int i = 0; i < 11; ++i)
-    for (int j = i + 1; j < 11; ++j)
-      KHIP_REQUIRE(n == 0 || all[i] != all[j],
-                   "bilqr_workspace_adopt: u_prev, u, q, v_prev, v, p, x, y, dbar, w_prev3, w_prev2 must be distinct");
   khip_bilqr_workspace *ws = new khip_bilqr_workspace();
   ws->ctx = ctx; ws->m = m; ws->n = n;
-  ws->u_prev = u_prev; ws->u = u; ws->q = q; ws->v_prev = v_prev; ws->v = v; ws->p = p; ws->x = x; ws->y = y; ws->dbar = dbar;
-  ws->w_prev3 = w_prev3; ws->w_prev2 = w_prev2;
-  for (const double *ptr : all) ws->borrowed.add(ptr);
+  const int rc = ws_adopt_core(ws, kVectors, "bilqr_workspace_adopt", {u_prev, u, q, v_prev, v, p, x, y, dbar, w_prev3, w_prev2});
+  if (rc) { delete ws; return rc; }
   *out = ws;
   return KHIP_OK;
 }
 
 int khip_bilqr_workspace_adopt_vector(khip_bilqr_workspace *ws, const char *name, double *ptr) {
-  KHIP_REQUIRE(ws && name, "bilqr_workspace_adopt_vector: null argument");
-  using S = NamedSlot;
-  return adopt_named(ws->ctx, ws->borrowed, {{"u_prev", &ws->u_prev, S::Fixed}, {"u", &ws->u, S::Fixed}, {"q", &ws->q, S::Fixed},
-                     {"v_prev", &ws->v_prev, S::Fixed}, {"v", &ws->v, S::Fixed}, {"p", &ws->p, S::Fixed}, {"x", &ws->x, S::Fixed},
-                     {"y", &ws->y, S::Fixed}, {"dbar", &ws->dbar, S::Fixed}, {"w_prev3", &ws->w_prev3, S::Fixed},
-                     {"w_prev2", &ws->w_prev2, S::Fixed}, {"dx", &ws->dx, S::Optional}, {"dy", &ws->dy, S::Optional}},
-                     "bilqr_workspace_adopt_vector", "vector", name, ptr);
+  return ws_adopt_vector(ws, kVectors, "bilqr_workspace_adopt_vector", name, ptr);
 }
 
 int khip_bilqr_workspace_destroy(khip_bilqr_workspace *ws) {
   if (!ws) return KHIP_OK;
-  for (double *ptr : {ws->u_prev, ws->u, ws->q, ws->v_prev, ws->v, ws->p, ws->x, ws->y, ws->dbar, ws->w_prev3, ws->w_prev2, ws->dx,
-                      ws->dy})
-    free_unless_borrowed(ws->ctx, ws->borrowed, ptr);
+  ws_free_vectors(ws, kVectors);
   ws->loop.release();
   delete ws;
   return KHIP_OK;
@@ -359,60 +412,33 @@ int khip_test_bilqr_status(int mask, char *cut96, const char **full) {
   return KHIP_OK;
 }
 int khip_bilqr_last_path(khip_bilqr_workspace *ws) { return ws ? ws->box.path : -1; }
-double *khip_bilqr_vector(khip_bilqr_workspace *ws, const char *name) {
-  if (!ws || !name) return nullptr;
-  struct { const char *k; double *p; } tab[] = {{"u_prev", ws->u_prev}, {"u", ws->u}, {"q", ws->q}, {"v_prev", ws->v_prev},
-                                                {"v", ws->v}, {"p", ws->p}, {"x", ws->x}, {"y", ws->y}, {"dbar", ws->dbar},
-                                                {"w_prev3", ws->w_prev3}, {"w_prev2", ws->w_prev2}, {"dx", ws->dx}, {"dy", ws->dy}};
-  for (auto &e : tab) if (strcmp(e.k, name) == 0) return e.p;
-  return nullptr;
-}
-size_t khip_bilqr_workspace_bytes(khip_bilqr_workspace *ws) {
-  if (!ws) return 0;
-  size_t cnt = 0;
-  for (double *ptr : {ws->u_prev, ws->u, ws->q, ws->v_prev, ws->v, ws->p, ws->x, ws->y, ws->dbar, ws->w_prev3, ws->w_prev2, ws->dx,
-                      ws->dy})
-    cnt += ptr ? 1 : 0;
-  return cnt * sizeof(double) * (size_t)ws->n;
-}
+double *khip_bilqr_vector(khip_bilqr_workspace *ws, const char *name) { return ws_vector(ws, kVectors, name); }
+size_t khip_bilqr_workspace_bytes(khip_bilqr_workspace *ws) { return ws_bytes(ws, kVectors); }
 
 int khip_bilqr_solve(khip_bilqr_workspace *ws, const khip_operator *A, const khip_operator *At, const double *b, const double *c,
                      const khip_options *opts_in, const khip_bilqr_params *params_in) {
   KHIP_REQUIRE(ws && A && b, "bilqr_solve: null argument");
-  khip_ctx *ctx = ws->ctx;
-  const khip_options o = opts_in ? *opts_in : khip_default_options();
   const khip_bilqr_params prm = params_in ? *params_in : khip_bilqr_default_params();
-  const double t0 = now_s();
-  const double timemax = timemax_of(o);
-  const int64_t n = ws->n;
+  BiLanczos<Bilqr> L(ws, A, At, nullptr, nullptr, nullptr, nullptr, opts_in);          // no M, no N
+  khip_ctx *ctx = L.ctx;
+  const khip_options &o = L.o;
+  const int64_t n = L.n;
+  BilqrDevState &s = L.s;
   khip_stats *st = &ws->box.st;
   const double atol = tol_or_default(o.atol), rtol = tol_or_default(o.rtol);
-  const int verbose = o.verbose;
-  const bool history = o.history != 0;
-  (void)take_alloc_seconds();
 
-  if (!At) return ws->box.fail(KHIP_ERR_INVALID, "bilqr_solve: At (the adjoint of A) is required");
-  if (!c) return ws->box.fail(KHIP_ERR_INVALID, "bilqr_solve: c (the right-hand side of the dual system) is required");
-  for (const khip_operator *op : {A, At}) {                                                              // :122-123
-    if (!(op->csr && !op->apply)) continue;
-    int64_t am, an;
-    khip_csr_shape(op->csr, &am, &an, nullptr);
-    if (am != ws->m || (an != ws->n && !op->csr->dist)) {             // a row-partitioned handle counts global columns
-      char msg[160];
-      snprintf(msg, sizeof(msg), "(workspace.m, workspace.n) = (%lld, %lld) is inconsistent with size(A) = (%lld, %lld)",
-               (long long)ws->m, (long long)ws->n, (long long)am, (long long)an);
-      return ws->box.fail(KHIP_ERR_INVALID, msg);
-    }
-  }
-  if (ws->m != ws->n) return ws->box.fail(KHIP_ERR_INVALID, "Systems must be square");
-  if (verbose > 0) klogf(o.log_fd, "BILQR: systems of size %lld\n", (long long)n);                       // :127
+  if (int rc = L.check("bilqr", "Systems must be square",                                                  // :122-123
+                       c ? nullptr : "bilqr_solve: c (the right-hand side of the dual system) is required"))
+    return rc;
+  if (o.verbose > 0) klogf(o.log_fd, "BILQR: systems of size %lld\n", (long long)n);                     // :127
   const bool warm_start = ws->warm_start;
   ws->box.reset();
   ws->residuals_dual.clear();
   ws->status = "unknown";
   ws->solved_primal = ws->solved_dual = 0;
-  double *x = ws->x, *y = ws->y, *dbar = ws->dbar, *q = ws->q, *p = ws->p;
-  double *v = ws->v, *v_prev = ws->v_prev, *u = ws->u, *u_prev = ws->u_prev, *w3 = ws->w_prev3, *w2 = ws->w_prev2;
+  double *x = L.pol.x = ws->x, *y = L.pol.y = ws->y, *dbar = L.pol.dbar = ws->dbar;
+  L.pol.w3 = ws->w_prev3;
+  L.pol.w2 = ws->w_prev2;
   auto finish = [&](const char *status, int solved_primal, int solved_dual) {
     ws->status = status;
     ws->solved_primal = solved_primal;
@@ -420,43 +446,38 @@ int khip_bilqr_solve(khip_bilqr_workspace *ws, const khip_operator *A, const khi
     st->solved = (solved_primal && solved_dual) ? 1 : 0;
     st->inconsistent = 0;
     copy_status(st->status, sizeof(st->status), ws->status);
-    st->timer = now_s() - t0;
-    ws->warm_start = false;
-    st->allocation_timer += take_alloc_seconds();
-    ws->box.publish();
+    L.finish();
   };
 
   // set-up, the same primitives on every path (:144-217)
   const double *r0 = b, *s0 = c;
   if (warm_start) {
-    K(apply_op(ctx, A, ws->dx, q));
-    K(khip_axpby(ctx, n, 1.0, b, -1.0, q));
-    K(apply_op(ctx, At, ws->dy, p));
-    K(khip_axpby(ctx, n, 1.0, c, -1.0, p));
-    r0 = q;
-    s0 = p;
+    K(apply_op(ctx, A, ws->dx, L.r.q));
+    K(khip_axpby(ctx, n, 1.0, b, -1.0, L.r.q));
+    K(apply_op(ctx, At, ws->dy, L.r.p));
+    K(khip_axpby(ctx, n, 1.0, c, -1.0, L.r.p));
+    r0 = L.r.q;
+    s0 = L.r.p;
   }
   K(khip_fill(ctx, n, x, 0.0));
   double bNorm, cNorm;
   K(khip_nrm2(ctx, n, r0, &bNorm));
   K(khip_fill(ctx, n, y, 0.0));
   K(khip_nrm2(ctx, n, s0, &cNorm));
-  const int64_t itmax = o.itmax == 0 ? 2 * global_rows(ctx, A, n) : o.itmax;
-  if (history) {
+  L.itmax = o.itmax == 0 ? 2 * global_rows(ctx, A, n) : o.itmax;
+  if (L.history) {
     ws->box.push(bNorm);
     ws->residuals_dual.push_back(cNorm);
   }
-  BilqrDevState s;
-  memset(&s, 0, sizeof(s));
   s.bNorm = bNorm;
   s.eps_L = atol + rtol * bNorm;
   s.eps_Q = atol + rtol * cNorm;
   s.sNorm = cNorm;
   s.rNorm_lq = bNorm;
   ws->box.path = o.fused ? 1 : 0;
-  if (verbose > 0) {
+  if (o.verbose > 0) {
     klogf(o.log_fd, "%5s  %s  %s  %5s\n", "k", "   \xe2\x80\x96r\xe2\x82\x96\xe2\x80\x96", "   \xe2\x80\x96s\xe2\x82\x96\xe2\x80\x96", "timer");
-    if (kdisplay(0, verbose)) klogf(o.log_fd, "%5d  %7.1e  %7.1e  %.2fs\n", 0, bNorm, cNorm, now_s() - t0);
+    if (kdisplay(0, o.verbose)) klogf(o.log_fd, "%5d  %7.1e  %7.1e  %.2fs\n", 0, bNorm, cNorm, now_s() - L.t0);
   }
   double cb;
   K(khip_dot(ctx, n, s0, r0, &cb));
@@ -469,186 +490,27 @@ int khip_bilqr_solve(khip_bilqr_workspace *ws, const khip_operator *A, const khi
     finish("Breakdown b\xe1\xb4\xb4" "c = 0", 0, 0);
     return KHIP_OK;
   }
-  s.beta = std::sqrt(std::fabs(cb));
-  s.gamma = cb / s.beta;
-  K(khip_fill(ctx, n, v_prev, 0.0));
-  K(khip_fill(ctx, n, u_prev, 0.0));
-  K(khip_divcopy(ctx, n, v, r0, s.beta));
-  K(khip_divcopy(ctx, n, u, s0, s.gamma));
+  K(L.start(cb, r0, s0));
   s.cs = s.cs_prev = -1.0;
   K(khip_fill(ctx, n, dbar, 0.0));
   s.norm_v = bNorm / s.beta;
-  K(khip_fill(ctx, n, w3, 0.0));
-  K(khip_fill(ctx, n, w2, 0.0));
+  K(khip_fill(ctx, n, L.pol.w3, 0.0));
+  K(khip_fill(ctx, n, L.pol.w2, 0.0));
   s.transfer_to_bicg = prm.transfer_to_bicg ? 1 : 0;
   s.stop_seq = kSeqNever;
   s.solved_lq = (bNorm == 0) ? 1 : 0;                                                                    // :207-212
   s.solved_primal = s.solved_lq;
   s.solved_dual = (cNorm == 0) ? 1 : 0;
-  bool tired = 0 >= itmax, user_exit = false, overtimed = false;
-  int64_t iter = 0;
-  auto running = [&] { return !((s.solved_primal && s.solved_dual) || tired || s.breakdown || user_exit || overtimed); };
-  auto products = [&](const double *vk, const double *uk, double *qk, double *pk) -> int {              // :227-228
-    KHIP_TRY(apply_op_no_epilogue(ctx, A, vk, qk));
-    KHIP_TRY(apply_op_no_epilogue(ctx, At, uk, pk));
-    return KHIP_OK;
-  };
-  // the end of an iteration on the host-driven loops (:327, :402, :433-441); the flags are those before the iteration's tests
-  auto host_tail = [&](int64_t k, bool primal_ran, bool dual_ran) {
-    if (history && primal_ran) ws->box.push(s.rNorm_lq);
-    if (history && dual_ran) ws->residuals_dual.push_back(s.sNorm);
-    if (o.callback) {
-      ws->box.publish();                          // the callback reads both histories
-      user_exit = o.callback(ws, o.callback_data) != 0;
-    }
-    tired = k >= itmax;
-    overtimed = time_limit_reached(ctx, now_s() - t0, timemax);
-    if (kdisplay(k, verbose)) verbose_row(o, k, s, t0);
-  };
 
-  const bool csr_pair = A->csr && !A->apply && At->csr && !At->apply;
-  const bool device_loop = o.fused >= 2 && csr_pair && !o.callback && verbose <= 0;
-  ws->box.path = (device_loop && running()) ? 2 : (o.fused ? 1 : 0);   // a loop that never starts reports 1, as the early return does
+  K(L.iterate());                                                                                         // :219-442
 
-  if (ws->box.path == 0) {
-    // ---------------------------------------------------------------- the reference's primitive sequence (:219-442) ----
-    while (running()) {
-      const int64_t k = ++iter;
-      const bool primal = !s.solved_primal, dual = !s.solved_dual;
-      K(products(v, u, q, p));
-      K(khip_axpy(ctx, n, -s.gamma, v_prev, q));
-      K(khip_axpy(ctx, n, -s.beta, u_prev, p));
-      double uq;
-      K(khip_dot(ctx, n, u, q, &uq));
-      bilqr_step_a(s, uq);
-      K(khip_axpy(ctx, n, -s.alpha, v, q));
-      K(khip_axpy(ctx, n, -s.alpha, u, p));
-      double pq;
-      K(khip_dot(ctx, n, p, q, &pq));
-      bilqr_step_b(s, pq, k);
-      double vq = 0.0, q_norm = 0.0;
-      if (primal) {                                                                                       // :296-315
-        if (k == 1) {
-          K(khip_copy(ctx, n, dbar, v));
-        } else {
-          K(khip_axpy(ctx, n, s.zc, dbar, x));
-          K(khip_axpy(ctx, n, s.zs, v, x));
-          K(khip_axpby(ctx, n, s.neg_c, v, s.sn, dbar));
-        }
-        K(khip_dot(ctx, n, v, q, &vq));
-        K(khip_nrm2(ctx, n, q, &q_norm));
-      }
-      if (dual) {                                                                                         // :361-398
-        double *w = nullptr;
-        if (k == 2) {
-          w = w2;
-          K(khip_divcopy(ctx, n, w, u_prev, s.delta));
-        }
-        if (k >= 3) {
-          w = w3;
-          if (k >= 4) K(khip_scal(ctx, n, s.neg_eps3, w));
-          K(khip_axpy(ctx, n, 1.0, u_prev, w));
-          K(khip_axpy(ctx, n, s.neg_lambda2, w2, w));
-          K(khip_div(ctx, n, w, s.delta));
-          std::swap(w3, w2);                                                                              // @kswap!(wₖ₋₃, wₖ₋₂)
-        }
-        if (k >= 2) K(khip_axpy(ctx, n, s.psi, w, y));
-        K(khip_dot(ctx, n, u, u, &s.uu));                                                                 // kdotr(n, uₖ, uₖ), :398
-      }
-      K(khip_copy(ctx, n, v_prev, v));
-      K(khip_copy(ctx, n, u_prev, u));
-      if (pq != 0) {
-        K(khip_divcopy(ctx, n, v, q, s.beta_next));
-        K(khip_divcopy(ctx, n, u, p, s.gamma_next));
-      }
-      bilqr_step_c(s, vq, q_norm, 0.0, k);          // ‖uₖ₊₁‖² is not carried here: the next iteration takes its own kdotr
-      host_tail(k, primal, dual);
-    }
-  } else if (ws->box.path == 1) {
-    // ---------------------------------------------------------------- host-driven loop on the fused kernels ----------
-    K(ws->loop.alloc());
-    s.hist_p = s.hist_d = nullptr;
-    if (running()) K(khip_dot(ctx, n, u, u, &s.uu));                                                      // ‖u₁‖²
-    while (running()) {
-      const int64_t k = ++iter;
-      const bool primal = !s.solved_primal, dual = !s.solved_dual;
-      K(products(v, u, q, p));
-      K(ws->loop.upload(ctx, s));
-      int slot = take_slots(ctx, 1);
-      K(launch_p1(ctx, n, ws->loop.dev, v_prev, u_prev, u, q, p, slot));
-      double uq;
-      K(fetch_results(ctx, slot, 1, &uq));
-      bilqr_step_a(s, uq);
-      K(ws->loop.upload(ctx, s));
-      slot = take_slots(ctx, 1);
-      K(launch_p2(ctx, n, ws->loop.dev, v, u, q, p, slot));
-      double pq;
-      K(fetch_results(ctx, slot, 1, &pq));
-      bilqr_step_b(s, pq, k);
-      K(ws->loop.upload(ctx, s));
-      slot = take_slots(ctx, kP3Sums);
-      K(launch_p3(ctx, n, ws->loop.dev, x, dbar, y, w3, w2, k == 2 ? w2 : w3, v, u, u_prev, q, p, v_prev, u_prev,
-                  k < 4 ? (int)k : 4, slot));
-      double r[kP3Sums];
-      K(fetch_results(ctx, slot, kP3Sums, r));
-      std::swap(v, v_prev);                        // vₖ₋₁ <- vₖ ; vₖ <- vₖ₊₁ (:411-418) as a rotation of the roles
-      std::swap(u, u_prev);
-      if (dual && k >= 3) std::swap(w3, w2);       // wₖ₋₁ was written over wₖ₋₃ (:383-386)
-      bilqr_step_c(s, r[0], std::sqrt(r[1]), r[2], k);
-      host_tail(k, primal, dual);
-    }
-  } else {
-    // ---------------------------------------------------------------- device-resident loop -----------------------------
-    K(khip_dot(ctx, n, u, u, &s.uu));                                                                     // ‖u₁‖²
-    double *vc = v, *vp = v_prev, *uc = u, *up = u_prev, *wc3 = w3, *wc2 = w2;
-    auto step = [&](BilqrDevState *dev, long long j) {
-      const int64_t k = j + 1;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 1, EPI_NONE, nullptr};
-      int rc = spmv_any(ctx, A->csr, vc, q, -1);                                          // q = A vₖ
-      if (rc == KHIP_OK) rc = spmv_any(ctx, At->csr, uc, p, -1);                          // p = A' uₖ
-      if (rc != KHIP_OK) return rc;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 2, EPI_BILQR_A, dev};
-      int slot = take_slots(ctx, 1);
-      rc = launch_p1(ctx, n, dev, vp, up, uc, q, p, slot);                               // P1 ; u.q -> α
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-      if (rc != KHIP_OK) return rc;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 3, EPI_BILQR_B, dev};
-      slot = take_slots(ctx, 1);
-      rc = launch_p2(ctx, n, dev, vc, uc, q, p, slot);                                   // P2 ; p.q -> the LQ update
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-      if (rc != KHIP_OK) return rc;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 4, EPI_BILQR_C, dev};
-      slot = take_slots(ctx, kP3Sums);
-      rc = launch_p3(ctx, n, dev, x, dbar, y, wc3, wc2, k == 2 ? wc2 : wc3, vc, uc, up, q, p, vp, up, k < 4 ? (int)k : 4,
-                     slot);                                                               // P3 ; the three sums -> tests
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, kP3Sums);
-      ctx->ctl = SeqCtl{};
-      if (rc != KHIP_OK) return rc;
-      std::swap(vc, vp);
-      std::swap(uc, up);
-      if (k >= 3) std::swap(wc3, wc2);             // a dual side that is solved no longer touches either buffer
-      return KHIP_OK;
-    };
-    // a finite timemax: the first chunk is ONE iteration, so that a limit already used up stops after iteration 1 as the
-    // host-driven loop does
-    const DeviceLoopArgs loop_args{itmax, t0, timemax, history, {&ws->box.residuals, &ws->residuals_dual, nullptr},
-                                   timemax < 1e300 ? 1 : kDevChunk};
-    K(ws->loop.run(ctx, s, loop_args, step, &s, &overtimed));
-    iter = s.iter;
-    tired = iter >= itmax;
-    // the host rotated the roles for every iteration it enqueued; the device ran s.iter of them, and its dual block s.nhist_d
-    if (iter & 1) { std::swap(v, v_prev); std::swap(u, u_prev); }
-    if (s.nhist_d >= 3 && (s.nhist_d & 1)) std::swap(w3, w2);
-  }
-  ws->v = v; ws->v_prev = v_prev; ws->u = u; ws->u_prev = u_prev; ws->w_prev3 = w3; ws->w_prev2 = w2;
-  if (verbose > 0) klogf(o.log_fd, "\n");
   if (s.solved_cg) K(khip_axpy(ctx, n, s.zbar, dbar, x));                                                // :447-449
-  const char *status = status_of(s, tired, user_exit, overtimed);
+  const char *status = status_of(s, L.tired, L.user_exit, L.overtimed);
   if (warm_start) {                                                                                       // :472-473
     K(khip_axpy(ctx, n, 1.0, ws->dx, x));
     K(khip_axpy(ctx, n, 1.0, ws->dy, y));
   }
-  st->niter = (int)iter;
+  st->niter = (int)L.iter;
   finish(status, s.solved_primal ? 1 : 0, s.solved_dual ? 1 : 0);
   return KHIP_OK;
 }

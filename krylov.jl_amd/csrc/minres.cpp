@@ -225,6 +225,12 @@ struct khip_minres_workspace {
 
 namespace {
 
+// x, r1, r2, w1, w2, y come with the workspace; dx, v, npc_dir stay empty until needed (src/krylov_workspaces.jl:94-112)
+using W = khip_minres_workspace;
+constexpr WsVec<W> kVectors[] = {{"x", &W::x, Core},   {"r1", &W::r1, Core}, {"r2", &W::r2, Core},
+                                 {"w1", &W::w1, Core}, {"w2", &W::w2, Core}, {"y", &W::y, Core},
+                                 {"dx", &W::dx, Lazy}, {"v", &W::v, Lazy},   {"npc_dir", &W::npc_dir, Lazy}};
+
 struct Bufs {
   double *x, *r1, *r2, *y, *v, *w1, *w2;   // v == r2 when M = I
 };
@@ -257,13 +263,8 @@ int khip_minres_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, int window
   khip_minres_workspace *ws = new khip_minres_workspace();
   ws->ctx = ctx; ws->m = m; ws->n = n; ws->window = window;
   ws->err_vec.assign((size_t)window, 0.0);
-  (void)take_alloc_seconds();
-  // x, r1, r2, w1, w2, y allocated; dx, npc_dir, v stay empty until needed (src/krylov_workspaces.jl:94-112)
-  int rc = KHIP_OK;
-  for (double **slot : {&ws->x, &ws->r1, &ws->r2, &ws->w1, &ws->w2, &ws->y})
-    if (!rc) rc = alloc_vec(ctx, n, slot);
+  const int rc = ws_create_core(ws, kVectors);
   if (rc) { khip_minres_workspace_destroy(ws); return rc; }
-  ws->box.st.allocation_timer = take_alloc_seconds();
   *out = ws;
   return KHIP_OK;
 }
@@ -272,44 +273,28 @@ int khip_minres_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, int window,
                                 double *w2, double *y, khip_minres_workspace **out) {
   KHIP_REQUIRE(ctx && out && m >= 0 && n >= 0, "minres_workspace_adopt: bad argument");
   KHIP_REQUIRE(window >= 1, "minres_workspace_adopt: window must be positive");
-  KHIP_REQUIRE(n == 0 || (x && r1 && r2 && w1 && w2 && y), "minres_workspace_adopt: x, r1, r2, w1, w2, y must be device vectors of n entries");
-  const double *all[6] = {x, r1, r2, w1, w2, y};
-  for (int i = 0; i < 6; ++i)
-    for (int j = i + 1; j < 6; ++j)
-      KHIP_REQUIRE(n == 0 || all[i] != all[j], "minres_workspace_adopt: x, r1, r2, w1, w2, y must be distinct");
   khip_minres_workspace *ws = new khip_minres_workspace();
   ws->ctx = ctx; ws->m = m; ws->n = n; ws->window = window;
   ws->err_vec.assign((size_t)window, 0.0);
-  ws->x = x; ws->r1 = r1; ws->r2 = r2; ws->w1 = w1; ws->w2 = w2; ws->y = y;
-  for (const double *p : all) ws->borrowed.add(p);
+  const int rc = ws_adopt_core(ws, kVectors, "minres_workspace_adopt", {x, r1, r2, w1, w2, y});
+  if (rc) { delete ws; return rc; }
   *out = ws;
   return KHIP_OK;
 }
 
 int khip_minres_workspace_adopt_vector(khip_minres_workspace *ws, const char *name, double *ptr) {
-  KHIP_REQUIRE(ws && name, "minres_workspace_adopt_vector: null argument");
-  using S = NamedSlot;
-  return adopt_named(ws->ctx, ws->borrowed, {{"x", &ws->x, S::Fixed}, {"r1", &ws->r1, S::Fixed}, {"r2", &ws->r2, S::Fixed},
-                     {"w1", &ws->w1, S::Fixed}, {"w2", &ws->w2, S::Fixed}, {"y", &ws->y, S::Fixed}, {"dx", &ws->dx, S::Optional},
-                     {"v", &ws->v, S::Optional}, {"npc_dir", &ws->npc_dir, S::Optional}},
-                     "minres_workspace_adopt_vector", "vector", name, ptr);
+  return ws_adopt_vector(ws, kVectors, "minres_workspace_adopt_vector", name, ptr);
 }
 
 int khip_minres_workspace_destroy(khip_minres_workspace *ws) {
   if (!ws) return KHIP_OK;
-  for (double *p : {ws->dx, ws->x, ws->r1, ws->r2, ws->npc_dir, ws->w1, ws->w2, ws->y, ws->v}) free_unless_borrowed(ws->ctx, ws->borrowed, p);
+  ws_free_vectors(ws, kVectors);
   ws->loop.release();
   delete ws;
   return KHIP_OK;
 }
 
-int khip_minres_warm_start(khip_minres_workspace *ws, const double *x0) {
-  KHIP_REQUIRE(ws && x0, "minres_warm_start: null argument");
-  if (!ws->dx) KHIP_TRY(alloc_vec(ws->ctx, ws->n, &ws->dx));
-  if (x0 != ws->dx) KHIP_TRY(khip_copy(ws->ctx, ws->n, ws->dx, x0));
-  ws->warm_start = true;
-  return KHIP_OK;
-}
+int khip_minres_warm_start(khip_minres_workspace *ws, const double *x0) { return ws_warm_start(ws, x0, "minres_warm_start"); }
 
 double *khip_minres_solution(khip_minres_workspace *ws) { return ws ? ws->x : nullptr; }
 const khip_stats *khip_minres_stats(khip_minres_workspace *ws) { return ws ? &ws->box.st : nullptr; }
@@ -324,19 +309,8 @@ int khip_minres_histories(khip_minres_workspace *ws, const double **aresiduals, 
   *nacond = (int)ws->aconds.size();
   return KHIP_OK;
 }
-double *khip_minres_vector(khip_minres_workspace *ws, const char *name) {
-  if (!ws || !name) return nullptr;
-  struct { const char *k; double *p; } tab[] = {{"x", ws->x}, {"r1", ws->r1}, {"r2", ws->r2}, {"w1", ws->w1}, {"w2", ws->w2},
-                                                {"y", ws->y}, {"v", ws->v}, {"dx", ws->dx}, {"npc_dir", ws->npc_dir}};
-  for (auto &e : tab) if (strcmp(e.k, name) == 0) return e.p;
-  return nullptr;
-}
-size_t khip_minres_workspace_bytes(khip_minres_workspace *ws) {
-  if (!ws) return 0;
-  size_t cnt = 0;
-  for (double *p : {ws->dx, ws->x, ws->r1, ws->r2, ws->npc_dir, ws->w1, ws->w2, ws->y, ws->v}) cnt += p ? 1 : 0;
-  return cnt * sizeof(double) * (size_t)ws->n;
-}
+double *khip_minres_vector(khip_minres_workspace *ws, const char *name) { return ws_vector(ws, kVectors, name); }
+size_t khip_minres_workspace_bytes(khip_minres_workspace *ws) { return ws_bytes(ws, kVectors); }
 
 int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const khip_operator *M, const double *b,
                       const khip_options *opts_in, const khip_minres_params *params_in) {

@@ -106,11 +106,18 @@ struct NamedSlot {
   double **slot;
   Use use;
 };
+struct NamedSlots {   // a braced list at the call, or the array ws_adopt_vector fills from a workspace's vector table
+  const NamedSlot *b, *e;
+  NamedSlots(std::initializer_list<NamedSlot> l) : b(l.begin()), e(l.end()) {}
+  NamedSlots(const NamedSlot *tab, size_t n) : b(tab), e(tab + n) {}
+  const NamedSlot *begin() const { return b; }
+  const NamedSlot *end() const { return e; }
+};
 // name's slot <- ptr as a caller-owned vector (ptr == nullptr empties the slot); what the library had allocated there is
 // freed.  `Borrowed` is a set of pointers, so a pointer may sit in ONE slot only: a pointer that already is
 // another vector of the workspace (or of `basis`, named "V") is refused; handing a slot the pointer it already holds changes
 // nothing, in particular not who owns it.  fn / what: the entry point and "vector" / "panel", for the messages.
-int adopt_named(khip_ctx *ctx, Borrowed &b, std::initializer_list<NamedSlot> tab, const char *fn, const char *what,
+int adopt_named(khip_ctx *ctx, Borrowed &b, NamedSlots tab, const char *fn, const char *what,
                 const char *name, double *ptr, const std::vector<double *> *basis = nullptr) {
   std::string names, required;
   for (const NamedSlot &e : tab) {
@@ -134,6 +141,77 @@ int adopt_named(khip_ctx *ctx, Borrowed &b, std::initializer_list<NamedSlot> tab
   }
   set_error("%s: unknown %s '%s' (%s)", fn, what, name, names.c_str());
   return KHIP_ERR_INVALID;
+}
+
+// ---- one vector table per workspace type (minres!, bilq!, qmr!, bilqr!): the only place a workspace lists its vectors ----------
+// Core vectors are allocated by khip_*_workspace_create, handed over in the table's order by khip_*_workspace_adopt and fixed
+// for khip_*_workspace_adopt_vector; they come first.  Lazy vectors stay empty until a solve, a warm start or adopt_vector
+// fills them.  A workspace W has ctx, n, borrowed and box beside its vectors; `fn` is the entry point, for the messages.
+enum WsVecKind { Core, Lazy };
+template <class W>
+struct WsVec {
+  const char *k;
+  double *W::*slot;
+  WsVecKind kind;
+};
+template <class W, size_t N> std::string ws_core_names(const WsVec<W> (&tab)[N]) {
+  std::string names;
+  for (const WsVec<W> &e : tab) if (e.kind == Core) names += (names.empty() ? "" : ", ") + std::string(e.k);
+  return names;
+}
+template <class W, size_t N> int ws_create_core(W *ws, const WsVec<W> (&tab)[N]) {
+  (void)take_alloc_seconds();
+  for (const WsVec<W> &e : tab) if (e.kind == Core) KHIP_TRY(alloc_vec(ws->ctx, ws->n, &(ws->*e.slot)));
+  ws->box.st.allocation_timer = take_alloc_seconds();
+  return KHIP_OK;
+}
+template <class W, size_t N>
+int ws_adopt_core(W *ws, const WsVec<W> (&tab)[N], const char *fn, std::initializer_list<double *> ptrs) {
+  const std::string names = ws_core_names(tab);
+  bool all = true;
+  for (const double *p : ptrs) all = all && p;
+  KHIP_REQUIRE(ws->n == 0 || all, "%s: %s must be device vectors of n entries", fn, names.c_str());
+  for (const double *const *i = ptrs.begin(); i != ptrs.end(); ++i)
+    for (const double *const *j = i + 1; j != ptrs.end(); ++j)
+      KHIP_REQUIRE(ws->n == 0 || *i != *j, "%s: %s must be distinct", fn, names.c_str());
+  double *const *next = ptrs.begin();
+  for (const WsVec<W> &e : tab) {
+    if (e.kind != Core) continue;
+    KHIP_REQUIRE(next != ptrs.end(), "%s: fewer pointers than core vectors", fn);
+    ws->*e.slot = *next;
+    ws->borrowed.add(*next++);
+  }
+  return KHIP_OK;
+}
+template <class W, size_t N>
+int ws_adopt_vector(W *ws, const WsVec<W> (&tab)[N], const char *fn, const char *name, double *ptr) {
+  KHIP_REQUIRE(ws && name, "%s: null argument", fn);
+  NamedSlot slots[N];
+  for (size_t i = 0; i < N; ++i)
+    slots[i] = NamedSlot{tab[i].k, &(ws->*tab[i].slot), tab[i].kind == Core ? NamedSlot::Fixed : NamedSlot::Optional};
+  return adopt_named(ws->ctx, ws->borrowed, NamedSlots(slots, N), fn, "vector", name, ptr);
+}
+template <class W, size_t N> void ws_free_vectors(W *ws, const WsVec<W> (&tab)[N]) {
+  for (const WsVec<W> &e : tab) free_unless_borrowed(ws->ctx, ws->borrowed, ws->*e.slot);
+}
+template <class W, size_t N> double *ws_vector(W *ws, const WsVec<W> (&tab)[N], const char *name) {
+  if (!ws || !name) return nullptr;
+  for (const WsVec<W> &e : tab) if (strcmp(e.k, name) == 0) return ws->*e.slot;
+  return nullptr;
+}
+template <class W, size_t N> size_t ws_bytes(W *ws, const WsVec<W> (&tab)[N]) {
+  if (!ws) return 0;
+  size_t cnt = 0;
+  for (const WsVec<W> &e : tab) cnt += ws->*e.slot ? 1 : 0;
+  return cnt * sizeof(double) * (size_t)ws->n;
+}
+// khip_*_warm_start of the workspaces with one Δx (minres!, bilq!, qmr!): x0 == ws->dx only sets the flag
+template <class W> int ws_warm_start(W *ws, const double *x0, const char *fn) {
+  KHIP_REQUIRE(ws && x0, "%s: null argument", fn);
+  if (!ws->dx) KHIP_TRY(alloc_vec(ws->ctx, ws->n, &ws->dx));
+  if (x0 != ws->dx) KHIP_TRY(khip_copy(ws->ctx, ws->n, ws->dx, x0));
+  ws->warm_start = true;
+  return KHIP_OK;
 }
 
 // y = op x inside a sequence whose reductions carry epilogues: the product keeps the sequence number (it is skipped once the
