@@ -668,6 +668,32 @@ int khip_bilqr_last_path(khip_bilqr_workspace *ws);
 double           *khip_bilqr_vector(khip_bilqr_workspace *ws, const char *name);
 size_t            khip_bilqr_workspace_bytes(khip_bilqr_workspace *ws);   /* 11n doubles without warm start */
 
+/* ---- cgs! (src/cgs.jl:126-281), real Float64: square nonsymmetric systems by the conjugate gradient squared recurrence; transpose-
+ * free (no A'), two products with A per iteration.  CgsWorkspace (src/krylov_workspaces.jl): x, r, u, p, q, ts; Δx, yz and vw ("dx",
+ * "yz", "vw") stay empty until a warm start, N or M needs them.  options.variant != 0 is refused (there is no other recurrence);
+ * window, reorthogonalization and restart are ignored. */
+typedef struct khip_cgs_workspace khip_cgs_workspace;
+int khip_cgs_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_cgs_workspace **out);
+/* CgsWorkspace on the caller's six vectors; every pointer must be distinct.  adopt_vector names: "dx" (Δx: warm_start! fills it on the
+ * caller's side and hands it over, then khip_cgs_warm_start(ws, dx) only sets the flag), "yz" (needed with N), "vw" (needed with M) */
+int khip_cgs_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *x, double *r, double *u, double *p, double *q, double *ts,
+                             khip_cgs_workspace **out);
+int khip_cgs_workspace_adopt_vector(khip_cgs_workspace *ws, const char *name, double *ptr);
+int khip_cgs_workspace_destroy(khip_cgs_workspace *ws);
+int khip_cgs_warm_start(khip_cgs_workspace *ws, const double *x0);
+/* cgs!(ws, A, b; c, M, N, atol, rtol, itmax, timemax, verbose, history, callback).  c == NULL means c = b; M / N == NULL mean the
+ * identity.  m != n: KHIP_ERR_INVALID "System must be square".  Loops (khip_cgs_last_path): 2 = device-resident (A a CSR handle,
+ * M = N = I, no callback, verbose = 0), 1 = host-driven on the same kernels (same bits as 2), 0 = one launch per primitive
+ * (options.fused = 0). */
+int khip_cgs_solve(khip_cgs_workspace *ws, const khip_operator *A, const khip_operator *M, const khip_operator *N, const double *b,
+                   const double *c, const khip_options *opts);
+double           *khip_cgs_solution(khip_cgs_workspace *ws);
+const khip_stats *khip_cgs_stats(khip_cgs_workspace *ws);
+int khip_cgs_last_path(khip_cgs_workspace *ws);
+/* named work vectors: "x", "r", "u", "p", "q", "ts", "dx", "yz", "vw" (NULL while not allocated) */
+double           *khip_cgs_vector(khip_cgs_workspace *ws, const char *name);
+size_t            khip_cgs_workspace_bytes(khip_cgs_workspace *ws);   /* 6n doubles without M, N and warm start */
+
 int khip_gmres_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, int memory, khip_gmres_workspace **out);
 /* GmresWorkspace on the caller's x, w and basis V_host[0 .. memory) (device pointers in a HOST array; `V::Vector{S}`,
  * src/krylov_workspaces.jl:2857-2873).  adopt_vector names: "x", "w", "p", "q", "dx".  adopt_basis replaces the whole list

@@ -587,8 +587,59 @@ function Krylov.qmr!(ws::QmrWs, A::HIPCsr, b::HIPVector; c::HIPVector = b, M = I
   return ws
 end
 
+# ------------------------------------------------------------------------------------------------ cgs!  (src/cgs.jl:126-281)
+const CgsWs = CgsWorkspace{Float64,Float64,HIPVector}
+function cgs_handle(ws::CgsWs)
+  get!(HANDLES, ws) do
+    r = Ref{Ptr{Cvoid}}()
+    ck(ccall((:khip_cgs_workspace_adopt, lib), Cint,
+             (Ptr{Cvoid}, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Ptr{Cvoid}}),
+             CTX[].h, ws.m, ws.n, ws.x.ptr, ws.r.ptr, ws.u.ptr, ws.p.ptr, ws.q.ptr, ws.ts.ptr, r))
+    h = r[]
+    finalizer(_ -> ccall((:khip_cgs_workspace_destroy, lib), Cint, (Ptr{Cvoid},), h), ws)
+    h
+  end
+end
+cgs_adopt(h, name, v::HIPVector) = ck(ccall((:khip_cgs_workspace_adopt_vector, lib), Cint, (Ptr{Cvoid}, Cstring, Ptr{Cdouble}), h, name, dptr(v)))
+
+# Transpose-free: no A', and M and N are whatever the library applies (I, Jacobi, ILU(0)), as for bicgstab!.  The library rotates
+# no roles: after the solve every vector of the workspace holds what the reference's variable of that name holds.
+function Krylov.cgs!(ws::CgsWs, A::HIPCsr, b::HIPVector; c::HIPVector = b, M = I, N = I, ldiv::Bool = false,
+                     atol::Float64 = √eps(Float64), rtol::Float64 = √eps(Float64), itmax::Int = 0, timemax::Float64 = Inf,
+                     verbose::Int = 0, history::Bool = false, callback = nothing, iostream::IO = Krylov.kstdout, fused::Int = 2)
+  if ldiv || !native_precond(M) || !native_precond(N) || !native_log(verbose, iostream)
+    GENERIC_SOLVES[] += 1
+    return invoke(Krylov.cgs!, Tuple{CgsWs,Any,AbstractVector{Float64}}, ws, A, b; c, M, N, ldiv, atol, rtol, itmax, timemax,
+                  verbose, history, callback = callback === nothing ? (w -> false) : callback, iostream)
+  end
+  m, n = size(A)                                                                            # :132-135
+  (m == ws.m && n == ws.n) || error("(workspace.m, workspace.n) = ($(ws.m), $(ws.n)) is inconsistent with size(A) = ($m, $n)")
+  m == n || error("System must be square")
+  length(b) == m || error("Inconsistent problem size")
+  Krylov.allocate_if(M !== I, ws, :vw, HIPVector, ws.x)                                      # :148-149
+  Krylov.allocate_if(N !== I, ws, :yz, HIPVector, ws.x)
+  h = cgs_handle(ws)
+  for (name, v) in (("vw", ws.vw), ("yz", ws.yz), ("dx", ws.Δx))
+    cgs_adopt(h, name, v)
+  end
+  ws.warm_start && ck(ccall((:khip_cgs_warm_start, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h, ws.Δx.ptr))
+  sp = ccall((:khip_cgs_stats, lib), Ptr{Stats}, (Ptr{Cvoid},), h)
+  cbf, cbd, box = callback_args(user_callback(callback), ws, sp, history)
+  opts = Ref(Options(; atol, rtol, itmax, timemax, history, fused, verbose, log_fd = logfd(iostream), callback = cbf, callback_data = cbd))
+  opA = Ref(Operator(A))
+  rc = GC.@preserve ws A b c M N opts opA box ccall((:khip_cgs_solve, lib), Cint,
+                                                 (Ptr{Cvoid}, Ref{Operator}, Ptr{Operator}, Ptr{Operator}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Options}),
+                                                 h, opA, opref(M), opref(N), b.ptr, c.ptr, opts)
+  st = fill_stats!(ws.stats, sp, history)
+  NATIVE_SOLVES[] += 1;  LAST_PATH[] = ccall((:khip_cgs_last_path, lib), Cint, (Ptr{Cvoid},), h)
+  ws.warm_start = false
+  finish_callback(box)
+  rc == 0 || failed(st)
+  return ws
+end
+
 # ------------------------------------------------------------------------------------------------ bilqr!  (src/bilqr.jl:116-484)
-struct BilqrParams                  # khip_bilqr_params: transfer_to_bicg
+struct BilqrParams                 # khip_bilqr_params: transfer_to_bicg
   transfer_to_bicg::Cint
 end
 const BilqrWs = BilqrWorkspace{Float64,Float64,HIPVector}

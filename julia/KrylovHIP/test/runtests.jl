@@ -248,6 +248,8 @@ end
     x, y, stats = native(2) do; bilqr(U_gpu, S(bu_cpu), S(bu_cpu)); end   # one process for A x = b and A' y = c
     @test norm(bu_cpu - U_cpu * Vector(x)) ≤ 1e-5 * norm(bu_cpu) && norm(bu_cpu - U_cpu' * Vector(y)) ≤ 1e-5 * norm(bu_cpu)
     @test U_gpu' === At
+    x, stats = native(2) do; cgs(U_gpu, S(bu_cpu)); end              # transpose-free: no A'
+    @test norm(bu_cpu - U_cpu * Vector(x)) ≤ 1e-5 * norm(bu_cpu)
   end
 
   @testset "solver -- $FC" begin                                     # test/gpu/gpu.jl test_solver
@@ -264,3 +266,4 @@ end
 end
 
 include("bilqr.jl")                                                  # bilqr! against the generic method, its breakdowns and statuses
+include("cgs.jl")                                                    # cgs! against the generic method, its endings and breakdowns

@@ -281,6 +281,18 @@ SIGNATURES = {
     "khip_qmr_last_path": (_int, [_vp]),
     "khip_qmr_vector": (_vp, [_vp, C.c_char_p]),
     "khip_qmr_workspace_bytes": (_sz, [_vp]),
+    "khip_cgs_workspace_create": (_int, [_vp, _i64, _i64, c_void_pp]),
+    "khip_cgs_workspace_adopt": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, c_void_pp]),
+    "khip_cgs_workspace_adopt_vector": (_int, [_vp, C.c_char_p, _vp]),
+    "khip_cgs_workspace_destroy": (_int, [_vp]),
+    "khip_cgs_warm_start": (_int, [_vp, _vp]),
+    "khip_cgs_solve": (_int, [_vp, C.POINTER(COperator), C.POINTER(COperator), C.POINTER(COperator), _vp, _vp,
+                              C.POINTER(COptions)]),
+    "khip_cgs_solution": (_vp, [_vp]),
+    "khip_cgs_stats": (C.POINTER(CStats), [_vp]),
+    "khip_cgs_last_path": (_int, [_vp]),
+    "khip_cgs_vector": (_vp, [_vp, C.c_char_p]),
+    "khip_cgs_workspace_bytes": (_sz, [_vp]),
     "khip_bilqr_default_params": (CBilqrParams, []),
     "khip_bilqr_workspace_create": (_int, [_vp, _i64, _i64, c_void_pp]),
     "khip_bilqr_workspace_adopt": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_void_pp]),
@@ -1640,6 +1652,13 @@ class QmrWorkspace(_BiLanczosWorkspace):
     VECTORS = ("u_prev", "u", "q", "v_prev", "v", "p", "x", "w_prev2", "w_prev")
 
 
+class CgsWorkspace(_BiLanczosWorkspace):
+    """CgsWorkspace(m, n, S) (src/krylov_workspaces.jl): x, r, u, p, q, ts; Δx, yz, vw stay empty until needed.  cgs! rotates no
+    roles: every name keeps its buffer."""
+    _prefix = "cgs"
+    VECTORS = ("x", "r", "u", "p", "q", "ts")
+
+
 class BilqrWorkspace(_BiLanczosWorkspace):
     """BilqrWorkspace(m, n, S) (src/krylov_workspaces.jl:1818-1836): uₖ₋₁, uₖ, q, vₖ₋₁, vₖ, p, x, y, d̅, wₖ₋₃, wₖ₋₂; Δx and Δy stay empty
     until a warm start."""
@@ -1729,6 +1748,20 @@ def bicgstab_(ws: BicgstabWorkspace, A, b: DeviceVector, c: DeviceVector | None 
     rc = lib().khip_bicgstab_solve(ws._h, _make_operator(ws.ctx, A, ws.n, keep),
                                    _make_operator(ws.ctx, M, ws.n, keep), _make_operator(ws.ctx, N, ws.n, keep),
                                    _p(b), _p(c), C.byref(opts))
+    return _finish(ws, rc)
+
+
+def cgs_(ws: CgsWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, M=None, N=None, **kw):
+    """cgs!(workspace, A, b; c, M, N, ldiv, atol, rtol, itmax, timemax, verbose, history, callback, iostream)
+    (src/cgs.jl:126-281).  Returns the workspace."""
+    keep = []
+    if len(b) != ws.n:
+        raise KhipError(-1, "Inconsistent problem size")                                  # src/cgs.jl:135
+    ws._allocate_if(M is not None, "vw")                                                # src/cgs.jl:148-149
+    ws._allocate_if(N is not None, "yz")
+    opts = _make_options(keep=keep, ws=ws, **kw)
+    rc = lib().khip_cgs_solve(ws._h, _make_operator(ws.ctx, A, ws.n, keep), _make_operator(ws.ctx, M, ws.n, keep),
+                              _make_operator(ws.ctx, N, ws.n, keep), _p(b), _p(c), C.byref(opts))
     return _finish(ws, rc)
 
 
@@ -1879,6 +1912,8 @@ FORWARDED_DEFAULTS = {
                  timemax=math.inf, verbose=0, history=False, callback=default_callback, iostream=None),
     "qmr": dict(c=None, M=None, N=None, ldiv=False, atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0, timemax=math.inf, verbose=0,
                 history=False, callback=default_callback, iostream=None),
+    "cgs": dict(c=None, M=None, N=None, ldiv=False, atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0, timemax=math.inf, verbose=0,
+                history=False, callback=default_callback, iostream=None),
     "bilqr": dict(transfer_to_bicg=True, atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0, timemax=math.inf, verbose=0, history=False,
                   callback=default_callback, iostream=None),
 }
@@ -1903,7 +1938,7 @@ def krylov_workspace(method: str, *args, ctx: Context | None = None, **kw):
     """krylov_workspace(Val(method), m, n, S; memory) / (Val(method), A, b; memory) (src/interface.jl:117-141, 237-244)."""
     cls = {"cg": CgWorkspace, "gmres": GmresWorkspace, "bicgstab": BicgstabWorkspace, "block_gmres": BlockGmresWorkspace,
            "minres": MinresWorkspace, "cg_lanczos_shift": CgLanczosShiftWorkspace, "bilq": BilqWorkspace,
-           "qmr": QmrWorkspace, "bilqr": BilqrWorkspace}[method]
+           "qmr": QmrWorkspace, "bilqr": BilqrWorkspace, "cgs": CgsWorkspace}[method]
     if method == "cg_lanczos_shift":                                            # (A, b, nshifts) / (m, n, nshifts)
         if isinstance(args[1], DeviceVector):
             A, b, nshifts = args
@@ -2004,6 +2039,11 @@ def bilq(A, b: DeviceVector, x0=None, **kw):
 def qmr(A, b: DeviceVector, x0=None, **kw):
     """Out-of-place qmr(A, b[, x0]; kwargs...) -> (x, stats, workspace) (src/qmr.jl:124-132); A' is taken once and kept on A."""
     return krylov_solve("qmr", A, b, x0, **kw)
+
+
+def cgs(A, b: DeviceVector, x0=None, **kw):
+    """Out-of-place cgs(A, b[, x0]; kwargs...) -> (x, stats, workspace) (src/cgs.jl:126-134)."""
+    return krylov_solve("cgs", A, b, x0, **kw)
 
 
 def bilqr(A, b: DeviceVector, c: DeviceVector, x0=None, y0=None, **kw):
@@ -2474,6 +2514,6 @@ def block_gmres(A, B, X0=None, ctx=None, **kw):
 
 _INPLACE.update({CgWorkspace: ("cg", cg_), GmresWorkspace: ("gmres", gmres_), BicgstabWorkspace: ("bicgstab", bicgstab_),
                  BlockGmresWorkspace: ("block_gmres", block_gmres_), MinresWorkspace: ("minres", minres_), BilqWorkspace: ("bilq", bilq_),
-                 QmrWorkspace: ("qmr", qmr_),
+                 QmrWorkspace: ("qmr", qmr_), CgsWorkspace: ("cgs", cgs_),
                  BilqrWorkspace: ("bilqr", bilqr_),
                  CgLanczosShiftWorkspace: ("cg_lanczos_shift", cg_lanczos_shift_)})

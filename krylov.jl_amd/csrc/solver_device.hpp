@@ -17,7 +17,7 @@ namespace khip {
 enum Epilogue { EPI_NONE = 0, EPI_CG_STEP1 = 1, EPI_CG_STEP2 = 2, EPI_BICG_A = 3, EPI_BICG_B = 4, EPI_BICG_C = 5, EPI_CGCG = 6,
                EPI_MINRES_A = 7, EPI_MINRES_B = 8, EPI_MINRES_C = 9, EPI_LZSHIFT_A = 10, EPI_LZSHIFT_B = 11,
                EPI_BILQ_A = 12, EPI_BILQ_B = 13, EPI_BILQ_C = 14, EPI_QMR_A = 15, EPI_QMR_B = 16, EPI_QMR_C = 17,
-               EPI_BILQR_A = 18, EPI_BILQR_B = 19, EPI_BILQR_C = 20 };
+               EPI_BILQR_A = 18, EPI_BILQR_B = 19, EPI_BILQR_C = 20, EPI_CGS_A = 21, EPI_CGS_B = 22 };
 
 struct CgDevState {
   double gamma;        // r.z of the current iterate              (src/cg.jl:162, 257)
@@ -612,6 +612,41 @@ __host__ __device__ inline bool bilqr_step_c(BilqrDevState &s, double vq, double
   return (s.solved_primal && s.solved_dual) || s.breakdown;
 }
 
+// cgs! (src/cgs.jl:126-281), real Float64: the two scalars of the recurrence and the stopping tests.  As for qmr!: the same two steps
+// run on the host (loops 0 and 1) and as the epilogues of the two reductions of an iteration (device-resident loop), so loops 1 and 2
+// produce the same bits.
+struct CgsDevState {
+  double rho;          // ρₖ = ⟨r̅₀, rₖ⟩                                  (:185, :238)
+  double alpha;        // αₖ = ρₖ / σₖ: P1 and P2                        (:221)
+  double beta;         // βₖ = ρₖ₊₁ / ρₖ: P3                             (:231)
+  double rNorm;        // ‖rₖ‖                                          (:244)
+  double eps_tol;      // ε = atol + rtol ‖r₀‖                          (:199)
+  long long stop_seq, iter, hist_base, hist_cap;
+  double *hist;        // device history window (null: no history)
+  int solved, breakdown;
+};
+
+// after σₖ = ⟨r̅₀, M⁻¹AN⁻¹pₖ⟩ (:220-221)
+__host__ __device__ inline void cgs_step_a(CgsDevState &s, double sigma) { s.alpha = s.rho / sigma; }
+
+// after ρₖ₊₁ = ⟨r̅₀, rₖ₊₁⟩ and ‖rₖ₊₁‖² (:230-231, :238-256): β, ρ, the history entry and the tests in the reference's order; true when
+// the loop stops (tired / overtimed / the callback are the driver's).  The u and p updates of this iteration (:232-235) still run.
+__host__ __device__ inline bool cgs_step_b(CgsDevState &s, double rho_next, double rr, long long k) {
+  s.beta = rho_next / s.rho;
+  s.rho = rho_next;
+  s.rNorm = sqrt(rr);
+  if (s.hist) {
+    const long long idx = k - 1 - s.hist_base;
+    if (idx >= 0 && idx < s.hist_cap) s.hist[idx] = s.rNorm;
+  }
+  const bool resid_decrease_mach = (s.rNorm + 1.0 <= 1.0);
+  const bool resid_decrease_lim = (s.rNorm <= s.eps_tol);
+  s.solved = (resid_decrease_lim || resid_decrease_mach) ? 1 : 0;
+  s.breakdown = (s.alpha == 0.0 || s.alpha != s.alpha) ? 1 : 0;
+  s.iter = k;
+  return s.solved || s.breakdown;
+}
+
 __device__ __forceinline__ bool seq_skip(const long long *stop_seq, long long seq) {
   return stop_seq != nullptr && seq >= *stop_seq;
 }
@@ -746,6 +781,11 @@ __device__ inline void solver_epilogue(int epi, void *state, const double *v, lo
     st->rho = next_rho;
     st->iter = k;
     if (solved || breakdown) st->stop_seq = seq + 2;   // the p update of this iteration (seq + 1) still runs (:236-237)
+  } else if (epi == EPI_CGS_A) {                   // v[0] = c.ts                src/cgs.jl:220-221
+    cgs_step_a(*static_cast<CgsDevState *>(state), v[0]);
+  } else if (epi == EPI_CGS_B) {                   // v = (c.r, r.r)             :230-256
+    CgsDevState *st = static_cast<CgsDevState *>(state);
+    if (cgs_step_b(*st, v[0], v[1], st->iter + 1)) st->stop_seq = seq + 2;   // P3 of this iteration (seq + 1) still runs (:232-235)
   }
 }
 
