@@ -135,7 +135,11 @@ int khip_csr_sell_narrow(const khip_csr *A, int *narrow);
  * rows of at most 64 entries and at most 255 distinct entries -- pairs (column - row, bit pattern of the value) -- keeps one byte
  * per entry (the rank of its pair, ascending (offset, value bits as unsigned); 0xFF = no entry) and no values in its slices:
  * 8 B per row of at most 8 entries, ceil(L / 8) words padded to an even count beyond.  khip_csr_sell_info reports this copy.
- * ctx option "spmv_sell_entries": 1 (default) = handles of at least 2^22 entries, 2 = whenever the handle qualifies, 0 = never. */
+ * ctx option "spmv_sell_entries": 1 (default) = handles of at least 2^22 entries, 2 = whenever the handle qualifies, 0 = never.
+ * ctx option "spmv_sell_persist": how the entry-coded product is launched.  1 (default) = on handles of one code word per row, where
+ * the loop-free launch would have more workgroups than eight rounds of what the device holds at once, that many long-lived workgroups
+ * walk the loop-free launch's workgroups, strided (same rows, same reduction partials: every result keeps its bits); 0 = the loop-free
+ * launch always; G > 1 = exactly min(G, workgroups of the loop-free launch) long-lived workgroups on every entry-coded handle. */
 int khip_csr_sell_entries(const khip_csr *A, int *pairs);
 /* The same for the int32 column stream -- operators that are not coded (more than 2048 diagonals, fewer than 4 M entries under
  * "spmv_codes" = 1, or "spmv_codes" = 0) with short rows (the staged kernel's operators: at most 12 entries per row on average):

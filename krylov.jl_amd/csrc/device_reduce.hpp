@@ -144,15 +144,19 @@ struct RedArgs {
 };
 
 // Streaming-kernel side: every wave folds its lanes and stores one partial per output.
+// ... into the slots of workgroup `blk` of a loop-free launch: a long-lived workgroup that walks several such (virtual) workgroups
+// publishes each one's partials where that workgroup would have stored them, so the finish kernel folds the same numbers in the same order
 template <int NOUT>
-__device__ __forceinline__ void wave_publish(dd (&acc)[NOUT], const RedArgs &ra) {
-  const int64_t wid = ra.wave_offset + (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+__device__ __forceinline__ void wave_publish_at(dd (&acc)[NOUT], const RedArgs &ra, int64_t blk) {
+  const int64_t wid = ra.wave_offset + blk * (blockDim.x >> 6) + (threadIdx.x >> 6);
 #pragma unroll
   for (int o = 0; o < NOUT; ++o) {
     dd r = wave_reduce(acc[o]);
     if ((threadIdx.x & 63) == kResultLane) ra.wave_partials[(size_t)o * ra.cap + wid] = r;
   }
 }
+template <int NOUT>
+__device__ __forceinline__ void wave_publish(dd (&acc)[NOUT], const RedArgs &ra) { wave_publish_at<NOUT>(acc, ra, (int64_t)blockIdx.x); }
 
 // The same for kernels whose workgroup is one tile and has LDS to spare at its end (the SpMV windows): the four waves leave
 // their lanes' partials in LDS and ONE wave folds all 256 (lane l: threads l, l + 64, l + 128, l + 192 in that order, then the
@@ -160,10 +164,13 @@ __device__ __forceinline__ void wave_publish(dd (&acc)[NOUT], const RedArgs &ra)
 // and three of the four waves now skip it: measured on the fused SpMV + p.Ap at 512^3 (profiles/r04*).  The partial lands
 // in the first wave's slot, the other three slots get an exact zero (the finish kernel's input layout is unchanged).
 // s_red: kBlock * NOUT dd of LDS that no wave reads any more once every wave has passed the caller's last barrier.
+// `blk`: the workgroup of a loop-free launch whose slots are written (see wave_publish_at).  A workgroup that publishes more than once hands in two
+// scratch regions by turns (s_red of publish k = region k & 1): waves 1-3 reach publish k + 1 while wave 0 may still read the scratch
+// of publish k, and the barrier of publish k + 1 orders those reads before anyone's writes of publish k + 2.
 template <int NOUT>
-__device__ __forceinline__ void block_publish(dd (&acc)[NOUT], const RedArgs &ra, dd *s_red) {
+__device__ __forceinline__ void block_publish_at(dd (&acc)[NOUT], const RedArgs &ra, dd *s_red, int64_t blk) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t wid = ra.wave_offset + (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+  const int64_t wid = ra.wave_offset + blk * (blockDim.x >> 6) + wave;
 #pragma unroll
   for (int o = 0; o < NOUT; ++o) s_red[o * kBlock + tid] = acc[o];
   __syncthreads();
@@ -182,6 +189,9 @@ __device__ __forceinline__ void block_publish(dd (&acc)[NOUT], const RedArgs &ra
     for (int o = 0; o < NOUT; ++o) ra.wave_partials[(size_t)o * ra.cap + wid] = dd{0.0, 0.0};
   }
 }
+
+template <int NOUT>
+__device__ __forceinline__ void block_publish(dd (&acc)[NOUT], const RedArgs &ra, dd *s_red) { block_publish_at<NOUT>(acc, ra, s_red, (int64_t)blockIdx.x); }
 
 // Workgroup reduction of NOUT partials; result valid in thread 0.
 template <int NOUT>

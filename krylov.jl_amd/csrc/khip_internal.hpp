@@ -99,6 +99,7 @@ struct Tuning {
   int spmv_sell_pair = 1;   // sliced form of a coded operator: the row's words in 16-byte pairs (half the vector-memory instructions of the matrix stream): 7-point 512^3 fused 1.92-2.00 -> 1.77-1.84 ms, 27-point 216^3 plain 0.53 -> 0.49 ms; 2 = for the int32 form too (96 instead of 88 B per 7-point row: no gain, off)
   int spmv_sell_entries = 1; // sliced form: one-byte (diagonal, value) codes instead of code words + values where the handle holds at most 255 distinct entries (8 instead of 64 B per 7-point row): 1 = on handles of at least 2^22 entries (the rule of spmv_codes), 2 = whenever the handle qualifies, 0 = never; read when the sliced copy is built
   int spmv_sell_narrow = 0; // sliced form: 1 = 4-bit codes in one 32-bit word per row where the operator allows (<= 15 diagonals, <= 8 entries per row): 60 instead of 64 B per 7-point row -- and 8-10 % SLOWER at 512^3 (fused 2.13-2.15 against 1.93-1.98 ms: slices of 7 units are no longer 4 KB blocks, and the codes are a second stream of 256-byte wave loads; profiles/r06au_spmv_sell_narrow_ab.log): off
+  int spmv_sell_persist = 1; // entry-coded sliced product: 1 = on handles of one code word per row, long-lived workgroups (8 for every one the chip holds at once) walk the workgroups of the loop-free launch, strided, where that launch has more of them -- one table fetch and barrier per launched workgroup, code words loaded ahead across the boundaries; same rows, same partial slots, same bits (spmv_sell_persist_kernel; 512^3 fused 1.30-1.32 -> 1.09-1.13 ms); 0 = the loop-free launch; G > 1 = exactly min(G, workgroups of the loop-free launch) workgroups on any entry-coded handle, whatever the size (tests)
   int spmv_blk_pub = 0;     // fused dots of the staged / coded / delta SpMV kernels: 1 = workgroup-level fold in LDS, one wave runs the double-double tree (block_publish); measured equal to the per-wave trees (profiles/r04b_sweep_headline.log): off
   int spmv_delta = 0;       // stream kernel: block-delta column stream (coldelta.hip: 1 or 2 B per entry + 6 B per escape) -- 0: never (default: 18 % fewer bytes but no faster on the banded + random operator, slower on stencils; profiles/r04a_sweep_delta.log); 1: operators of >= 4 M entries where it saves at least a sixth of the column bytes; 2: whatever the size; 8 / 16: that width, always
   int spmv_wide = 0;        // stream kernel: 1 = the 16-byte-load form (spmv_delta_kernel<int32_t>) where the delta stream is not used (measured equal on the irregular operator, 8 % slower on the 27-point one); 0: the 8 + 4 byte loads of spmv_stream_kernel
@@ -190,6 +191,8 @@ struct khip_ctx {
   hipEvent_t ev_red = nullptr;         // comm_allreduce_dd_device_begin / _end (all-reduce on the communication stream)
   bool allreduce_pending = false;      // a _begin on this context still waits for its _end
   int num_cu = 256;
+  // workgroups of spmv_sell_persist_kernel a CU holds (occupancy query, once per instantiation and LDS size; 0 = not asked yet)
+  int sell_persist_occ[32][3] = {};
   // test-only record of what the last khip_spmm on this context launched (khip_test_spmm_last_launch, include/krylov_hip_test.h):
   // written from the variables the launch itself uses, read by nothing but the export
   int64_t spmm_last[khip::kSpmmLastWords] = {};

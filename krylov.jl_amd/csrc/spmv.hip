@@ -469,6 +469,30 @@ __device__ __forceinline__ double ent_step(const SpmvArgs &a, int32_t row, unsig
   return acc;
 }
 
+// ent_step with the value lookups behind the gathers: the values are not live while the gathers are issued (the same lookups, the
+// same products in the same order -- the same bits); LDS answers long before the gathers do
+template <bool DIST>
+__device__ __forceinline__ double ent_step_late(const SpmvArgs &a, int32_t row, unsigned long long cw, const int32_t *s_off, const double *s_val, double acc) {
+  double xx[8];
+  int32_t cc[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) cc[u] = row + s_off[(int)((cw >> (8 * u)) & 0xFFull)];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    xx[u] = 0.0;
+    if (((cw >> (8 * u)) & 0xFFull) != 0xFFull) xx[u] = gather_x<DIST>(a, cc[u]);
+  }
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int c = (int)((cw >> (8 * u)) & 0xFFull);
+    if (c != 0xFF) {
+      const double prod = s_val[c] * xx[u];
+      acc = acc + prod;
+    }
+  }
+  return acc;
+}
+
 // the first code words of a row: the one word of a one-word slice (in .x), else the first 16-byte pair
 template <bool NTM>
 __device__ __forceinline__ dbl2 ent_first(const SpmvArgs &a, int64_t rowl, int64_t o0, int T) {
@@ -674,6 +698,125 @@ __global__ __launch_bounds__(kBlock) void spmv_sell_kernel(SpmvArgs a, RedArgs r
       else block_publish<1>(reinterpret_cast<dd (&)[1]>(dacc), ra, s_red);
     } else if (a.dot_sq) wave_publish<2>(dacc, ra);
     else wave_publish<1>(reinterpret_cast<dd (&)[1]>(dacc), ra);
+  }
+}
+
+// ---------------------------------------------------------------- sliced, entry codes, long-lived workgroups ----
+// The ENT arm of spmv_sell_kernel for large operators (spmv_sell_persist).  Workgroup v of that kernel's launch of nvirt workgroups -- its
+// row blocks, its reset accumulators, its partial slots -- becomes a VIRTUAL workgroup here, and gridDim.x workgroups walk
+// v = blockIdx.x, + gridDim.x, ... : strided, so the workgroups alive at one moment stay one front through the matrix, as the dispatch
+// order makes them there (a contiguous chunk each would fetch the x planes at +-n1^2 once per workgroup's own front).  Rows, lanes,
+// arithmetic and published slots are those of spmv_sell_kernel<..., ENT>: y and every partial are the same bits.  What changes is what a
+// workgroup waits for: the table fetch and its barrier once per launched workgroup, and the code words of the next row block loaded
+// beside the gathers of this one ACROSS the boundary between virtual workgroups.
+// ONE: every slice holds one code word per row (a.sell_units == 1, the 7-point operators): a lane carries that word instead of a
+// 16-byte pair, 60 VGPRs and 8 waves per SIMD with the compensated dot where the general walk takes 73 and 6.
+// Not kept: issuing the NEXT block's gathers before this block's products (124-127 VGPRs, 4 waves per SIMD, slower).
+struct SellPos { int v, rb, rb_end; };            // a row block of virtual workgroup v; behind the end: v >= nvirt, rb = rb_end = nrb
+
+template <bool DOT, bool COMP, bool DIST, bool NTM, bool ONE>
+__global__ __launch_bounds__(kBlock) void spmv_sell_persist_kernel(SpmvArgs a, RedArgs ra, int nvirt) {
+  if (seq_skip(a.stop_seq, a.seq)) return;
+  const int ROWS = a.stage_rows;
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_stage[];
+  // [block_publish scratch, twice: see block_publish_at][offsets, 256 x int32][values, 256 x double]
+  const size_t pub = (DOT && a.blk_pub) ? sizeof(dd) * (size_t)kBlock * (a.dot_sq ? 2u : 1u) : 0u;
+  int32_t *s_off = reinterpret_cast<int32_t *>(s_stage + 2 * pub);
+  double *s_val = reinterpret_cast<double *>(s_stage + 2 * pub + 256 * sizeof(int32_t));
+  const int tid = threadIdx.x;
+  const int G = gridDim.x;
+  const int64_t nrows = a.row_hi - a.row_lo - a.hole_len;
+  const int nrb = (int)((nrows + ROWS - 1) / ROWS);      // rows are int32 (the gathers' columns are): so are row blocks
+  const int tpb = a.tiles_per_block > 0 ? a.tiles_per_block : 1;
+  auto first_of = [&](int v) -> SellPos {      // the row blocks of spmv_sell_kernel's workgroup v
+    if (v >= nvirt) return SellPos{v, nrb, nrb};
+    const int64_t b = (int64_t)chunk_id(v, nvirt, a.xcd_remap) * tpb;
+    return SellPos{v, (int)(b < nrb ? b : nrb), (int)((b + tpb < nrb) ? b + tpb : nrb)};
+  };
+  auto next_of = [&](const SellPos &p) -> SellPos {
+    if (p.rb + 1 < p.rb_end) return SellPos{p.v, p.rb + 1, p.rb_end};
+    return first_of(p.v + G);
+  };
+  auto lane_row = [&](const SellPos &p) -> int64_t {      // this lane's row in the block, -1: none
+    if (p.rb >= p.rb_end || tid >= ROWS) return -1;
+    int64_t r = a.row_lo + (int64_t)p.rb * ROWS;
+    if (r >= a.hole_lo) r += a.hole_len;       // the second range of a two-range launch
+    r += tid;
+    return r < a.row_hi ? r : -1;
+  };
+  auto slice_of = [&](int64_t rowl, int64_t &o0, int &T) {
+    const int64_t sl = rowl >> 6;
+    if (ONE) { o0 = sl; T = 1; }               // a.sell_units == 1: a lane carries one code word, not a pair
+    else if (a.sell_units) { o0 = sl * a.sell_units; T = a.sell_units; }
+    else { const uint32_t b0 = a.sell_off[sl], b1 = a.sell_off[sl + 1]; o0 = (int64_t)b0; T = (int)(b1 - b0); }
+  };
+  auto load_codes = [&](const SellPos &p, dbl2 &ce) {      // the first code words of this lane's row in the block
+    const int64_t rowl = lane_row(p);
+    if (rowl < 0) return;
+    int64_t o0;
+    int T;
+    slice_of(rowl, o0, T);
+    ce = ent_first<NTM>(a, rowl, o0, T);
+  };
+  // code words behind the first pair: the walk of spmv_sell_kernel's ENT arm
+  auto walk_row = [&](int64_t rowl, dbl2 ce) -> double {
+    int64_t o0;
+    int T;
+    slice_of(rowl, o0, T);
+    const dbl2 *pb = reinterpret_cast<const dbl2 *>(a.sell + (size_t)o0 * 64) + (rowl & 63);
+    double acc = 0.0;
+    for (int w = 0; w < T; ++w) {
+      if (w >= 2 && (w & 1) == 0) ce = ld<NTM>(pb + (size_t)(w >> 1) * 64);
+      acc = ent_step_late<DIST>(a, (int32_t)rowl, (unsigned long long)__double_as_longlong((w & 1) ? ce.y : ce.x), s_off, s_val, acc);
+    }
+    return acc;
+  };
+  dd dacc[2];
+  dacc[0] = dd{0.0, 0.0};
+  dacc[1] = dd{0.0, 0.0};
+  auto finish_row = [&](int64_t rowl, double acc, double wv) {
+    if (DOT && a.lz) acc = lanczos_row(a, rowl, acc, wv);
+    store_y(a, rowl, acc);
+    if (DOT) {
+      acc_prod<COMP>(dacc[0], wv, acc);
+      if (a.dot_sq == 1) acc_prod<COMP>(dacc[1], acc, acc);
+      else if (a.dot_sq == 2) acc_prod<COMP>(dacc[1], wv, wv);
+    }
+  };
+  int npub = 0;
+  auto publish = [&](int v) {                  // the partials of virtual workgroup v, then a fresh accumulator
+    if (DOT) {
+      if (a.blk_pub) {
+        dd *s_red = reinterpret_cast<dd *>(s_stage + (size_t)(npub & 1) * pub);
+        if (a.dot_sq) block_publish_at<2>(dacc, ra, s_red, v);
+        else block_publish_at<1>(reinterpret_cast<dd (&)[1]>(dacc), ra, s_red, v);
+      } else if (a.dot_sq) wave_publish_at<2>(dacc, ra, v);
+      else wave_publish_at<1>(reinterpret_cast<dd (&)[1]>(dacc), ra, v);
+      ++npub;
+      dacc[0] = dd{0.0, 0.0};
+      dacc[1] = dd{0.0, 0.0};
+    }
+  };
+
+  SellPos cur = first_of(blockIdx.x);
+  dbl2 ent_next = dbl2{0.0, 0.0};
+  load_codes(cur, ent_next);                   // before the table: they do not depend on it
+  {
+    const int32_t *eo = static_cast<const int32_t *>(a.sell_ent);
+    const double *ev = reinterpret_cast<const double *>(eo + 256);
+    for (int i = tid; i < 256; i += kBlock) { s_off[i] = eo[i]; s_val[i] = ev[i]; }
+    __syncthreads();
+  }
+  while (cur.v < nvirt) {                      // depends on blockIdx only: every barrier below is reached by all four waves
+    const SellPos nxt = next_of(cur);
+    const int64_t rowl = lane_row(cur);
+    double wv = 0.0;
+    if (DOT && rowl >= 0) wv = a.dotw[rowl];
+    const dbl2 ce = ent_next;                  // loaded one row block ahead
+    load_codes(nxt, ent_next);                 // ... and the next block's, beside this block's gathers
+    if (rowl >= 0) finish_row(rowl, walk_row(rowl, ce), wv);
+    if (nxt.v != cur.v) publish(cur.v);
+    cur = nxt;
   }
 }
 
@@ -1182,6 +1325,45 @@ static void launch_sell_cfg(khip_ctx *ctx, const SpmvArgs &a, const RedArgs &ra,
 #undef KHIP_SELL
 }
 
+// The entry-coded product of `nvirt` loop-free workgroups by long-lived ones (spmv_sell_persist; a.sell_ent is set).  want = 1:
+// kSellPersistRounds workgroups for every one the chip holds at once (occupancy query x CUs; a multiple of 8, so that a virtual workgroup
+// keeps the XCD of its launch index), and the loop-free launch where that launch is no larger; want > 1: exactly min(want, nvirt).
+// Returns false where the loop-free launch is to run.  Nothing depends on co-residency for correctness.
+// The rounds, measured on the fused product at 512^3 (262,144 virtual workgroups, 2048 resident): with one round the
+// workgroups drift apart and the front through x widens (1.41-1.44 ms, slower than the loop-free launch's 1.30-1.32); the dispatcher
+// closes the front again every time it hands out the next workgroups: 2 rounds 1.25 ms, 4 rounds 1.16-1.17, 8 to 32 rounds 1.09-1.10.
+// Handles whose rows take more than one code word keep the loop-free launch under want = 1: their arm of the kernel carries a pair of
+// code words per lane (73 VGPRs, 6 waves per SIMD with the compensated dot, where spmv_sell_kernel runs 7) and measured no gain on
+// the 27-point operator at 216^3 (plain 0.182 against 0.183-0.201 ms, fused 0.230 against 0.222-0.229).
+constexpr int kSellPersistRounds = 8;
+static bool launch_sell_persist_cfg(khip_ctx *ctx, const SpmvArgs &a, const RedArgs &ra, unsigned nvirt, int want, bool dot, bool comp, bool dist) {
+  const size_t pub = dot && a.blk_pub ? sizeof(dd) * (size_t)kBlock * (a.dot_sq ? 2u : 1u) : 0u;
+  const size_t lds = 2u * pub + 4u * 256u + 8u * 256u;      // two publish regions by turns (block_publish_at)
+  const bool ntm = ctx->tune.spmv_sell == 2;
+  unsigned grid = 0;
+  bool ok = true;
+#define KHIP_L(DOT, COMP, DIST) \
+  do { auto go = [&](auto kern, int key) { \
+         if (want > 1) grid = (unsigned)want < nvirt ? (unsigned)want : nvirt; \
+         else if (a.sell_units != 1) { ok = false; return; } \
+         else { \
+           int &nb = ctx->sell_persist_occ[key][pub ? (a.dot_sq ? 2 : 1) : 0]; \
+           if (nb == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, kBlock, lds) != hipSuccess || nb <= 0)) { (void)hipGetLastError(); nb = -1; } \
+           const int64_t g = nb > 0 ? ((int64_t)nb * ctx->num_cu * kSellPersistRounds) & ~(int64_t)7 : 0; \
+           if (g < 8 || (int64_t)nvirt <= g) { ok = false; return; } \
+           grid = (unsigned)g; \
+         } \
+         hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, ctx->stream, a, ra, (int)nvirt); }; \
+       const int key = (DOT ? 1 : 0) | (COMP ? 2 : 0) | (DIST ? 4 : 0) | (ntm ? 8 : 0); \
+       if (a.sell_units == 1) { if (ntm) go(spmv_sell_persist_kernel<DOT, COMP, DIST, true, true>, key | 16); \
+                                else go(spmv_sell_persist_kernel<DOT, COMP, DIST, false, true>, key | 16); } \
+       else if (ntm) go(spmv_sell_persist_kernel<DOT, COMP, DIST, true, false>, key); \
+       else go(spmv_sell_persist_kernel<DOT, COMP, DIST, false, false>, key); } while (0)
+  KHIP_DISPATCH_DCD(KHIP_L);
+#undef KHIP_L
+  return ok;
+}
+
 template <typename CODE>
 static void launch_delta_cfg(khip_ctx *ctx, const SpmvArgs &a, const RedArgs &ra, unsigned grid, bool dot, bool comp,
                              bool dist) {
@@ -1484,7 +1666,11 @@ int launch_spmv(khip_ctx *ctx, const khip_csr *A, const double *x, double *y, in
     if (form == SpmvForm::Sliced) {
       a.sell = A->sell; a.sell_off = A->sell_off; a.sell_units = A->sell_units; a.sell_cols = 0; a.sell_c4 = A->sell_c4; a.sell_pair = A->sell_pair;
       a.sell_ent = A->sell_ent_state == 1 ? A->sell_ent_tab : nullptr;
-      launch_sell_cfg(ctx, a, ra, grid, dot, comp, dist);
+      // entry codes: long-lived workgroups walk the `grid` workgroups of the loop-free launch (same rows, same partial slots: the
+      // scratch, the cursor and the finish kernel see grid * 4 partials either way)
+      const int want = ctx->tune.spmv_sell_persist;
+      if (!(a.sell_ent && want > 0 && launch_sell_persist_cfg(ctx, a, ra, grid, want, dot, comp, dist)))
+        launch_sell_cfg(ctx, a, ra, grid, dot, comp, dist);
     } else if (form == SpmvForm::Sliced32) {
       a.sell = A->sell32; a.sell_off = A->sell32_off; a.sell_units = A->sell32_units; a.sell_cols = 1; a.sell_pair = A->sell32_pair; a.sell_c4 = nullptr;
       launch_sell_cfg(ctx, a, ra, grid, dot, comp, dist);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Resource usage of every spmv_sell_kernel instantiation, from the compiler's remarks on a gfx950 cross-compile (no GPU needed).
+"""Resource usage of every spmv_sell_kernel and spmv_sell_persist_kernel instantiation, from the compiler's remarks on a gfx950 cross-compile (no GPU needed).
 
   tools/sell_resource_usage.py [csrc directory ...]      # default: this tree's krylov.jl_amd/csrc
 
@@ -27,7 +27,7 @@ def usage(csrc):
         m = re.search(r"remark: .*Function Name: (\S+)", line)
         if m:
             name = subprocess.run(["c++filt", m.group(1)], stdout=subprocess.PIPE, text=True).stdout.strip()
-            cur = out.setdefault(name, {}) if "spmv_sell_kernel" in name else None
+            cur = out.setdefault(name, {}) if re.search(r"spmv_sell(_persist)?_kernel<", name) else None
             continue
         if cur is None:
             continue
@@ -39,8 +39,8 @@ def usage(csrc):
 
 
 def short(name):
-    m = re.search(r"spmv_sell_kernel<([^>]*)>", name)
-    return "<" + ", ".join("1" if v.strip() == "true" else "0" for v in m.group(1).split(",")) + ">"
+    m = re.search(r"spmv_sell(_persist)?_kernel<([^>]*)>", name)
+    return ("persist" if m.group(1) else "") + "<" + ", ".join("1" if v.strip() == "true" else "0" for v in m.group(2).split(",")) + ">"
 
 
 def main():
@@ -49,7 +49,7 @@ def main():
     for d in dirs:
         u = usage(d)
         print(f"# {os.path.relpath(d, ROOT) if len(dirs) == 1 else 'tree ' + str(dirs.index(d) + 1)}: {len(u)} instantiations of "
-              "spmv_sell_kernel<DOT, COMP, DIST, NTM, COLS32, C4, PAIR, PAIRG[, ENT]>")
+              "spmv_sell_kernel<DOT, COMP, DIST, NTM, COLS32, C4, PAIR, PAIRG[, ENT]> and spmv_sell_persist_kernel (persist<DOT, COMP, DIST, NTM, ONE>)")
         print(f"{'instantiation':<30}" + "".join(f"{k:>9}" for _, k in KEYS) + ("  vs tree 1" if prev is not None else ""))
         for name in sorted(u, key=short):
             row = u[name]
