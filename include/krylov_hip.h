@@ -698,6 +698,53 @@ int khip_cgs_last_path(khip_cgs_workspace *ws);
 double           *khip_cgs_vector(khip_cgs_workspace *ws, const char *name);
 size_t            khip_cgs_workspace_bytes(khip_cgs_workspace *ws);   /* 6n doubles without M, N and warm start */
 
+/* ---- symmlq! (src/symmlq.jl:132-464), real Float64: (A + λI) x = b with A symmetric, possibly indefinite; the iterate xᴸ minimises
+ * the error, and the CG point xᶜ is handed back when it is good enough (transfer_to_cg).  SymmlqWorkspace
+ * (src/krylov_workspaces.jl:461-476): x, Mvold, Mv, Mv_next, w̅ ("wbar"); Δx and v ("dx", "v") stay empty until a warm start or M
+ * needs them; clist, zlist and sprod (window entries each) live in the library.  options.variant != 0 is refused (there is no other
+ * recurrence); radius, linesearch, reorthogonalization and restart are ignored. */
+typedef struct khip_symmlq_workspace khip_symmlq_workspace;
+typedef struct {
+  double lambda;       /* λ */
+  double lambda_est;   /* λest: 0 = no error estimates */
+  double etol;         /* NaN: the reference's default, √eps */
+  double conlim;       /* NaN: the reference's default, 1 / √eps */
+  int transfer_to_cg;  /* default 1 */
+} khip_symmlq_params;
+khip_symmlq_params khip_symmlq_default_params(void);   /* lambda = lambda_est = 0, etol = conlim = NaN, transfer_to_cg = 1 */
+int khip_symmlq_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, int window, khip_symmlq_workspace **out);
+/* SymmlqWorkspace on the caller's five vectors; every pointer must be distinct.  adopt_vector names: "dx" (Δx: warm_start! fills it
+ * on the caller's side and hands it over, then khip_symmlq_warm_start(ws, dx) only sets the flag), "v" (needed with M).  The fused
+ * loops rotate the roles of (Mvold, Mv, Mv_next) where the reference copies: khip_symmlq_vector returns a name's pointer by its
+ * current role, so after a solve every name holds what the reference's variable of that name holds. */
+int khip_symmlq_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, int window, double *x, double *Mvold, double *Mv,
+                                double *Mv_next, double *wbar, khip_symmlq_workspace **out);
+int khip_symmlq_workspace_adopt_vector(khip_symmlq_workspace *ws, const char *name, double *ptr);
+int khip_symmlq_workspace_destroy(khip_symmlq_workspace *ws);
+int khip_symmlq_warm_start(khip_symmlq_workspace *ws, const double *x0);
+/* symmlq!(ws, A, b; M, transfer_to_cg, λ, λest, atol, rtol, etol, conlim, itmax, timemax, verbose, history, callback).  M == NULL
+ * means the identity; params == NULL: the defaults.  m != n: KHIP_ERR_INVALID "System must be square"; ⟨v, Mv⟩ < 0:
+ * KHIP_ERR_INVALID "Preconditioner is not positive definite" (also where the reference takes the square root of ⟨b, M b⟩ < 0).  The
+ * status strings are the reference's, in UTF-8:
+ *   "solution xᴸ good enough given atol and rtol", "solution xᶜ good enough given atol and rtol", "found approximate solution", ...
+ * Loops (khip_symmlq_last_path): 2 = device-resident (A a CSR handle, M = I, λest = 0, no callback, verbose = 0), 1 = host-driven on
+ * the same kernels (same bits as 2), 0 = one launch per primitive (options.fused = 0). */
+int khip_symmlq_solve(khip_symmlq_workspace *ws, const khip_operator *A, const khip_operator *M, const double *b,
+                      const khip_options *opts, const khip_symmlq_params *params);
+double           *khip_symmlq_solution(khip_symmlq_workspace *ws);
+const khip_stats *khip_symmlq_stats(khip_symmlq_workspace *ws);      /* residuals = the reference's stats.residuals */
+/* stats.residualscg, stats.errors and stats.errorscg of the last solve (history = true), owned by the workspace until its next
+ * solve.  Where the reference stores `missing` (no CG point: γbar = 0) the entry is NaN.  errors and errorscg are empty unless
+ * λest != 0. */
+int khip_symmlq_histories(khip_symmlq_workspace *ws, const double **residualscg, int *nresidualscg, const double **errors,
+                          int *nerrors, const double **errorscg, int *nerrorscg);
+/* stats.Anorm and stats.Acond of the last solve (NaN after "x is a zero-residual solution", as in the reference) */
+int khip_symmlq_norms(khip_symmlq_workspace *ws, double *Anorm, double *Acond);
+int khip_symmlq_last_path(khip_symmlq_workspace *ws);
+/* named work vectors: "x", "Mvold", "Mv", "Mv_next", "wbar", "dx", "v" (NULL while not allocated) */
+double           *khip_symmlq_vector(khip_symmlq_workspace *ws, const char *name);
+size_t            khip_symmlq_workspace_bytes(khip_symmlq_workspace *ws);   /* 5n doubles without M and warm start */
+
 int khip_gmres_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, int memory, khip_gmres_workspace **out);
 /* GmresWorkspace on the caller's x, w and basis V_host[0 .. memory) (device pointers in a HOST array; `V::Vector{S}`,
  * src/krylov_workspaces.jl:2857-2873).  adopt_vector names: "x", "w", "p", "q", "dx".  adopt_basis replaces the whole list

@@ -638,6 +638,83 @@ function Krylov.cgs!(ws::CgsWs, A::HIPCsr, b::HIPVector; c::HIPVector = b, M = I
   return ws
 end
 
+# ------------------------------------------------------------------------------------------------ symmlq!  (src/symmlq.jl:132-464)
+struct SymmlqParams                # khip_symmlq_params: λ, λest, etol, conlim, transfer_to_cg
+  lambda::Cdouble; lambda_est::Cdouble; etol::Cdouble; conlim::Cdouble; transfer_to_cg::Cint
+end
+const SymmlqWs = SymmlqWorkspace{Float64,Float64,HIPVector}
+function symmlq_handle(ws::SymmlqWs)
+  get!(HANDLES, ws) do
+    r = Ref{Ptr{Cvoid}}()
+    ck(ccall((:khip_symmlq_workspace_adopt, lib), Cint,
+             (Ptr{Cvoid}, Int64, Int64, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Ptr{Cvoid}}),
+             CTX[].h, ws.m, ws.n, length(ws.clist), ws.x.ptr, ws.Mvold.ptr, ws.Mv.ptr, ws.Mv_next.ptr, ws.w̅.ptr, r))
+    h = r[]
+    finalizer(_ -> ccall((:khip_symmlq_workspace_destroy, lib), Cint, (Ptr{Cvoid},), h), ws)
+    h
+  end
+end
+# SymmlqStats (src/krylov_stats.jl) has no inconsistent / indefinite / npcCount; reset! empties its four histories
+function fill_stats!(stats::Krylov.SymmlqStats{Float64}, sp::Ptr{Stats}, history::Bool)
+  st = unsafe_load(sp)
+  Krylov.reset!(stats)
+  history && st.nres > 0 && append!(stats.residuals, unsafe_wrap(Array, st.residuals, Int(st.nres)))
+  stats.niter = st.niter;  stats.solved = st.solved != 0
+  stats.timer = st.timer;  stats.status = cstr(st.status)
+  return st
+end
+symmlq_adopt(h, name, v::HIPVector) =ck(ccall((:khip_symmlq_workspace_adopt_vector, lib), Cint, (Ptr{Cvoid}, Cstring, Ptr{Cdouble}), h, name, dptr(v)))
+
+# The window lists (clist, zlist, sprod) live in the library, which takes their length from ws.clist.  The fused loops rotate the
+# roles of (Mvold, Mv, Mv_next): after the solve only x and the stats are defined on this side.  NaN in residualscg and errorscg is
+# the reference's `missing`.
+function Krylov.symmlq!(ws::SymmlqWs, A::HIPCsr, b::HIPVector; M = I, ldiv::Bool = false, transfer_to_cg::Bool = true, λ::Float64 = 0.0,
+                        λest::Float64 = 0.0, atol::Float64 = √eps(Float64), rtol::Float64 = √eps(Float64),
+                        etol::Float64 = √eps(Float64), conlim::Float64 = 1/√eps(Float64), itmax::Int = 0, timemax::Float64 = Inf,
+                        verbose::Int = 0, history::Bool = false, callback = nothing, iostream::IO = Krylov.kstdout, fused::Int = 2)
+  if ldiv || !native_precond(M) || !native_log(verbose, iostream)
+    GENERIC_SOLVES[] += 1
+    return invoke(Krylov.symmlq!, Tuple{SymmlqWs,Any,AbstractVector{Float64}}, ws, A, b; M, ldiv, transfer_to_cg, λ, λest, atol, rtol,
+                  etol, conlim, itmax, timemax, verbose, history, callback = callback === nothing ? (w -> false) : callback, iostream)
+  end
+  m, n = size(A)                                                                            # :138-141
+  (m == ws.m && n == ws.n) || error("(workspace.m, workspace.n) = ($(ws.m), $(ws.n)) is inconsistent with size(A) = ($m, $n)")
+  m == n || error("System must be square")
+  length(b) == m || error("Inconsistent problem size")
+  Krylov.allocate_if(M !== I, ws, :v, HIPVector, ws.x)                                        # :152
+  h = symmlq_handle(ws)
+  for (name, v) in (("v", ws.v), ("dx", ws.Δx))
+    symmlq_adopt(h, name, v)
+  end
+  ws.warm_start && ck(ccall((:khip_symmlq_warm_start, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h, ws.Δx.ptr))
+  sp = ccall((:khip_symmlq_stats, lib), Ptr{Stats}, (Ptr{Cvoid},), h)
+  cbf, cbd, box = callback_args(user_callback(callback), ws, sp, history)
+  opts = Ref(Options(; atol, rtol, itmax, timemax, history, fused, verbose, log_fd = logfd(iostream), callback = cbf, callback_data = cbd))
+  prm = Ref(SymmlqParams(λ, λest, etol, conlim, transfer_to_cg))
+  opA = Ref(Operator(A))
+  rc = GC.@preserve ws A b M opts prm opA box ccall((:khip_symmlq_solve, lib), Cint,
+                                                     (Ptr{Cvoid}, Ref{Operator}, Ptr{Operator}, Ptr{Cdouble}, Ref{Options}, Ptr{Cvoid}),
+                                                     h, opA, opref(M), b.ptr, opts, prm)
+  st = fill_stats!(ws.stats, sp, history)
+  if history                                                                               # stats.residualscg, errors, errorscg
+    rc_, nrc, er, ner, ec, nec = Ref{Ptr{Cvoid}}(), Ref{Cint}(0), Ref{Ptr{Cvoid}}(), Ref{Cint}(0), Ref{Ptr{Cvoid}}(), Ref{Cint}(0)
+    ck(ccall((:khip_symmlq_histories, lib), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Cint}, Ref{Ptr{Cvoid}}, Ref{Cint}, Ref{Ptr{Cvoid}}, Ref{Cint}),
+             h, rc_, nrc, er, ner, ec, nec))
+    unmissing(v) = isnan(v) ? missing : v
+    nrc[] > 0 && append!(ws.stats.residualscg, unmissing.(unsafe_wrap(Array, Ptr{Float64}(rc_[]), Int(nrc[]))))
+    ner[] > 0 && append!(ws.stats.errors, unsafe_wrap(Array, Ptr{Float64}(er[]), Int(ner[])))
+    nec[] > 0 && append!(ws.stats.errorscg, unmissing.(unsafe_wrap(Array, Ptr{Float64}(ec[]), Int(nec[]))))
+  end
+  an, ac = Ref{Cdouble}(NaN), Ref{Cdouble}(NaN)
+  ck(ccall((:khip_symmlq_norms, lib), Cint, (Ptr{Cvoid}, Ref{Cdouble}, Ref{Cdouble}), h, an, ac))
+  ws.stats.Anorm = an[];  ws.stats.Acond = ac[]
+  NATIVE_SOLVES[] += 1;  LAST_PATH[] = ccall((:khip_symmlq_last_path, lib), Cint, (Ptr{Cvoid},), h)
+  ws.warm_start = false
+  finish_callback(box)
+  rc == 0 || failed(st)
+  return ws
+end
+
 # ------------------------------------------------------------------------------------------------ bilqr!  (src/bilqr.jl:116-484)
 struct BilqrParams                 # khip_bilqr_params: transfer_to_bicg
   transfer_to_bicg::Cint

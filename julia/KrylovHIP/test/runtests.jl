@@ -267,3 +267,4 @@ end
 
 include("bilqr.jl")                                                  # bilqr! against the generic method, its breakdowns and statuses
 include("cgs.jl")                                                    # cgs! against the generic method, its endings and breakdowns
+include("symmlq.jl")                                                 # symmlq! against the generic method, its histories and error estimates

@@ -58,6 +58,11 @@ class CMinresParams(C.Structure):
     _fields_ = [("lambda_", C.c_double), ("etol", C.c_double), ("conlim", C.c_double)]
 
 
+class CSymmlqParams(C.Structure):
+    _fields_ = [("lambda_", C.c_double), ("lambda_est", C.c_double), ("etol", C.c_double), ("conlim", C.c_double),
+                ("transfer_to_cg", C.c_int)]
+
+
 class CLanczosShiftParams(C.Structure):
     _fields_ = [("shifts", c_double_p), ("nshifts", C.c_int), ("check_curvature", C.c_int)]
 
@@ -293,6 +298,22 @@ SIGNATURES = {
     "khip_cgs_last_path": (_int, [_vp]),
     "khip_cgs_vector": (_vp, [_vp, C.c_char_p]),
     "khip_cgs_workspace_bytes": (_sz, [_vp]),
+    "khip_symmlq_default_params": (CSymmlqParams, []),
+    "khip_symmlq_workspace_create": (_int, [_vp, _i64, _i64, _int, c_void_pp]),
+    "khip_symmlq_workspace_adopt": (_int, [_vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, c_void_pp]),
+    "khip_symmlq_workspace_adopt_vector": (_int, [_vp, C.c_char_p, _vp]),
+    "khip_symmlq_workspace_destroy": (_int, [_vp]),
+    "khip_symmlq_warm_start": (_int, [_vp, _vp]),
+    "khip_symmlq_solve": (_int, [_vp, C.POINTER(COperator), C.POINTER(COperator), _vp, C.POINTER(COptions),
+                                 C.POINTER(CSymmlqParams)]),
+    "khip_symmlq_solution": (_vp, [_vp]),
+    "khip_symmlq_stats": (C.POINTER(CStats), [_vp]),
+    "khip_symmlq_histories": (_int, [_vp, C.POINTER(c_double_p), C.POINTER(_int), C.POINTER(c_double_p), C.POINTER(_int),
+                                     C.POINTER(c_double_p), C.POINTER(_int)]),
+    "khip_symmlq_norms": (_int, [_vp, c_double_p, c_double_p]),
+    "khip_symmlq_last_path": (_int, [_vp]),
+    "khip_symmlq_vector": (_vp, [_vp, C.c_char_p]),
+    "khip_symmlq_workspace_bytes": (_sz, [_vp]),
     "khip_bilqr_default_params": (CBilqrParams, []),
     "khip_bilqr_workspace_create": (_int, [_vp, _i64, _i64, c_void_pp]),
     "khip_bilqr_workspace_adopt": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_void_pp]),
@@ -1659,6 +1680,47 @@ class CgsWorkspace(_BiLanczosWorkspace):
     VECTORS = ("x", "r", "u", "p", "q", "ts")
 
 
+class SymmlqWorkspace(_Workspace):
+    """SymmlqWorkspace(m, n, S; window = 5) (src/krylov_workspaces.jl:461-476): x, Mvold, Mv, Mv_next, w̅ ("wbar"); Δx and v stay
+    empty until needed.  stats carries residualscg, errors, errorscg (NaN where the reference has `missing`), Anorm and Acond.  The
+    fused loops rotate the roles of (Mvold, Mv, Mv_next), and `vector(name)` follows the role (khip_symmlq_vector): after a solve
+    a name holds what the reference's variable of that name holds."""
+    _prefix = "symmlq"
+    VECTORS = ("x", "Mvold", "Mv", "Mv_next", "wbar")
+
+    def __init__(self, ctx: Context, m: int, n: int, window: int = 5, adopt: bool | None = None, vectors=None):
+        self.ctx, self.m, self.n, self.window = ctx, m, n, window
+        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
+        self._h = C.c_void_p()
+        if self.adopted:
+            t0 = time.perf_counter()
+            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(n) for k in self.VECTORS}     # dx, v stay empty
+            self._alloc_s = time.perf_counter() - t0
+            _ck(lib().khip_symmlq_workspace_adopt(ctx._h, m, n, window, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
+        else:
+            _ck(lib().khip_symmlq_workspace_create(ctx._h, m, n, window, C.byref(self._h)))
+
+    @property
+    def stats(self) -> SimpleStats:
+        st = super().stats
+        ptr = [c_double_p() for _ in range(3)]
+        cnt = [_int() for _ in range(3)]
+        _ck(lib().khip_symmlq_histories(self._h, C.byref(ptr[0]), C.byref(cnt[0]), C.byref(ptr[1]), C.byref(cnt[1]),
+                                        C.byref(ptr[2]), C.byref(cnt[2])))
+        for name, q, k in zip(("residualscg", "errors", "errorscg"), ptr, cnt):
+            setattr(st, name, np.array(q[:k.value]) if k.value else np.zeros(0))
+        an, ac = C.c_double(), C.c_double()
+        _ck(lib().khip_symmlq_norms(self._h, C.byref(an), C.byref(ac)))
+        st.Anorm, st.Acond = an.value, ac.value
+        return st
+
+    def vector(self, name: str):
+        if name == "x":
+            return self.x
+        p = lib().khip_symmlq_vector(self._h, name.encode())
+        return DeviceVector(self.ctx, self.n, ptr=p, owner=self) if p else None
+
+
 class BilqrWorkspace(_BiLanczosWorkspace):
     """BilqrWorkspace(m, n, S) (src/krylov_workspaces.jl:1818-1836): uₖ₋₁, uₖ, q, vₖ₋₁, vₖ, p, x, y, d̅, wₖ₋₃, wₖ₋₂; Δx and Δy stay empty
     until a warm start."""
@@ -1778,6 +1840,27 @@ def minres_(ws: MinresWorkspace, A, b: DeviceVector, M=None, λ=0.0, etol=None, 
     if conlim is not None:
         prm.conlim = conlim
     rc = lib().khip_minres_solve(ws._h, _make_operator(ws.ctx, A, ws.n, keep), _make_operator(ws.ctx, M, ws.n, keep), _p(b),
+                                 C.byref(opts), C.byref(prm))
+    return _finish(ws, rc)
+
+
+def symmlq_(ws: SymmlqWorkspace, A, b: DeviceVector, M=None, transfer_to_cg=True, λ=0.0, λest=0.0, etol=None, conlim=None, **kw):
+    """symmlq!(workspace, A, b; M, ldiv, transfer_to_cg, λ, λest, atol, rtol, etol, conlim, itmax, timemax, verbose, history,
+    callback, iostream) (src/symmlq.jl:132-464).  Returns the workspace."""
+    keep = []
+    if len(b) != ws.n:
+        raise KhipError(-1, "Inconsistent problem size")                                  # src/symmlq.jl:141
+    ws._allocate_if(M is not None, "v")                                                   # src/symmlq.jl:152
+    opts = _make_options(keep=keep, ws=ws, **kw)
+    prm = lib().khip_symmlq_default_params()
+    prm.lambda_ = float(λ)
+    prm.lambda_est = float(λest)
+    prm.transfer_to_cg = int(bool(transfer_to_cg))
+    if etol is not None:
+        prm.etol = etol
+    if conlim is not None:
+        prm.conlim = conlim
+    rc = lib().khip_symmlq_solve(ws._h, _make_operator(ws.ctx, A, ws.n, keep), _make_operator(ws.ctx, M, ws.n, keep), _p(b),
                                  C.byref(opts), C.byref(prm))
     return _finish(ws, rc)
 
@@ -1914,15 +1997,21 @@ FORWARDED_DEFAULTS = {
                 history=False, callback=default_callback, iostream=None),
     "cgs": dict(c=None, M=None, N=None, ldiv=False, atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0, timemax=math.inf, verbose=0,
                 history=False, callback=default_callback, iostream=None),
+    "symmlq": dict(M=None, ldiv=False, transfer_to_cg=True, λ=0.0, λest=0.0, atol=_SQRT_EPS, rtol=_SQRT_EPS, etol=_SQRT_EPS,
+                   conlim=1.0 / _SQRT_EPS, itmax=0, timemax=math.inf, verbose=0, history=False, callback=default_callback,
+                   iostream=None),
     "bilqr": dict(transfer_to_bicg=True, atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0, timemax=math.inf, verbose=0, history=False,
                   callback=default_callback, iostream=None),
 }
 WORKSPACE_KWARGS = {"gmres": dict(memory=20), "block_gmres": dict(memory=5)}      # kwargs_workspace_gmres, _block_gmres
 # kwargs_workspace_minres (src/minres.jl:159): kept apart from WORKSPACE_KWARGS, whose contents tests/test_abi.py pins
 MINRES_WORKSPACE_KWARGS = dict(window=5)
+SYMMLQ_WORKSPACE_KWARGS = dict(window=5)                                        # kwargs_workspace_symmlq (src/symmlq.jl:121)
 
 
 def _workspace_kwargs(method: str) -> dict:
+    if method == "symmlq":
+        return SYMMLQ_WORKSPACE_KWARGS
     return MINRES_WORKSPACE_KWARGS if method == "minres" else WORKSPACE_KWARGS.get(method, {})
 
 
@@ -1938,7 +2027,8 @@ def krylov_workspace(method: str, *args, ctx: Context | None = None, **kw):
     """krylov_workspace(Val(method), m, n, S; memory) / (Val(method), A, b; memory) (src/interface.jl:117-141, 237-244)."""
     cls = {"cg": CgWorkspace, "gmres": GmresWorkspace, "bicgstab": BicgstabWorkspace, "block_gmres": BlockGmresWorkspace,
            "minres": MinresWorkspace, "cg_lanczos_shift": CgLanczosShiftWorkspace, "bilq": BilqWorkspace,
-           "qmr": QmrWorkspace, "bilqr": BilqrWorkspace, "cgs": CgsWorkspace}[method]
+           "qmr": QmrWorkspace, "bilqr": BilqrWorkspace, "cgs": CgsWorkspace,
+           "symmlq": SymmlqWorkspace}[method]
     if method == "cg_lanczos_shift":                                            # (A, b, nshifts) / (m, n, nshifts)
         if isinstance(args[1], DeviceVector):
             A, b, nshifts = args
@@ -2044,6 +2134,11 @@ def qmr(A, b: DeviceVector, x0=None, **kw):
 def cgs(A, b: DeviceVector, x0=None, **kw):
     """Out-of-place cgs(A, b[, x0]; kwargs...) -> (x, stats, workspace) (src/cgs.jl:126-134)."""
     return krylov_solve("cgs", A, b, x0, **kw)
+
+
+def symmlq(A, b: DeviceVector, x0=None, **kw):
+    """Out-of-place symmlq(A, b[, x0]; window, kwargs...) -> (x, stats, workspace) (src/symmlq.jl:16-22)."""
+    return krylov_solve("symmlq", A, b, x0, **kw)
 
 
 def bilqr(A, b: DeviceVector, c: DeviceVector, x0=None, y0=None, **kw):
@@ -2515,5 +2610,6 @@ def block_gmres(A, B, X0=None, ctx=None, **kw):
 _INPLACE.update({CgWorkspace: ("cg", cg_), GmresWorkspace: ("gmres", gmres_), BicgstabWorkspace: ("bicgstab", bicgstab_),
                  BlockGmresWorkspace: ("block_gmres", block_gmres_), MinresWorkspace: ("minres", minres_), BilqWorkspace: ("bilq", bilq_),
                  QmrWorkspace: ("qmr", qmr_), CgsWorkspace: ("cgs", cgs_),
+                 SymmlqWorkspace: ("symmlq", symmlq_),
                  BilqrWorkspace: ("bilqr", bilqr_),
                  CgLanczosShiftWorkspace: ("cg_lanczos_shift", cg_lanczos_shift_)})

@@ -17,7 +17,8 @@ namespace khip {
 enum Epilogue { EPI_NONE = 0, EPI_CG_STEP1 = 1, EPI_CG_STEP2 = 2, EPI_BICG_A = 3, EPI_BICG_B = 4, EPI_BICG_C = 5, EPI_CGCG = 6,
                EPI_MINRES_A = 7, EPI_MINRES_B = 8, EPI_MINRES_C = 9, EPI_LZSHIFT_A = 10, EPI_LZSHIFT_B = 11,
                EPI_BILQ_A = 12, EPI_BILQ_B = 13, EPI_BILQ_C = 14, EPI_QMR_A = 15, EPI_QMR_B = 16, EPI_QMR_C = 17,
-               EPI_BILQR_A = 18, EPI_BILQR_B = 19, EPI_BILQR_C = 20, EPI_CGS_A = 21, EPI_CGS_B = 22 };
+               EPI_BILQR_A = 18, EPI_BILQR_B = 19, EPI_BILQR_C = 20, EPI_CGS_A = 21, EPI_CGS_B = 22,
+               EPI_SYMMLQ_A = 23, EPI_SYMMLQ_B = 24 };
 
 struct CgDevState {
   double gamma;        // r.z of the current iterate              (src/cg.jl:162, 257)
@@ -647,6 +648,154 @@ __host__ __device__ inline bool cgs_step_b(CgsDevState &s, double rho_next, doub
   return s.solved || s.breakdown;
 }
 
+// symmlq! (src/symmlq.jl:132-464), real Float64: the Lanczos scalars, the QR recurrences of Tₖ (and of Tₖ - λest I), the residual
+// and error estimates of the LQ and CG points, the norm estimates and the stopping tests.  As for cgs!: the same steps run on the host
+// (loops 0 and 1) and as the epilogues of the two reductions of an iteration (device-resident loop), so loops 1 and 2 produce the same
+// bits.  Field names follow the reference; NaN stands for its `missing`.
+struct SymmlqDevState {
+  // coefficients the vector kernels read
+  double inv_beta;               // one(T) / β: kdiv!(v, β) carried into the next P1                 (:309)
+  double cz, sz, neg_c, sn;      // cζ, sζ, -c, s: the x and w̅ updates of P1                        (:292-295)
+  double alpha, beta;            // α (λ included) and β: P2 reads -α and -oldβ = -β                 (:300-303)
+  // constants of the solve
+  double lambda, lambda_est;     // λ, λest
+  double beta1, tol, etol, ctol; // β₁, atol + rtol β₁, etol, 1 / conlim                            (:163, :272)
+  // the rotation of the iteration that runs (symmlq_rotation) and the recurrences
+  double c, s, gamma, zeta;      // c, s, γ, ζ                                                       (:287-291)
+  double gbar, dbar;             // γbar, δbar
+  double eps_old, zeta_old, c_old;   // ϵold, ζold, cold
+  double eta, zbar;              // η, ζbar
+  double ANorm2, ANorm, Acond, gmax, gmin, xNorm, xcgNorm, rNorm, rcgNorm, test1;
+  double err, errcg;             // Inf without λest
+  double rhobar, sigbar, rho, cwold, cw, sw;   // the QR factorisation of Tₖ - λest I             (:251-256, :387-394)
+  double hist_rcg, hist_errcg;   // what this iteration pushes to residualscg / errorscg: NaN where the reference pushes missing
+  long long stop_seq, iter, hist_base, hist_cap;
+  double *hist, *hist_cg;        // device history windows of residuals and residualscg (null: no history)
+  int transfer_to_cg, window;
+  int solved, solved_lq, solved_cg, solved_mach, fwd_err, ill_cond_mach, ill_cond_lim, not_pd;
+};
+
+// the host arrays of the window code (:342-374), which runs with λest ≠ 0 only: the workspace's clist, zlist and sprod, and
+// stats.errorscg as it stands before this iteration's push (null without history).  The device-resident loop passes none.
+struct SymmlqWindow {
+  double *clist, *zlist, *sprod, *errorscg;
+};
+
+// (c, s, γ) = sym_givens(γbar, β) ; ηold = η ; ζ = ηold / γ (:287-291) and the coefficients of P1.  Runs on the host before
+// iteration 1 and at the end of symmlq_step_b of an iteration that does not stop: the next P1 finds them in the state.
+__host__ __device__ inline void symmlq_rotation(SymmlqDevState &s) {
+  sym_givens(s.gbar, s.beta, s.c, s.s, s.gamma);
+  s.zeta = s.eta / s.gamma;
+  s.cz = s.c * s.zeta;
+  s.sz = s.s * s.zeta;
+  s.neg_c = -s.c;
+  s.sn = s.s;
+  s.inv_beta = 1.0 / s.beta;
+}
+
+// after vᴴ A v (:300)
+__host__ __device__ inline void symmlq_step_a(SymmlqDevState &st, double vAv) { st.alpha = vAv + st.lambda; }
+
+// after β² = ⟨v, Mv⟩ of the next Lanczos vector (:306-308, :313-430); k = iter.  True when the loop stops (tired / overtimed / the
+// callback are the driver's); not_pd is set when β² < 0 (M not positive definite).
+__host__ __device__ inline bool symmlq_step_b(SymmlqDevState &st, double beta2, long long k, const SymmlqWindow &win) {
+  const double oldbeta = st.beta, alpha = st.alpha, c = st.c, s = st.s, gamma = st.gamma, zeta = st.zeta;
+  const double lest = st.lambda_est;
+  if (beta2 < 0) { st.not_pd = 1; return true; }
+  const double beta = sqrt(beta2);
+  st.beta = beta;
+  st.ANorm2 = st.ANorm2 + alpha * alpha + oldbeta * oldbeta + beta * beta;
+  double psi = 0.0, omegabar = 0.0;
+  if (lest != 0) {
+    const double eta_w = -oldbeta * oldbeta * st.cwold / st.rhobar;
+    const double omega = lest + eta_w;
+    psi = c * st.dbar + s * omega;
+    omegabar = s * st.dbar - c * omega;
+  }
+  const double delta = st.dbar * c + alpha * s;
+  st.gbar = st.dbar * s - alpha * c;
+  const double eps = beta * s;
+  st.dbar = -beta * c;
+  st.eta = -st.eps_old * st.zeta_old - delta * zeta;
+  st.rNorm = sqrt(gamma * gamma * zeta * zeta + st.eps_old * st.eps_old * st.zeta_old * st.zeta_old);
+  st.xNorm = st.xNorm + zeta * zeta;
+  const double nan = __builtin_nan("");                                                       // the reference's missing
+  const bool cg_point = st.gbar != 0;
+  if (cg_point) {
+    st.zbar = st.eta / st.gbar;
+    st.rcgNorm = beta * fabs(s * zeta - c * st.zbar);
+    st.xcgNorm = st.xNorm + st.zbar * st.zbar;
+  }
+  st.hist_rcg = cg_point ? st.rcgNorm : nan;
+  if (st.hist) {
+    const long long idx = k - 1 - st.hist_base;
+    if (idx >= 0 && idx < st.hist_cap) { st.hist[idx] = st.rNorm; st.hist_cg[idx] = st.hist_rcg; }
+  }
+  const int window = st.window;
+  if (window > 0 && lest != 0) {                                                              // :342-374
+    if (k < window && window > 1)
+      for (long long i = k; i < window; ++i) win.sprod[i] = s * win.sprod[i];
+    long long ix = (k - 1) % window;
+    win.clist[ix] = c;
+    win.zlist[ix] = zeta;
+    if (k >= window) {
+      const long long jx = k % window;
+      const double zetabark = win.zlist[jx] / win.clist[jx];
+      if (cg_point) {
+        double theta = 0.0;
+        for (int i = 0; i < window; ++i) theta = theta + win.clist[i] * win.sprod[i] * win.zlist[i];
+        theta = zetabark * fabs(theta) + fabs(zetabark * st.zbar * win.sprod[ix] * s) - zetabark * zetabark;
+        if (win.errorscg) {
+          const double e = win.errorscg[k - window];
+          win.errorscg[k - window] = sqrt(fabs(e * e - 2 * theta));
+        }
+      } else if (win.errorscg) {
+        win.errorscg[k - window] = nan;
+      }
+    }
+    ix = k % window;
+    if (k >= window && window > 1) {
+      const double f = 1.0 / win.sprod[(ix + 1) % window];                                    // kdiv! = kscal!(one(T) / s)
+      for (int i = 0; i < window; ++i) win.sprod[i] = f * win.sprod[i];
+      win.sprod[ix] = win.sprod[(ix - 1 + window) % window] * s;
+    }
+  }
+  if (lest != 0) {                                                                            // :376-395
+    st.err = fabs((st.eps_old * st.zeta_old + psi * zeta) / omegabar);
+    if (cg_point) st.errcg = sqrt(fabs(st.err * st.err - st.zbar * st.zbar));
+    st.hist_errcg = cg_point ? st.errcg : nan;
+    st.rhobar = st.sw * st.sigbar - st.cw * (alpha - lest);
+    st.sigbar = -st.cw * beta;
+    st.rho = sqrt(st.rhobar * st.rhobar + beta * beta);
+    st.cwold = st.cw;
+    st.cw = st.rhobar / st.rho;
+    st.sw = beta / st.rho;
+  }
+  st.gmax = jl_max(st.gmax, gamma);
+  st.gmin = jl_min(st.gmin, gamma);
+  st.Acond = st.gmax / st.gmin;
+  st.ANorm = sqrt(st.ANorm2);
+  st.test1 = st.rNorm / (st.ANorm * st.xNorm);
+  st.eps_old = eps;
+  st.zeta_old = zeta;
+  st.c_old = c;
+  const bool resid_decrease_mach = (1.0 + st.rNorm <= 1.0);                                   // :414-430
+  st.ill_cond_mach = (1.0 + 1.0 / st.Acond <= 1.0) ? 1 : 0;
+  const bool zero_resid_mach = (1.0 + st.test1 <= 1.0);
+  st.ill_cond_lim = (1.0 / st.Acond <= st.ctol) ? 1 : 0;
+  const bool zero_resid_lim = (st.test1 <= st.tol);
+  st.fwd_err = ((st.err <= st.etol) || (cg_point && st.errcg <= st.etol)) ? 1 : 0;
+  st.solved_lq = (st.rNorm <= st.tol) ? 1 : 0;
+  st.solved_cg = (st.transfer_to_cg && cg_point && st.rcgNorm <= st.tol) ? 1 : 0;
+  const bool zero_resid = st.solved_lq || st.solved_cg;
+  const bool ill_cond = st.ill_cond_mach || st.ill_cond_lim;
+  st.solved = (st.solved_mach || zero_resid || zero_resid_mach || zero_resid_lim || st.fwd_err || resid_decrease_mach) ? 1 : 0;
+  st.iter = k;
+  const bool stop = st.solved || ill_cond;
+  if (!stop) symmlq_rotation(st);
+  return stop;
+}
+
 __device__ __forceinline__ bool seq_skip(const long long *stop_seq, long long seq) {
   return stop_seq != nullptr && seq >= *stop_seq;
 }
@@ -786,6 +935,11 @@ __device__ inline void solver_epilogue(int epi, void *state, const double *v, lo
   } else if (epi == EPI_CGS_B) {                   // v = (c.r, r.r)             :230-256
     CgsDevState *st = static_cast<CgsDevState *>(state);
     if (cgs_step_b(*st, v[0], v[1], st->iter + 1)) st->stop_seq = seq + 2;   // P3 of this iteration (seq + 1) still runs (:232-235)
+  } else if (epi == EPI_SYMMLQ_A) {                // v[0] = v.(A v)             src/symmlq.jl:300
+    symmlq_step_a(*static_cast<SymmlqDevState *>(state), v[0]);
+  } else if (epi == EPI_SYMMLQ_B) {                // v[0] = Mv.Mv = β²          :306-430 (λest = 0 here: no window lists)
+    SymmlqDevState *st = static_cast<SymmlqDevState *>(state);
+    if (symmlq_step_b(*st, v[0], st->iter + 1, SymmlqWindow{nullptr, nullptr, nullptr, nullptr})) st->stop_seq = seq + 1;
   }
 }
 
