@@ -745,6 +745,52 @@ int khip_symmlq_last_path(khip_symmlq_workspace *ws);
 double           *khip_symmlq_vector(khip_symmlq_workspace *ws, const char *name);
 size_t            khip_symmlq_workspace_bytes(khip_symmlq_workspace *ws);   /* 5n doubles without M and warm start */
 
+/* ---- minres_qlp! (src/minres_qlp.jl:131-538), real Float64: (A + λI) x = b with A symmetric, possibly indefinite or SINGULAR; on a
+ * singular inconsistent system the iterate is the minimum-length least-squares solution.  MinresQlpWorkspace
+ * (src/krylov_workspaces.jl:713-768): x, wₖ₋₁, wₖ, M⁻¹vₖ₋₁, M⁻¹vₖ, p ("x", "wkm1", "wk", "Mvkm1", "Mvk", "p"); Δx and vₖ ("dx", "vk")
+ * stay empty until a warm start or M needs them.  options.linesearch: KHIP_ERR_UNSUPPORTED; options.variant != 0 is refused (there
+ * is no other recurrence); radius, reorthogonalization and restart are ignored. */
+typedef struct khip_minres_qlp_workspace khip_minres_qlp_workspace;
+typedef struct {
+  double lambda;       /* λ */
+  double Artol;        /* NaN: the reference's default, √eps */
+} khip_minres_qlp_params;
+khip_minres_qlp_params khip_minres_qlp_default_params(void);   /* lambda = 0, Artol = NaN */
+int khip_minres_qlp_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_minres_qlp_workspace **out);
+/* MinresQlpWorkspace on the caller's six vectors; every pointer must be distinct.  adopt_vector names: "dx" (Δx: warm_start! fills
+ * it on the caller's side and hands it over, then khip_minres_qlp_warm_start(ws, dx) only sets the flag), "vk" (needed with M).
+ * The fused loops rotate the roles of (Mvkm1, Mvk, p) where the reference copies and swap those of (wkm1, wk) where it swaps:
+ * khip_minres_qlp_vector returns a name's pointer by its current role, so after a solve every name holds what the reference's
+ * variable of that name holds (p is scratch there: the fused loops leave M⁻¹vₖ₋₂ in it). */
+int khip_minres_qlp_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *x, double *wkm1, double *wk, double *Mvkm1,
+                                    double *Mvk, double *p, khip_minres_qlp_workspace **out);
+int khip_minres_qlp_workspace_adopt_vector(khip_minres_qlp_workspace *ws, const char *name, double *ptr);
+int khip_minres_qlp_workspace_destroy(khip_minres_qlp_workspace *ws);
+int khip_minres_qlp_warm_start(khip_minres_qlp_workspace *ws, const double *x0);
+/* minres_qlp!(ws, A, b; M, λ, atol, rtol, Artol, itmax, timemax, verbose, history, callback).  M == NULL means the identity;
+ * params == NULL: the defaults.  m != n: KHIP_ERR_INVALID "System must be square"; ⟨v, Mv⟩ < 0: KHIP_ERR_NUMERIC "Preconditioner is
+ * not positive definite".  stats.inconsistent is the reference's flag; the status strings are the reference's:
+ *   "found approximate minimum least-squares solution", "found approximate zero-residual solution",
+ *   "solution good enough given atol and rtol", ...
+ * Loops (khip_minres_qlp_last_path): 2 = device-resident (A a CSR handle, M = I, no callback, verbose = 0), 1 = host-driven on the
+ * same kernels (same bits as 2), 0 = one launch per primitive (options.fused = 0).  A callback on loop 1 finds every named vector
+ * in the reference's state of that point (the division of vₖ₊₁ by βₖ₊₁ is not carried forward then). */
+int khip_minres_qlp_solve(khip_minres_qlp_workspace *ws, const khip_operator *A, const khip_operator *M, const double *b,
+                          const khip_options *opts, const khip_minres_qlp_params *params);
+double           *khip_minres_qlp_solution(khip_minres_qlp_workspace *ws);
+const khip_stats *khip_minres_qlp_stats(khip_minres_qlp_workspace *ws);      /* residuals = the reference's stats.residuals */
+/* stats.Aresiduals and stats.Acond of the last solve (history = true), owned by the workspace until its next solve; Acond has one
+ * entry more than Aresiduals (the reference pushes it before the loop as well) */
+int khip_minres_qlp_histories(khip_minres_qlp_workspace *ws, const double **aresiduals, int *naresiduals, const double **acond,
+                              int *nacond);
+int khip_minres_qlp_last_path(khip_minres_qlp_workspace *ws);
+/* 1 when the last solve's Lanczos step (p = A vₖ + λ vₖ - βₖ M⁻¹vₖ₋₁ and αₖ = vₖ.p) ran inside the CSR handle's product, as for
+ * khip_minres_fused_product; 0 when the product and the step were separate passes; -1 without a workspace */
+int khip_minres_qlp_fused_product(khip_minres_qlp_workspace *ws);
+/* named work vectors: "x", "wkm1", "wk", "Mvkm1", "Mvk", "p", "dx", "vk" (NULL while not allocated) */
+double           *khip_minres_qlp_vector(khip_minres_qlp_workspace *ws, const char *name);
+size_t            khip_minres_qlp_workspace_bytes(khip_minres_qlp_workspace *ws);   /* 6n doubles without M and warm start */
+
 int khip_gmres_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, int memory, khip_gmres_workspace **out);
 /* GmresWorkspace on the caller's x, w and basis V_host[0 .. memory) (device pointers in a HOST array; `V::Vector{S}`,
  * src/krylov_workspaces.jl:2857-2873).  adopt_vector names: "x", "w", "p", "q", "dx".  adopt_basis replaces the whole list

@@ -463,6 +463,67 @@ function Krylov.minres!(ws::MinresWs, A::HIPCsr, b::HIPVector; M = I, ldiv::Bool
   return ws
 end
 
+# ------------------------------------------------------------------------------------------------ minres_qlp!  (src/minres_qlp.jl:131-538)
+struct MinresQlpParams              # khip_minres_qlp_params: λ, Artol
+  lambda::Cdouble; Artol::Cdouble
+end
+const MinresQlpWs = MinresQlpWorkspace{Float64,Float64,HIPVector}
+function minres_qlp_handle(ws::MinresQlpWs)
+  get!(HANDLES, ws) do
+    r = Ref{Ptr{Cvoid}}()
+    ck(ccall((:khip_minres_qlp_workspace_adopt, lib), Cint,
+             (Ptr{Cvoid}, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Ptr{Cvoid}}),
+             CTX[].h, ws.m, ws.n, ws.x.ptr, ws.wₖ₋₁.ptr, ws.wₖ.ptr, ws.M⁻¹vₖ₋₁.ptr, ws.M⁻¹vₖ.ptr, ws.p.ptr, r))
+    h = r[]
+    finalizer(_ -> ccall((:khip_minres_qlp_workspace_destroy, lib), Cint, (Ptr{Cvoid},), h), ws)
+    h
+  end
+end
+minres_qlp_adopt(h, name, v::HIPVector) = ck(ccall((:khip_minres_qlp_workspace_adopt_vector, lib), Cint, (Ptr{Cvoid}, Cstring, Ptr{Cdouble}), h, name, dptr(v)))
+
+# The fused loops rotate the roles of (M⁻¹vₖ₋₁, M⁻¹vₖ, p) and swap those of (wₖ₋₁, wₖ): after the solve only x and the stats are defined
+# on this side.  linesearch (nonpositive curvature, npc_dir) is the generic method's.
+function Krylov.minres_qlp!(ws::MinresQlpWs, A::HIPCsr, b::HIPVector; M = I, ldiv::Bool = false, linesearch::Bool = false, λ::Float64 = 0.0,
+                            atol::Float64 = √eps(Float64), rtol::Float64 = √eps(Float64), Artol::Float64 = √eps(Float64),
+                            itmax::Int = 0, timemax::Float64 = Inf, verbose::Int = 0, history::Bool = false, callback = nothing,
+                            iostream::IO = Krylov.kstdout, fused::Int = 2)
+  if ldiv || linesearch || !native_precond(M) || !native_log(verbose, iostream)
+    GENERIC_SOLVES[] += 1
+    return invoke(Krylov.minres_qlp!, Tuple{MinresQlpWs,Any,AbstractVector{Float64}}, ws, A, b; M, ldiv, linesearch, λ, atol, rtol, Artol,
+                  itmax, timemax, verbose, history, callback = callback === nothing ? (w -> false) : callback, iostream)
+  end
+  m, n = size(A)                                                                            # :137-140
+  (m == ws.m && n == ws.n) || error("(workspace.m, workspace.n) = ($(ws.m), $(ws.n)) is inconsistent with size(A) = ($m, $n)")
+  m == n || error("System must be square")
+  length(b) == m || error("Inconsistent problem size")
+  Krylov.allocate_if(M !== I, ws, :vₖ, HIPVector, ws.x)                                       # :152
+  h = minres_qlp_handle(ws)
+  for (name, v) in (("vk", ws.vₖ), ("dx", ws.Δx))
+    minres_qlp_adopt(h, name, v)
+  end
+  ws.warm_start && ck(ccall((:khip_minres_qlp_warm_start, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h, ws.Δx.ptr))
+  sp = ccall((:khip_minres_qlp_stats, lib), Ptr{Stats}, (Ptr{Cvoid},), h)
+  cbf, cbd, box = callback_args(user_callback(callback), ws, sp, history)
+  opts = Ref(Options(; atol, rtol, itmax, timemax, history, fused, verbose, log_fd = logfd(iostream), callback = cbf, callback_data = cbd))
+  prm = Ref(MinresQlpParams(λ, Artol))
+  opA = Ref(Operator(A))
+  rc = GC.@preserve ws A b M opts prm opA box ccall((:khip_minres_qlp_solve, lib), Cint,
+                                                     (Ptr{Cvoid}, Ref{Operator}, Ptr{Operator}, Ptr{Cdouble}, Ref{Options}, Ptr{Cvoid}),
+                                                     h, opA, opref(M), b.ptr, opts, prm)
+  st = fill_stats!(ws.stats, sp, history)
+  if history                                                                                # stats.Aresiduals, stats.Acond
+    ar, nar, ac, nac = Ref{Ptr{Cvoid}}(), Ref{Cint}(0), Ref{Ptr{Cvoid}}(), Ref{Cint}(0)
+    ck(ccall((:khip_minres_qlp_histories, lib), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Cint}, Ref{Ptr{Cvoid}}, Ref{Cint}), h, ar, nar, ac, nac))
+    nar[] > 0 && append!(ws.stats.Aresiduals, unsafe_wrap(Array, Ptr{Float64}(ar[]), Int(nar[])))
+    nac[] > 0 && append!(ws.stats.Acond, unsafe_wrap(Array, Ptr{Float64}(ac[]), Int(nac[])))
+  end
+  NATIVE_SOLVES[] += 1;  LAST_PATH[] = ccall((:khip_minres_qlp_last_path, lib), Cint, (Ptr{Cvoid},), h)
+  ws.warm_start = false
+  finish_callback(box)
+  rc == 0 || failed(st)
+  return ws
+end
+
 # ------------------------------------------------------------------------------------------------ bilq!  (src/bilq.jl:118-407)
 struct BilqParams                   # khip_bilq_params: transfer_to_bicg, the adjoints of M and N (NULL: the operator itself)
   transfer_to_bicg::Cint; Mt::Ptr{Operator}; Nt::Ptr{Operator}

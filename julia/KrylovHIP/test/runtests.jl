@@ -268,3 +268,4 @@ end
 include("bilqr.jl")                                                  # bilqr! against the generic method, its breakdowns and statuses
 include("cgs.jl")                                                    # cgs! against the generic method, its endings and breakdowns
 include("symmlq.jl")                                                 # symmlq! against the generic method, its histories and error estimates
+include("minres_qlp.jl")                                             # minres_qlp! against the generic method, singular and inconsistent systems

@@ -63,6 +63,10 @@ class CSymmlqParams(C.Structure):
                 ("transfer_to_cg", C.c_int)]
 
 
+class CMinresQlpParams(C.Structure):
+    _fields_ = [("lambda_", C.c_double), ("Artol", C.c_double)]
+
+
 class CLanczosShiftParams(C.Structure):
     _fields_ = [("shifts", c_double_p), ("nshifts", C.c_int), ("check_curvature", C.c_int)]
 
@@ -314,6 +318,21 @@ SIGNATURES = {
     "khip_symmlq_last_path": (_int, [_vp]),
     "khip_symmlq_vector": (_vp, [_vp, C.c_char_p]),
     "khip_symmlq_workspace_bytes": (_sz, [_vp]),
+    "khip_minres_qlp_default_params": (CMinresQlpParams, []),
+    "khip_minres_qlp_workspace_create": (_int, [_vp, _i64, _i64, c_void_pp]),
+    "khip_minres_qlp_workspace_adopt": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, c_void_pp]),
+    "khip_minres_qlp_workspace_adopt_vector": (_int, [_vp, C.c_char_p, _vp]),
+    "khip_minres_qlp_workspace_destroy": (_int, [_vp]),
+    "khip_minres_qlp_warm_start": (_int, [_vp, _vp]),
+    "khip_minres_qlp_solve": (_int, [_vp, C.POINTER(COperator), C.POINTER(COperator), _vp, C.POINTER(COptions),
+                                     C.POINTER(CMinresQlpParams)]),
+    "khip_minres_qlp_solution": (_vp, [_vp]),
+    "khip_minres_qlp_stats": (C.POINTER(CStats), [_vp]),
+    "khip_minres_qlp_histories": (_int, [_vp, C.POINTER(c_double_p), C.POINTER(_int), C.POINTER(c_double_p), C.POINTER(_int)]),
+    "khip_minres_qlp_last_path": (_int, [_vp]),
+    "khip_minres_qlp_fused_product": (_int, [_vp]),
+    "khip_minres_qlp_vector": (_vp, [_vp, C.c_char_p]),
+    "khip_minres_qlp_workspace_bytes": (_sz, [_vp]),
     "khip_bilqr_default_params": (CBilqrParams, []),
     "khip_bilqr_workspace_create": (_int, [_vp, _i64, _i64, c_void_pp]),
     "khip_bilqr_workspace_adopt": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_void_pp]),
@@ -1721,6 +1740,47 @@ class SymmlqWorkspace(_Workspace):
         return DeviceVector(self.ctx, self.n, ptr=p, owner=self) if p else None
 
 
+class MinresQlpWorkspace(_Workspace):
+    """MinresQlpWorkspace(m, n, S) (src/krylov_workspaces.jl:713-768): x, wₖ₋₁, wₖ, M⁻¹vₖ₋₁, M⁻¹vₖ, p ("wkm1", "wk", "Mvkm1", "Mvk");
+    Δx and vₖ ("dx", "vk") stay empty until needed.  stats carries Aresiduals and Acond (one entry more than Aresiduals).  The fused
+    loops rotate the roles of (Mvkm1, Mvk, p) and swap those of (wkm1, wk), and `vector(name)` follows the role
+    (khip_minres_qlp_vector): after a solve a name holds what the reference's variable of that name holds."""
+    _prefix = "minres_qlp"
+    VECTORS = ("x", "wkm1", "wk", "Mvkm1", "Mvk", "p")
+
+    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
+        self.ctx, self.m, self.n = ctx, m, n
+        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
+        self._h = C.c_void_p()
+        if self.adopted:
+            t0 = time.perf_counter()
+            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(n) for k in self.VECTORS}     # dx, vk stay empty
+            self._alloc_s = time.perf_counter() - t0
+            _ck(lib().khip_minres_qlp_workspace_adopt(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
+        else:
+            _ck(lib().khip_minres_qlp_workspace_create(ctx._h, m, n, C.byref(self._h)))
+
+    @property
+    def stats(self) -> SimpleStats:
+        st = super().stats
+        ar, nar, ac, nac = c_double_p(), _int(), c_double_p(), _int()
+        _ck(lib().khip_minres_qlp_histories(self._h, C.byref(ar), C.byref(nar), C.byref(ac), C.byref(nac)))
+        st.Aresiduals = np.array(ar[:nar.value]) if nar.value else np.zeros(0)
+        st.Acond = np.array(ac[:nac.value]) if nac.value else np.zeros(0)
+        return st
+
+    @property
+    def fused_product(self) -> bool:
+        """The last solve's Lanczos step ran inside the sliced SpMV (khip_minres_qlp_fused_product)."""
+        return lib().khip_minres_qlp_fused_product(self._h) == 1
+
+    def vector(self, name: str):
+        if name == "x":
+            return self.x
+        p = lib().khip_minres_qlp_vector(self._h, name.encode())
+        return DeviceVector(self.ctx, self.n, ptr=p, owner=self) if p else None
+
+
 class BilqrWorkspace(_BiLanczosWorkspace):
     """BilqrWorkspace(m, n, S) (src/krylov_workspaces.jl:1818-1836): uₖ₋₁, uₖ, q, vₖ₋₁, vₖ, p, x, y, d̅, wₖ₋₃, wₖ₋₂; Δx and Δy stay empty
     until a warm start."""
@@ -1865,6 +1925,23 @@ def symmlq_(ws: SymmlqWorkspace, A, b: DeviceVector, M=None, transfer_to_cg=True
     return _finish(ws, rc)
 
 
+def minres_qlp_(ws: MinresQlpWorkspace, A, b: DeviceVector, M=None, λ=0.0, Artol=None, **kw):
+    """minres_qlp!(workspace, A, b; M, ldiv, linesearch, λ, atol, rtol, Artol, itmax, timemax, verbose, history, callback, iostream)
+    (src/minres_qlp.jl:131-538).  linesearch = true is refused (KHIP_ERR_UNSUPPORTED).  Returns the workspace."""
+    keep = []
+    if len(b) != ws.n:
+        raise KhipError(-1, "Inconsistent problem size")                                  # src/minres_qlp.jl:140
+    ws._allocate_if(M is not None, "vk")                                                  # src/minres_qlp.jl:152
+    opts = _make_options(keep=keep, ws=ws, **kw)
+    prm = lib().khip_minres_qlp_default_params()
+    prm.lambda_ = float(λ)
+    if Artol is not None:
+        prm.Artol = Artol
+    rc = lib().khip_minres_qlp_solve(ws._h, _make_operator(ws.ctx, A, ws.n, keep), _make_operator(ws.ctx, M, ws.n, keep), _p(b),
+                                     C.byref(opts), C.byref(prm))
+    return _finish(ws, rc)
+
+
 def cg_lanczos_shift_(ws: CgLanczosShiftWorkspace, A, b: DeviceVector, shifts, M=None, ldiv=False, check_curvature=False, **kw):
     """cg_lanczos_shift!(workspace, A, b, shifts; M, ldiv, check_curvature, atol, rtol, itmax, timemax, verbose, history, callback,
     iostream) (src/cg_lanczos_shift.jl:107-284).  Returns the workspace."""
@@ -2000,6 +2077,8 @@ FORWARDED_DEFAULTS = {
     "symmlq": dict(M=None, ldiv=False, transfer_to_cg=True, λ=0.0, λest=0.0, atol=_SQRT_EPS, rtol=_SQRT_EPS, etol=_SQRT_EPS,
                    conlim=1.0 / _SQRT_EPS, itmax=0, timemax=math.inf, verbose=0, history=False, callback=default_callback,
                    iostream=None),
+    "minres_qlp": dict(M=None, ldiv=False, linesearch=False, λ=0.0, atol=_SQRT_EPS, rtol=_SQRT_EPS, Artol=_SQRT_EPS, itmax=0,
+                       timemax=math.inf, verbose=0, history=False, callback=default_callback, iostream=None),
     "bilqr": dict(transfer_to_bicg=True, atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0, timemax=math.inf, verbose=0, history=False,
                   callback=default_callback, iostream=None),
 }
@@ -2028,7 +2107,7 @@ def krylov_workspace(method: str, *args, ctx: Context | None = None, **kw):
     cls = {"cg": CgWorkspace, "gmres": GmresWorkspace, "bicgstab": BicgstabWorkspace, "block_gmres": BlockGmresWorkspace,
            "minres": MinresWorkspace, "cg_lanczos_shift": CgLanczosShiftWorkspace, "bilq": BilqWorkspace,
            "qmr": QmrWorkspace, "bilqr": BilqrWorkspace, "cgs": CgsWorkspace,
-           "symmlq": SymmlqWorkspace}[method]
+           "symmlq": SymmlqWorkspace, "minres_qlp": MinresQlpWorkspace}[method]
     if method == "cg_lanczos_shift":                                            # (A, b, nshifts) / (m, n, nshifts)
         if isinstance(args[1], DeviceVector):
             A, b, nshifts = args
@@ -2139,6 +2218,11 @@ def cgs(A, b: DeviceVector, x0=None, **kw):
 def symmlq(A, b: DeviceVector, x0=None, **kw):
     """Out-of-place symmlq(A, b[, x0]; window, kwargs...) -> (x, stats, workspace) (src/symmlq.jl:16-22)."""
     return krylov_solve("symmlq", A, b, x0, **kw)
+
+
+def minres_qlp(A, b: DeviceVector, x0=None, **kw):
+    """Out-of-place minres_qlp(A, b[, x0]; kwargs...) -> (x, stats, workspace) (src/minres_qlp.jl:20-26)."""
+    return krylov_solve("minres_qlp", A, b, x0, **kw)
 
 
 def bilqr(A, b: DeviceVector, c: DeviceVector, x0=None, y0=None, **kw):
@@ -2611,5 +2695,6 @@ _INPLACE.update({CgWorkspace: ("cg", cg_), GmresWorkspace: ("gmres", gmres_), Bi
                  BlockGmresWorkspace: ("block_gmres", block_gmres_), MinresWorkspace: ("minres", minres_), BilqWorkspace: ("bilq", bilq_),
                  QmrWorkspace: ("qmr", qmr_), CgsWorkspace: ("cgs", cgs_),
                  SymmlqWorkspace: ("symmlq", symmlq_),
+                 MinresQlpWorkspace: ("minres_qlp", minres_qlp_),
                  BilqrWorkspace: ("bilqr", bilqr_),
                  CgLanczosShiftWorkspace: ("cg_lanczos_shift", cg_lanczos_shift_)})

@@ -18,7 +18,7 @@ enum Epilogue { EPI_NONE = 0, EPI_CG_STEP1 = 1, EPI_CG_STEP2 = 2, EPI_BICG_A = 3
                EPI_MINRES_A = 7, EPI_MINRES_B = 8, EPI_MINRES_C = 9, EPI_LZSHIFT_A = 10, EPI_LZSHIFT_B = 11,
                EPI_BILQ_A = 12, EPI_BILQ_B = 13, EPI_BILQ_C = 14, EPI_QMR_A = 15, EPI_QMR_B = 16, EPI_QMR_C = 17,
                EPI_BILQR_A = 18, EPI_BILQR_B = 19, EPI_BILQR_C = 20, EPI_CGS_A = 21, EPI_CGS_B = 22,
-               EPI_SYMMLQ_A = 23, EPI_SYMMLQ_B = 24 };
+               EPI_SYMMLQ_A = 23, EPI_SYMMLQ_B = 24, EPI_MINRES_QLP_X = 25, EPI_MINRES_QLP_A = 26, EPI_MINRES_QLP_B = 27 };
 
 struct CgDevState {
   double gamma;        // r.z of the current iterate              (src/cg.jl:162, 257)
@@ -796,6 +796,171 @@ __host__ __device__ inline bool symmlq_step_b(SymmlqDevState &st, double beta2, 
   return stop;
 }
 
+// minres_qlp! (src/minres_qlp.jl:131-538), real Float64, linesearch = false: the Lanczos scalars, the QR factorisation of Tₖ₊₁.ₖ, the LQ
+// factorisation of Rₖ, the solve with Lₖ, the norm estimates and the stopping tests.  As for symmlq!: the same steps run on the host
+// (loops 0 and 1) and as the epilogues of the three reductions of an iteration (device-resident loop), so loops 1 and 2 produce the
+// same bits.  Field names follow the reference; the suffixes 1 and 2 stand for its subscripts k-1 and k-2.
+struct MinresQlpDevState {
+  // the Lanczos product's coefficients, contiguous: the sliced SpMV reads them as SpmvArgs::lz_coef[0..2]
+  double lambda;                 // λ                                                               (:248)
+  double one;                    // 1.0: the product is not divided here (multiplication by 1.0 is exact)
+  double neg_beta;               // -βₖ                                                             (:252)
+  // coefficients the vector kernels read
+  double inv_beta;               // one(T) / βₖ: kdiv!(vₖ₊₁, βₖ₊₁) carried into the next P1          (:265)
+  double cpt, spt, neg_cp, sp;   // cpₖ τₖ₋₂, spₖ τₖ₋₂, -cpₖ, spₖ: x and wₐᵤₓ in P1 (k ≥ 3), the two outputs of P2 at k = 2 (:417-430)
+  double cp;                     // cpₖ                                                             (:419)
+  double neg_alpha, cd, sd;      // -αₖ, cdₖ, sdₖ: P2                                               (:257, :433)
+  // constants of the solve
+  double eps_tol, atol, Artol, btol, kappa;   // ε, atol, Artol, eps^(3/4), κ                     (:206, :224, :450)
+  int MisI;
+  // recurrences
+  double alpha, beta;            // αₖ; βₖ, after step B βₖ₊₁
+  double gbar1, gamma1, lambar, lam;   // γbarₖ₋₁, γₖ₋₁, λbarₖ, λₖ
+  double c2, c1, c, s2, s1, s;   // cₖ₋₂, cₖ₋₁, cₖ, sₖ₋₂, sₖ₋₁, sₖ
+  double zbar;                   // ζbarₖ
+  double xi1;                    // ξₖ₋₁
+  double tau2, tau1, tau;        // τₖ₋₂, τₖ₋₁, τₖ
+  double psibar2, mubis2, mubar1;   // ψbarₖ₋₂, μbisₖ₋₂, μbarₖ₋₁
+  double mu2, mubis1, psi2, theta, mubar;   // μₖ₋₂, μbisₖ₋₁, ψₖ₋₂, θₖ, μbarₖ (of the iteration that runs)
+  double ANorm2, ANorm, Acond, mumin, mumax, xNorm, rNorm, ArNorm, backward;
+  long long stop_seq, iter, hist_base, hist_cap;
+  double *hist_r, *hist_ar, *hist_acond;   // device history windows (null: no history)
+  int solved, zero_resid, inconsistent, ill_cond_mach, breakdown, not_pd;
+};
+
+// What iteration k = s.iter + 1 ≥ 3 knows before its product: ϵₖ₋₂, γbarₖ₋₁ (:291-292), (cpₖ, spₖ, μₖ₋₂) (:370) and τₖ₋₂ (:400-401) depend
+// on βₖ and on earlier scalars only; for k = 2, γbarₖ₋₁ = βₖ (:296).  Runs at the end of minres_qlp_step_b of an iteration that does
+// not stop: the next P1 and the next product find their coefficients in the state.
+__host__ __device__ inline void minres_qlp_ahead(MinresQlpDevState &s, long long k) {
+  if (k >= 3) {
+    const double eps2 = s.s2 * s.beta;
+    s.gbar1 = -s.c2 * s.beta;
+    double cp, sp;
+    sym_givens(s.mubis2, eps2, cp, sp, s.mu2);
+    s.cp = cp;
+    s.sp = sp;
+    s.neg_cp = -cp;
+    s.tau2 = s.tau1;
+    s.tau2 = s.tau2 * s.mubis2 / s.mu2;
+    s.cpt = cp * s.tau2;
+    s.spt = sp * s.tau2;
+  } else if (k == 2) {
+    s.gbar1 = s.beta;
+  }
+  s.inv_beta = 1.0 / s.beta;
+  s.neg_beta = -s.beta;
+}
+
+// after αₖ = ⟨vₖ, p⟩ (:255, :287-302, and what of :358-382 needs αₖ only); k = iter
+__host__ __device__ inline void minres_qlp_step_a(MinresQlpDevState &s, double alpha, long long k) {
+  s.alpha = alpha;
+  s.neg_alpha = -alpha;
+  if (k >= 2) {
+    s.gamma1 = s.c1 * s.gbar1 + s.s1 * alpha;
+    s.lambar = s.s1 * s.gbar1 - s.c1 * alpha;
+  } else {
+    s.lambar = alpha;
+  }
+  if (k == 2) {
+    double cp, sp;
+    sym_givens(s.mubar1, s.gamma1, cp, sp, s.mubis1);
+    s.cp = cp;
+    s.sp = sp;
+    s.neg_cp = -cp;
+  } else if (k >= 3) {
+    s.psi2 = s.cp * s.psibar2 + s.sp * s.gamma1;
+    s.theta = s.sp * s.psibar2 - s.cp * s.gamma1;
+    sym_givens(s.mubar1, s.theta, s.cd, s.sd, s.mubis1);
+  }
+}
+
+// after βₖ₊₁² = ⟨vₖ₊₁, p⟩ and xNorm = ‖x‖ (:261-269, :333-405 but for step A's part, :442-504); k = iter.  True when the loop stops
+// (tired / overtimed / the callback are the driver's); not_pd is set when β² < 0 (M not positive definite).
+__host__ __device__ inline bool minres_qlp_step_b(MinresQlpDevState &st, double beta2, double xNorm, long long k) {
+  const double epsM = 2.220446049250313e-16;
+  if (beta2 < 0) { st.not_pd = 1; return true; }
+  const double beta = st.beta, alpha = st.alpha;
+  const double beta_next = sqrt(beta2);
+  st.ANorm2 = st.ANorm2 + alpha * alpha + beta * beta + beta_next * beta_next;                // :269
+  sym_givens(st.lambar, beta_next, st.c, st.s, st.lam);                                       // :333
+  const double zeta = st.c * st.zbar;                                                         // :340-341
+  const double zbar_next = st.s * st.zbar;
+  double psibar1 = 0.0, rho2 = 0.0;
+  if (k == 1) {                                                                               // :358-382
+    st.mubar = st.lam;
+  } else if (k == 2) {
+    psibar1 = st.sp * st.lam;
+    st.mubar = -st.cp * st.lam;
+  } else {
+    rho2 = st.sp * st.lam;
+    const double eta = -st.cp * st.lam;
+    psibar1 = st.sd * eta;
+    st.mubar = -st.cd * eta;
+  }
+  double xi = 0.0;
+  if (k == 1) {                                                                               // :392-405
+    st.tau = zeta / st.mubar;
+  } else if (k == 2) {
+    st.tau1 = st.tau;
+    st.tau1 = st.tau1 * st.mubar1 / st.mubis1;
+    xi = zeta;
+    st.tau = (xi - psibar1 * st.tau1) / st.mubar;
+  } else {
+    st.tau1 = (st.xi1 - st.psi2 * st.tau2) / st.mubis1;
+    xi = zeta - rho2 * st.tau2;
+    st.tau = (xi - psibar1 * st.tau1) / st.mubar;
+  }
+  st.rNorm = fabs(zbar_next);                                                                 // :444
+  const double cb = st.c1 * beta_next;
+  st.ArNorm = fabs(st.zbar) * sqrt(st.lambar * st.lambar + cb * cb);                          // :449
+  if (k == 1) st.kappa = st.atol + st.Artol * st.ArNorm;
+  st.ANorm = sqrt(st.ANorm2);                                                                 // :453-466
+  const double abs_mubar = fabs(st.mubar);
+  if (k == 1) {
+    st.mumin = abs_mubar;
+    st.mumax = abs_mubar;
+  } else if (k == 2) {
+    st.mumax = jl_max(jl_max(st.mumax, st.mubis1), abs_mubar);
+    st.mumin = jl_min(jl_min(st.mumin, st.mubis1), abs_mubar);
+  } else {
+    st.mumax = jl_max(jl_max(jl_max(st.mumax, st.mu2), st.mubis1), abs_mubar);
+    st.mumin = jl_min(jl_min(jl_min(st.mumin, st.mu2), st.mubis1), abs_mubar);
+  }
+  st.Acond = st.mumax / st.mumin;
+  st.xNorm = xNorm;                                                                           // :468-469
+  st.backward = st.rNorm / (st.ANorm * xNorm);
+  if (st.hist_r) {
+    const long long idx = k - 1 - st.hist_base;
+    if (idx >= 0 && idx < st.hist_cap) { st.hist_r[idx] = st.rNorm; st.hist_ar[idx] = st.ArNorm; st.hist_acond[idx] = st.Acond; }
+  }
+  st.ill_cond_mach = (1.0 + 1.0 / st.Acond <= 1.0) ? 1 : 0;                                   // :474-488
+  const bool resid_decrease_mach = (1.0 + st.rNorm <= 1.0);
+  const bool zero_resid_mach = (1.0 + st.backward <= 1.0);
+  const bool resid_decrease_lim = (st.rNorm <= st.eps_tol);
+  const bool zero_resid_lim = st.MisI && (st.backward <= epsM);
+  st.breakdown = (beta_next <= st.btol) ? 1 : 0;
+  st.zero_resid = (zero_resid_mach || zero_resid_lim) ? 1 : 0;
+  const bool resid_decrease = resid_decrease_mach || resid_decrease_lim;
+  st.solved = (resid_decrease || st.zero_resid) ? 1 : 0;
+  st.inconsistent = ((st.ArNorm <= st.kappa && abs_mubar <= st.Artol) || (st.breakdown && !st.solved)) ? 1 : 0;
+  if (k >= 2) {                                                                               // :493-504
+    st.s2 = st.s1;
+    st.c2 = st.c1;
+    st.xi1 = xi;
+    st.mubis2 = st.mubis1;
+    st.psibar2 = psibar1;
+  }
+  st.s1 = st.s;
+  st.c1 = st.c;
+  st.mubar1 = st.mubar;
+  st.zbar = zbar_next;
+  st.beta = beta_next;
+  st.iter = k;
+  const bool stop = st.solved || st.inconsistent || st.ill_cond_mach || st.breakdown;
+  if (!stop) minres_qlp_ahead(st, k + 1);
+  return stop;
+}
+
 __device__ __forceinline__ bool seq_skip(const long long *stop_seq, long long seq) {
   return stop_seq != nullptr && seq >= *stop_seq;
 }
@@ -940,6 +1105,14 @@ __device__ inline void solver_epilogue(int epi, void *state, const double *v, lo
   } else if (epi == EPI_SYMMLQ_B) {                // v[0] = Mv.Mv = β²          :306-430 (λest = 0 here: no window lists)
     SymmlqDevState *st = static_cast<SymmlqDevState *>(state);
     if (symmlq_step_b(*st, v[0], st->iter + 1, SymmlqWindow{nullptr, nullptr, nullptr, nullptr})) st->stop_seq = seq + 1;
+  } else if (epi == EPI_MINRES_QLP_X) {            // v[0] = x.x                 src/minres_qlp.jl:468
+    static_cast<MinresQlpDevState *>(state)->xNorm = sqrt(v[0]);
+  } else if (epi == EPI_MINRES_QLP_A) {            // v[0] = ⟨vₖ, p⟩ = αₖ         :255, :287-302
+    MinresQlpDevState *st = static_cast<MinresQlpDevState *>(state);
+    minres_qlp_step_a(*st, v[0], st->iter + 1);
+  } else if (epi == EPI_MINRES_QLP_B) {            // v[0] = p.p = βₖ₊₁²         :261-504
+    MinresQlpDevState *st = static_cast<MinresQlpDevState *>(state);
+    if (minres_qlp_step_b(*st, v[0], st->xNorm, st->iter + 1)) st->stop_seq = seq + 1;
   }
 }
 

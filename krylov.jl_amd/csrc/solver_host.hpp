@@ -235,6 +235,11 @@ void set_history(MinresDevState &s, double *w) {
   s.hist_ar = w ? w + kHistWindowMax : nullptr;
   s.hist_acond = w ? w + 2 * kHistWindowMax : nullptr;
 }
+void set_history(MinresQlpDevState &s, double *w) {
+  s.hist_r = w;
+  s.hist_ar = w ? w + kHistWindowMax : nullptr;
+  s.hist_acond = w ? w + 2 * kHistWindowMax : nullptr;
+}
 void set_history(SymmlqDevState &s, double *w) {
   s.hist = w;
   s.hist_cg = w ? w + kHistWindowMax : nullptr;
