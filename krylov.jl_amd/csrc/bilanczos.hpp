@@ -179,16 +179,7 @@ struct BiLanczos {
     snprintf(msg, sizeof(msg), "%s_solve: At (the adjoint of A) is required", solver);
     if (!At) return ws->box.fail(KHIP_ERR_INVALID, msg);
     if (missing) return ws->box.fail(KHIP_ERR_INVALID, missing);
-    for (const khip_operator *op : {A, At}) {
-      if (!(op->csr && !op->apply)) continue;
-      int64_t am, an;
-      khip_csr_shape(op->csr, &am, &an, nullptr);
-      if (am != ws->m || (an != ws->n && !op->csr->dist)) {             // a row-partitioned handle counts global columns
-        snprintf(msg, sizeof(msg), "(workspace.m, workspace.n) = (%lld, %lld) is inconsistent with size(A) = (%lld, %lld)",
-                 (long long)ws->m, (long long)ws->n, (long long)am, (long long)an);
-        return ws->box.fail(KHIP_ERR_INVALID, msg);
-      }
-    }
+    if (int rc = check_shape(ws, {A, At})) return rc;
     if (ws->m != ws->n) return ws->box.fail(KHIP_ERR_INVALID, square);
     return KHIP_OK;
   }
@@ -205,8 +196,7 @@ struct BiLanczos {
   int residual(const double *b, bool warm_start, const double **r0) {
     *r0 = b;
     if (warm_start) {
-      K(apply_op(ctx, A, ws->dx, r.q));
-      K(khip_axpby(ctx, n, 1.0, b, -1.0, r.q));
+      K(residual0(ws, A, 0.0, b, true, r.q));
       *r0 = r.q;
     }
     if (M) {
@@ -221,13 +211,7 @@ struct BiLanczos {
       K(khip_copy(ctx, n, s_tmp, ws->x));
       K(apply_op(ctx, N, s_tmp, ws->x));
     }
-    if (warm_start) K(khip_axpy(ctx, n, 1.0, ws->dx, ws->x));
-    ws->box.st.niter = (int)iter;
-    ws->box.st.solved = solved;
-    ws->box.st.inconsistent = 0;
-    snprintf(ws->box.st.status, sizeof(ws->box.st.status), "%s", status);
-    finish();
-    return KHIP_OK;
+    return ws_end(ws, {iter, solved, 0, status, warm_start, t0, false});
   }
 
   // βₖ, γₖ from cᴴr₀ and the first Lanczos vectors (src/bilq.jl:204-209)
@@ -283,12 +267,8 @@ struct BiLanczos {
   // the end of an iteration on the host-driven loops (src/bilq.jl:347, :367-374)
   void host_tail(int64_t k) {
     if (history) pol.push_history(ws, s);
-    if (o.callback) {
-      ws->box.publish();                          // the callback reads stats.residuals
-      user_exit = o.callback(ws, o.callback_data) != 0;
-    }
     tired = k >= itmax;
-    overtimed = time_limit_reached(ctx, now_s() - t0, timemax);
+    host_exit(ws, o, t0, timemax, &user_exit, &overtimed);
     if (kdisplay(k, o.verbose)) pol.verbose_row(o, k, s, t0);
   }
 
@@ -347,39 +327,24 @@ struct BiLanczos {
       P dpol = pol;
       auto step = [&](State *dev, long long j) {
         const int64_t k = j + 1;
-        ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 1, EPI_NONE, nullptr};
-        int rc = spmv_any(ctx, A->csr, d.v, d.q, -1);                                     // q = A vₖ
-        if (rc == KHIP_OK) rc = spmv_any(ctx, At->csr, d.u, d.p, -1);                     // p = A' uₖ
-        if (rc != KHIP_OK) return rc;
-        ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 2, P::kEpiA, dev};
-        int slot = take_slots(ctx, 1);
-        rc = launch_p1(ctx, n, dev, d.v_prev, d.u_prev, d.u, d.q, d.p, slot);            // P1 ; u.q -> α
-        if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-        if (rc != KHIP_OK) return rc;
-        ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 3, P::kEpiB, dev};
-        slot = take_slots(ctx, 1);
-        rc = launch_p2(ctx, n, dev, d.v, d.u, d.q, d.p, slot);                           // P2 ; p.q -> the solver's update
-        if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-        if (rc != KHIP_OK) return rc;
-        ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 4, P::kEpiC, dev};
-        slot = take_slots(ctx, P::kP3Sums);
-        rc = dpol.p3(ctx, n, dev, d, k, slot);                                           // P3 ; its sums -> the tests
-        if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, P::kP3Sums);
-        ctx->ctl = SeqCtl{};
-        if (rc != KHIP_OK) return rc;
+        KHIP_TRY(dev_pass(ctx, &dev->stop_seq, 4 * j + 1, EPI_NONE, nullptr, [&] {       // both products under one number
+          const int rc = spmv_any(ctx, A->csr, d.v, d.q, -1);                            // q = A vₖ
+          return rc != KHIP_OK ? rc : spmv_any(ctx, At->csr, d.u, d.p, -1); }));         // p = A' uₖ
+        KHIP_TRY(dev_stage(ctx, dev, 4 * j + 2, P::kEpiA, 1, [&](int slot) {
+          return launch_p1(ctx, n, dev, d.v_prev, d.u_prev, d.u, d.q, d.p, slot); }));   // P1 ; u.q -> α
+        KHIP_TRY(dev_stage(ctx, dev, 4 * j + 3, P::kEpiB, 1, [&](int slot) {
+          return launch_p2(ctx, n, dev, d.v, d.u, d.q, d.p, slot); }));                  // P2 ; p.q -> the solver's update
+        KHIP_TRY(dev_stage(ctx, dev, 4 * j + 4, P::kEpiC, P::kP3Sums, [&](int slot) {
+          return dpol.p3(ctx, n, dev, d, k, slot); }));                                  // P3 ; its sums -> the tests
         d.rotate();
         dpol.rotate(k, false);
         return (int)KHIP_OK;
       };
-      // a finite timemax: the first chunk is ONE iteration, so that a limit already used up stops after iteration 1 as the
-      // host-driven loop does
-      const DeviceLoopArgs loop_args{itmax, t0, timemax, history, {&ws->box.residuals, P::dual_history(ws), nullptr},
-                                     timemax < 1e300 ? 1 : kDevChunk};
-      K(ws->loop.run(ctx, s, loop_args, step, &s, &overtimed));
+      K(ws->loop.run(ctx, s, device_loop_args(itmax, t0, timemax, history, {&ws->box.residuals, P::dual_history(ws)}), step, &s,
+                     &overtimed));
       iter = s.iter;
       tired = iter >= itmax;
-      // the host rotated the roles for every iteration it enqueued; the device ran s.iter of them
-      if (iter & 1) r.rotate();
+      r = replay(r, iter, 2, [](BiLanczosRoles &b) { b.rotate(); });   // r stayed where the loop began
       pol.fix_after_device_loop(s);
     }
     ws->v = r.v; ws->v_prev = r.v_prev; ws->u = r.u; ws->u_prev = r.u_prev;
@@ -390,10 +355,8 @@ struct BiLanczos {
 
   // the end of every solve that got past the checks
   void finish() {
-    ws->box.st.timer = now_s() - t0;
     ws->warm_start = false;
-    ws->box.st.allocation_timer += take_alloc_seconds();
-    ws->box.publish();
+    ws_finish(ws, t0);
   }
 };
 

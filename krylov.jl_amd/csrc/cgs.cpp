@@ -215,45 +215,14 @@ int cgs_device_loop(W *ws, const khip_csr *A, const double *c, const CgsDevState
   const int64_t n = ws->n;
   double *x = ws->x, *r = ws->r, *u = ws->u, *p = ws->p, *q = ws->q, *ts = ws->ts;
   auto step = [&](CgsDevState *dev, long long j) {
-    ctx->ctl = SeqCtl{&dev->stop_seq, 5 * j, EPI_CGS_A, dev};
-    int slot = take_slots(ctx, 1);
-    int rc = spmv_any(ctx, A, p, ts, slot, c, 0);                                        // :218-221  ts = A p ; c.ts -> α
-    if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-    if (rc != KHIP_OK) return rc;
-    ctx->ctl = SeqCtl{&dev->stop_seq, 5 * j + 1, EPI_NONE, nullptr};
-    rc = launch_p1(ctx, n, dev, ts, u, q, x, true);                                      // :222-226
-    if (rc != KHIP_OK) return rc;
-    ctx->ctl = SeqCtl{&dev->stop_seq, 5 * j + 2, EPI_NONE, nullptr};
-    rc = spmv_any(ctx, A, u, ts, -1);                                                    // :227      ts = A u
-    if (rc != KHIP_OK) return rc;
-    ctx->ctl = SeqCtl{&dev->stop_seq, 5 * j + 3, EPI_CGS_B, dev};
-    slot = take_slots(ctx, 2);
-    rc = launch_p2(ctx, n, dev, ts, c, r, slot);                                         // :229-230, :244 -> β, ρ, the tests
-    if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 2);
-    if (rc != KHIP_OK) return rc;
-    ctx->ctl = SeqCtl{&dev->stop_seq, 5 * j + 4, EPI_NONE, nullptr};
-    rc = launch_p3(ctx, n, dev, r, q, u, p);                                             // :232-235
-    ctx->ctl = SeqCtl{};
-    return rc;
+    const long long *stop = &dev->stop_seq;
+    KHIP_TRY(dev_stage(ctx, dev, 5 * j, EPI_CGS_A, 1, [&](int slot) { return spmv_any(ctx, A, p, ts, slot, c, 0); }));   // :218-221  ts = A p ; c.ts -> α
+    KHIP_TRY(dev_pass(ctx, stop, 5 * j + 1, EPI_NONE, nullptr, [&] { return launch_p1(ctx, n, dev, ts, u, q, x, true); }));   // :222-226
+    KHIP_TRY(dev_pass(ctx, stop, 5 * j + 2, EPI_NONE, nullptr, [&] { return spmv_any(ctx, A, u, ts, -1); }));   // :227      ts = A u
+    KHIP_TRY(dev_stage(ctx, dev, 5 * j + 3, EPI_CGS_B, 2, [&](int slot) { return launch_p2(ctx, n, dev, ts, c, r, slot); }));   // :229-230, :244 -> β, ρ, the tests
+    return dev_pass(ctx, stop, 5 * j + 4, EPI_NONE, nullptr, [&] { return launch_p3(ctx, n, dev, r, q, u, p); });   // :232-235
   };
   return ws->loop.run(ctx, h, a, step, out, overtimed);
-}
-
-// every return of khip_cgs_solve past the checks (:174-182, :186-194, :270-280)
-int cgs_end(W *ws, int64_t iter, int solved, const char *status, bool warm_start, double t0) {
-  khip_ctx *ctx = ws->ctx;
-  if (warm_start) K(khip_axpy(ctx, ws->n, 1.0, ws->dx, ws->x));
-  ws->warm_start = false;
-  K(khip_ctx_sync(ctx));
-  khip_stats *st = &ws->box.st;
-  st->niter = (int)iter;
-  st->solved = solved;
-  st->inconsistent = 0;
-  st->timer = now_s() - t0;
-  st->allocation_timer += take_alloc_seconds();
-  snprintf(st->status, sizeof(st->status), "%s", status);
-  ws->box.publish();
-  return KHIP_OK;
 }
 
 }  // namespace
@@ -312,16 +281,7 @@ int khip_cgs_solve(khip_cgs_workspace *ws, const khip_operator *A, const khip_op
   const bool history = o.history != 0;
   (void)take_alloc_seconds();
 
-  if (A->csr && !A->apply) {                                                                               // :132-134
-    int64_t am, an;
-    khip_csr_shape(A->csr, &am, &an, nullptr);
-    if (am != ws->m || (an != ws->n && !A->csr->dist)) {                   // a row-partitioned handle counts global columns
-      char msg[160];
-      snprintf(msg, sizeof(msg), "(workspace.m, workspace.n) = (%lld, %lld) is inconsistent with size(A) = (%lld, %lld)",
-               (long long)ws->m, (long long)ws->n, (long long)am, (long long)an);
-      return ws->box.fail(KHIP_ERR_INVALID, msg);
-    }
-  }
+  if (int rc = check_shape(ws, {A})) return rc;                                                            // :132-134
   if (ws->m != ws->n) return ws->box.fail(KHIP_ERR_INVALID, "System must be square");
   if (o.variant != 0) return ws->box.fail(KHIP_ERR_INVALID, "cgs: options.variant must be 0 (there is no other recurrence)");
   if (o.verbose > 0) klogf(o.log_fd, "CGS: system of size %lld\n", (long long)n);                         // :136
@@ -339,12 +299,7 @@ int khip_cgs_solve(khip_cgs_workspace *ws, const khip_operator *A, const khip_op
   double *r0 = MisI ? r : ts;
 
   // set-up, the same primitives on every path (:161-213)
-  if (warm_start) {
-    K(apply_op(ctx, A, ws->dx, r0));
-    K(khip_axpby(ctx, n, 1.0, b, -1.0, r0));
-  } else {
-    K(khip_copy(ctx, n, r0, b));
-  }
+  K(residual0(ws, A, 0.0, b, warm_start, r0));
   K(khip_fill(ctx, n, x, 0.0));
   if (!MisI) K(apply_op(ctx, M, r0, r));
   CgsDevState s;
@@ -352,9 +307,9 @@ int khip_cgs_solve(khip_cgs_workspace *ws, const khip_operator *A, const khip_op
   K(khip_nrm2(ctx, n, r, &s.rNorm));
   if (history) ws->box.push(s.rNorm);
   ws->box.path = o.fused ? 1 : 0;
-  if (s.rNorm == 0) return cgs_end(ws, 0, 1, "x is a zero-residual solution", warm_start, t0);
+  if (s.rNorm == 0) return ws_end(ws, {0, 1, 0, "x is a zero-residual solution", warm_start, t0, true});
   K(khip_dot(ctx, n, c, r, &s.rho));
-  if (s.rho == 0) return cgs_end(ws, 0, 0, "Breakdown b\xe1\xb4\xb4" "c = 0", warm_start, t0);
+  if (s.rho == 0) return ws_end(ws, {0, 0, 0, "Breakdown b\xe1\xb4\xb4" "c = 0", warm_start, t0, true});
 
   int64_t iter = 0;
   const int64_t itmax = o.itmax == 0 ? 2 * global_rows(ctx, A, n) : o.itmax;      // 2n of the GLOBAL system on every rank
@@ -373,12 +328,8 @@ int khip_cgs_solve(khip_cgs_workspace *ws, const khip_operator *A, const khip_op
   // the end of an iteration on the host-driven loops (:244-259)
   auto host_tail = [&](int64_t k) {
     if (history) ws->box.push(s.rNorm);
-    if (o.callback) {
-      ws->box.publish();                          // the callback reads stats.residuals
-      user_exit = o.callback(ws, o.callback_data) != 0;
-    }
     tired = k >= itmax;
-    overtimed = time_limit_reached(ctx, now_s() - t0, timemax);
+    host_exit(ws, o, t0, timemax, &user_exit, &overtimed);
     if (kdisplay(k, o.verbose)) verbose_row(o, k, s.rNorm, t0);
   };
 
@@ -455,10 +406,7 @@ int khip_cgs_solve(khip_cgs_workspace *ws, const khip_operator *A, const khip_op
     }
   } else {
     // -------------------------------------------------------------- device-resident loop ------------------------------
-    // a finite timemax: the first chunk is ONE iteration, so that a limit already used up stops after iteration 1 as the
-    // host-driven loop does
-    const DeviceLoopArgs loop_args{itmax, t0, timemax, history, {&ws->box.residuals, nullptr, nullptr}, timemax < 1e300 ? 1 : kDevChunk};
-    K(cgs_device_loop(ws, A->csr, c, s, loop_args, &s, &overtimed));
+    K(cgs_device_loop(ws, A->csr, c, s, device_loop_args(itmax, t0, timemax, history, {&ws->box.residuals}), &s, &overtimed));
     iter = s.iter;
     tired = iter >= itmax;
   }
@@ -470,7 +418,7 @@ int khip_cgs_solve(khip_cgs_workspace *ws, const khip_operator *A, const khip_op
   if (s.solved) status = "solution good enough given atol and rtol";
   if (user_exit) status = "user-requested exit";
   if (overtimed) status = "time limit exceeded";
-  return cgs_end(ws, iter, s.solved ? 1 : 0, status, warm_start, t0);                                   // :271-280
+  return ws_end(ws, {iter, s.solved ? 1 : 0, 0, status, warm_start, t0, true});                         // :271-280
 }
 
 }  // extern "C"

@@ -278,6 +278,18 @@ LzShiftArrays host_arrays(khip_cg_lanczos_shift_workspace *ws, const double *shi
                        ws->nhist.data()};
 }
 
+// the host copy of the fused loops' pointer table (x_i, p_i); false when one of the vectors is not 16-byte aligned
+bool fill_table(khip_cg_lanczos_shift_workspace *ws) {
+  bool aligned = true;
+  ws->tab_host.resize(2 * (size_t)ws->nshifts);
+  for (size_t i = 0; i < (size_t)ws->nshifts; ++i) {
+    ws->tab_host[2 * i] = ws->x[i];
+    ws->tab_host[2 * i + 1] = ws->p[i];
+    aligned = aligned && aligned16(ws->x[i]) && aligned16(ws->p[i]);
+  }
+  return aligned;
+}
+
 // act / coef of the host-driven loop's iteration (from pageable host memory: waited for)
 int upload_coefs(khip_cg_lanczos_shift_workspace *ws) {
   const int na = ws->act[0];
@@ -443,16 +455,7 @@ int khip_cg_lanczos_shift_solve(khip_cg_lanczos_shift_workspace *ws, const khip_
   const bool history = o.history != 0;
   (void)take_alloc_seconds();
 
-  if (A->csr && !A->apply) {                                                                              // :115-118
-    int64_t am, an;
-    khip_csr_shape(A->csr, &am, &an, nullptr);
-    if (am != ws->m || (an != ws->n && !A->csr->dist)) {             // a row-partitioned handle counts global columns
-      char msg[160];
-      snprintf(msg, sizeof(msg), "(workspace.m, workspace.n) = (%lld, %lld) is inconsistent with size(A) = (%lld, %lld)",
-               (long long)ws->m, (long long)ws->n, (long long)am, (long long)an);
-      return ws->box.fail(KHIP_ERR_INVALID, msg);
-    }
-  }
+  if (int rc = check_shape(ws, {A})) return rc;                                                           // :115-118
   if (ws->m != ws->n) return ws->box.fail(KHIP_ERR_INVALID, "System must be square");
   if (params->nshifts != p) {                                                                             // :121-122
     char msg[160];
@@ -471,23 +474,16 @@ int khip_cg_lanczos_shift_solve(khip_cg_lanczos_shift_workspace *ws, const khip_
   std::fill(ws->nhist.begin(), ws->nhist.end(), 0LL);
   double *Mv = ws->Mv, *Mv_prev = ws->Mv_prev, *Mv_next = ws->Mv_next;
   double *v = MisI ? Mv : ws->v;
-  auto finish = [&](void) {
-    st->timer = now_s() - t0;
+  auto finish = [&](void) {                                  // there is no Δx here: the stats of the moment, no ws_end
     int any = 0;
     for (int i = 0; i < p; ++i) any |= ws->indefinite[(size_t)i];
     st->indefinite = any;
-    st->allocation_timer += take_alloc_seconds();
-    ws->box.publish();
+    ws_finish(ws, t0);
   };
   // the device pointer table of the fused loops: the vectors may have been re-adopted since the last solve
   bool tab_aligned = true;
   if (o.fused) {
-    ws->tab_host.resize(2 * (size_t)p);
-    for (int i = 0; i < p; ++i) {
-      ws->tab_host[2 * (size_t)i] = ws->x[(size_t)i];
-      ws->tab_host[2 * (size_t)i + 1] = ws->p[(size_t)i];
-      tab_aligned = tab_aligned && aligned16(ws->x[(size_t)i]) && aligned16(ws->p[(size_t)i]);
-    }
+    tab_aligned = fill_table(ws);
     if (!ws->tab) K(khip_malloc(ctx, sizeof(double *) * 2 * (size_t)p, reinterpret_cast<void **>(&ws->tab)));
     KHIP_CHECK_HIP(hipMemcpyAsync(ws->tab, ws->tab_host.data(), sizeof(double *) * 2 * (size_t)p, hipMemcpyHostToDevice, ctx->stream));
     KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
@@ -584,11 +580,10 @@ int khip_cg_lanczos_shift_solve(khip_cg_lanczos_shift_workspace *ws, const khip_
       if (kdisplay(iter, verbose)) verbose_row(o, iter, ws->rNorms, t0);
       if (o.callback) {
         KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        finish();
-        user_exit = o.callback(ws, o.callback_data) != 0;
+        finish();                                 // the callback sees the timers and the indefinite flag of the moment
       }
       tired = iter >= itmax;
-      overtimed = time_limit_reached(ctx, now_s() - t0, timemax);
+      host_exit(ws, o, t0, timemax, &user_exit, &overtimed);
     }
   } else if (ws->box.path == 1) {
     // ---------------------------------------------------------------- host-driven loop on the fused kernels ----------
@@ -638,11 +633,10 @@ int khip_cg_lanczos_shift_solve(khip_cg_lanczos_shift_workspace *ws, const khip_
       if (kdisplay(iter, verbose)) verbose_row(o, iter, ws->rNorms, t0);
       if (o.callback) {
         KHIP_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        finish();
-        user_exit = o.callback(ws, o.callback_data) != 0;
+        finish();                                 // the callback sees the timers and the indefinite flag of the moment
       }
       tired = iter >= itmax;
-      overtimed = time_limit_reached(ctx, now_s() - t0, timemax);
+      host_exit(ws, o, t0, timemax, &user_exit, &overtimed);
     }
     ws->Mv = cur; ws->Mv_prev = prev; ws->Mv_next = nxt;
   } else if (!(solved || tired)) {
@@ -654,30 +648,24 @@ int khip_cg_lanczos_shift_solve(khip_cg_lanczos_shift_workspace *ws, const khip_
       s.converged[i] = ws->converged[(size_t)i]; s.not_cv[i] = ws->not_cv[(size_t)i]; s.indefinite[i] = 0;
     }
     K(khip_div(ctx, n, v, beta));                                                                         // v₁ = Mv₁ / β₁
-    double *cur = Mv, *prev = Mv_prev, *nxt = Mv_next;
+    struct Roles {                                            // Mv_prev <- Mv ; Mv <- Mv_next as a rotation of the roles
+      double *cur, *prev, *nxt;
+      void rotate() { double *old_prev = prev; prev = cur; cur = nxt; nxt = old_prev; }
+    };
+    const Roles first{Mv, Mv_prev, Mv_next};
+    Roles B = first;
     auto step = [&](LanczosShiftDevState *dev, long long j) {
       const int64_t k = j + 1;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j + 1, EPI_LZSHIFT_A, dev};
-      int slot = take_slots(ctx, 1);
-      int rc = spmv_any(ctx, A->csr, cur, nxt, slot);                                    // P0: y = A v ; v.y -> δ
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-      if (rc != KHIP_OK) return rc;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j + 2, EPI_LZSHIFT_B, dev};
-      slot = take_slots(ctx, 1);
-      rc = launch_p1(ctx, n, dev, prev, cur, nxt, k >= 2, true, slot);                  // P1: w ; w.w -> β, the shifts' step
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-      if (rc != KHIP_OK) return rc;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j + 3, EPI_NONE, dev};
-      rc = launch_p2(ctx, n, &dev->inv_beta, dev->act, dev->coef, ws->tab, tab_aligned, nxt, true);   // P2: v ; x_i, p_i
-      ctx->ctl = SeqCtl{};
-      if (rc != KHIP_OK) return rc;
-      double *old_prev = prev;
-      prev = cur; cur = nxt; nxt = old_prev;
-      return KHIP_OK;
+      KHIP_TRY(dev_stage(ctx, dev, 3 * j + 1, EPI_LZSHIFT_A, 1, [&](int slot) {
+        return spmv_any(ctx, A->csr, B.cur, B.nxt, slot); }));                           // P0: y = A v ; v.y -> δ
+      KHIP_TRY(dev_stage(ctx, dev, 3 * j + 2, EPI_LZSHIFT_B, 1, [&](int slot) {
+        return launch_p1(ctx, n, dev, B.prev, B.cur, B.nxt, k >= 2, true, slot); }));   // P1: w ; w.w -> β, the shifts' step
+      KHIP_TRY(dev_pass(ctx, &dev->stop_seq, 3 * j + 3, EPI_NONE, dev, [&] {
+        return launch_p2(ctx, n, &dev->inv_beta, dev->act, dev->coef, ws->tab, tab_aligned, B.nxt, true); }));   // P2: v ; x_i, p_i
+      B.rotate();
+      return (int)KHIP_OK;
     };
-    // a finite timemax: the first chunk is ONE iteration, so that a limit already used up stops after iteration 1 as the
-    // host-driven loop does
-    DeviceLoopArgs loop_args{itmax, t0, timemax, history, {nullptr, nullptr, nullptr}, timemax < 1e300 ? 1 : kDevChunk};
+    DeviceLoopArgs loop_args = device_loop_args(itmax, t0, timemax, history, {});
     loop_args.width = p;
     loop_args.columns = ws->hist.data();
     K(ws->loop.run(ctx, s, loop_args, step, &s, &overtimed));
@@ -690,10 +678,8 @@ int khip_cg_lanczos_shift_solve(khip_cg_lanczos_shift_workspace *ws, const khip_
       ws->converged[(size_t)i] = s.converged[i]; ws->not_cv[(size_t)i] = s.not_cv[i]; ws->indefinite[(size_t)i] = s.indefinite[i];
       ws->nhist[(size_t)i] = s.nhist[i];
     }
-    // the host rotated the roles for every iteration it enqueued; the device ran s.iter of them
-    cur = Mv; prev = Mv_prev; nxt = Mv_next;
-    for (int64_t j = 0; j < iter % 3; ++j) { double *old_prev = prev; prev = cur; cur = nxt; nxt = old_prev; }
-    ws->Mv = cur; ws->Mv_prev = prev; ws->Mv_next = nxt;
+    B = replay(first, iter, 3, [](Roles &r) { r.rotate(); });
+    ws->Mv = B.cur; ws->Mv_prev = B.prev; ws->Mv_next = B.nxt;
   }
   if (verbose > 0) klogf(o.log_fd, "\n");
   const char *status = "unknown";                                                                         // :269-273

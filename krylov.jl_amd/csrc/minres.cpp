@@ -321,7 +321,6 @@ int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const k
   const double t0 = now_s();
   const double timemax = timemax_of(o);
   const int64_t n = ws->n;
-  khip_stats *st = &ws->box.st;
   const double atol = tol_or_default(o.atol), rtol = tol_or_default(o.rtol), etol = tol_or_default(prm.etol);
   const double conlim = std::isnan(prm.conlim) ? 1.0 / std::sqrt(kEps) : prm.conlim;
   const double lambda = prm.lambda;
@@ -346,35 +345,19 @@ int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const k
   Bufs B{ws->x, ws->r1, ws->r2, ws->y, MisI ? ws->r2 : ws->v, ws->w1, ws->w2};
   const double ctol = conlim > 0 ? 1.0 / conlim : 0.0;
   const bool history = o.history != 0;
-  auto finish_early = [&](void) {
-    st->timer = now_s() - t0;
-    ws->warm_start = false;
-    st->allocation_timer += take_alloc_seconds();
-    ws->box.publish();
-  };
 
   // set-up, the same primitives on every path (:208-231)
   K(khip_fill(ctx, n, B.x, 0.0));
-  if (warm_start) {
-    K(apply_op(ctx, A, ws->dx, B.r1));
-    if (lambda != 0) K(khip_axpy(ctx, n, lambda, ws->dx, B.r1));
-    K(khip_axpby(ctx, n, 1.0, b, -1.0, B.r1));
-  } else {
-    K(khip_copy(ctx, n, B.r1, b));
-  }
+  K(residual0(ws, A, lambda, b, warm_start, B.r1));
   K(khip_copy(ctx, n, B.r2, B.r1));
   if (!MisI) K(apply_op(ctx, M, B.r1, B.v));
   double beta1;
   K(khip_dot(ctx, n, B.r1, B.v, &beta1));
   if (beta1 < 0) return ws->box.fail(KHIP_ERR_NUMERIC, "Preconditioner is not positive definite");
   if (beta1 == 0) {                                                                                       // :233-244
-    st->niter = 1; st->solved = 1; st->inconsistent = 0;
-    snprintf(st->status, sizeof(st->status), "x is a zero-residual solution");
     if (history) { ws->box.residuals.push_back(beta1); ws->aresiduals.push_back(0.0); ws->aconds.push_back(0.0); }
-    if (warm_start) K(khip_axpy(ctx, n, 1.0, ws->dx, B.x));
     ws->box.path = o.fused ? 1 : 0;
-    finish_early();
-    return KHIP_OK;
+    return ws_end(ws, {1, 1, 0, "x is a zero-residual solution", warm_start, t0, false});   // niter = 1, as the least-squares exit
   }
   beta1 = std::sqrt(beta1);
   MinresDevState s;
@@ -450,11 +433,7 @@ int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const k
       if (kdisplay(k, verbose)) verbose_row(o, k, s, t0, false);
       if (s.lsq_exit) break;
       tired = k >= itmax;
-      if (o.callback) {
-        ws->box.publish();                          // the callback reads stats.residuals (as cg! / gmres! / bicgstab! publish them)
-        user_exit = o.callback(ws, o.callback_data) != 0;
-      }
-      overtimed = time_limit_reached(ctx, now_s() - t0, timemax);
+      host_exit(ws, o, t0, timemax, &user_exit, &overtimed);
       stop = stop || user_exit || overtimed;
     }
   } else if (ws->box.path == 1) {
@@ -496,11 +475,7 @@ int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const k
       if (kdisplay(k, verbose)) verbose_row(o, k, s, t0, false);
       if (s.lsq_exit) break;
       tired = k >= itmax;
-      if (o.callback) {
-        ws->box.publish();                          // the callback reads stats.residuals (as cg! / gmres! / bicgstab! publish them)
-        user_exit = o.callback(ws, o.callback_data) != 0;
-      }
-      overtimed = time_limit_reached(ctx, now_s() - t0, timemax);
+      host_exit(ws, o, t0, timemax, &user_exit, &overtimed);
       stop = stop || user_exit || overtimed;
     }
   } else if (!stop) {
@@ -508,45 +483,26 @@ int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const k
     for (int i = 0; i < ws->window; ++i) s.err_vec[i] = 0.0;
     auto step = [&](MinresDevState *dev, long long j) {
       const int64_t k = j + 1;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 1, EPI_MINRES_A, dev};
-      int slot = take_slots(ctx, 1);
-      int rc = lanczos_product(ctx, A, fuse, n, dev, B.v, B.r1, B.y, k >= 2, slot);          // y = A v + P1 ; v.y -> alpha, delta
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-      if (rc != KHIP_OK) return rc;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 2, EPI_MINRES_B, dev};
-      slot = take_slots(ctx, 1);
-      rc = launch_p2(ctx, n, dev, B.r2, B.v, B.y, B.w1, B.w2, (int)std::min<int64_t>(k, 3), true, slot);   // P2 ; y.y -> rotation
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-      if (rc != KHIP_OK) return rc;
+      KHIP_TRY(dev_stage(ctx, dev, 4 * j + 1, EPI_MINRES_A, 1, [&](int slot) {
+        return lanczos_product(ctx, A, fuse, n, dev, B.v, B.r1, B.y, k >= 2, slot); }));   // y = A v + P1 ; v.y -> alpha, delta
+      KHIP_TRY(dev_stage(ctx, dev, 4 * j + 2, EPI_MINRES_B, 1, [&](int slot) {
+        return launch_p2(ctx, n, dev, B.r2, B.v, B.y, B.w1, B.w2, (int)std::min<int64_t>(k, 3), true, slot); }));   // P2 ; y.y -> rotation
       double *w = k == 1 ? B.w2 : B.w1;
       double *old_r1 = B.r1;
       B.r1 = B.r2; B.r2 = B.y; B.y = old_r1; B.v = B.r2;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 4 * j + 3, EPI_MINRES_C, dev};
-      slot = take_slots(ctx, 1);
-      rc = launch_p3(ctx, n, dev, w, B.x, slot);                                         // P3 ; x.x -> tests
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-      ctx->ctl = SeqCtl{};
-      if (rc != KHIP_OK) return rc;
+      KHIP_TRY(dev_stage(ctx, dev, 4 * j + 3, EPI_MINRES_C, 1, [&](int slot) {
+        return launch_p3(ctx, n, dev, w, B.x, slot); }));                                // P3 ; x.x -> tests
       if (k >= 2) std::swap(B.w1, B.w2);
-      return KHIP_OK;
+      return (int)KHIP_OK;
     };
-    // a finite timemax: the first chunk is ONE iteration, so that a limit already used up stops after iteration 1 as the
-    // host-driven loop does
-    const DeviceLoopArgs loop_args{itmax, t0, timemax, history, {&ws->box.residuals, &ws->aresiduals, &ws->aconds},
-                                   timemax < 1e300 ? 1 : kDevChunk};
-    K(ws->loop.run(ctx, s, loop_args, step, &s, &overtimed));
+    K(ws->loop.run(ctx, s, device_loop_args(itmax, t0, timemax, history, {&ws->box.residuals, &ws->aresiduals, &ws->aconds}), step,
+                   &s, &overtimed));
     iter = s.iter;
     tired = iter >= itmax;
   }
   if (verbose > 0) klogf(o.log_fd, "\n");
-  if (warm_start) K(khip_axpy(ctx, n, 1.0, ws->dx, B.x));
-  st->niter = (int)iter;
-  if (s.lsq_exit) {                                                                                       // :410-419
-    st->niter = 1; st->solved = 1; st->inconsistent = 1;
-    snprintf(st->status, sizeof(st->status), "x is a minimum least-squares solution");
-    finish_early();
-    return KHIP_OK;
-  }
+  if (s.lsq_exit)                                                                                         // :410-419
+    return ws_end(ws, {1, 1, 1, "x is a minimum least-squares solution", warm_start, t0, false});
   const char *status = "unknown";
   if (tired) status = "maximum number of iterations exceeded";
   if (s.ill_cond_mach) status = "condition number seems too large for this machine";
@@ -556,11 +512,7 @@ int khip_minres_solve(khip_minres_workspace *ws, const khip_operator *A, const k
   if (s.fwd_err) status = "truncated forward error small enough";
   if (user_exit) status = "user-requested exit";
   if (overtimed) status = "time limit exceeded";
-  snprintf(st->status, sizeof(st->status), "%s", status);
-  st->solved = s.solved;
-  st->inconsistent = !s.zero_resid;
-  finish_early();
-  return KHIP_OK;
+  return ws_end(ws, {iter, s.solved, !s.zero_resid, status, warm_start, t0, false});
 }
 
 }  // extern "C"

@@ -358,22 +358,12 @@ int khip_minres_qlp_solve(khip_minres_qlp_workspace *ws, const khip_operator *A,
   const double t0 = now_s();
   const double timemax = timemax_of(o);
   const int64_t n = ws->n;
-  khip_stats *st = &ws->box.st;
   const double atol = tol_or_default(o.atol), rtol = tol_or_default(o.rtol), Artol = tol_or_default(prm.Artol);
   const double lambda = prm.lambda;
   const bool history = o.history != 0;
   (void)take_alloc_seconds();
 
-  if (A->csr && !A->apply) {                                                                               // :137-138
-    int64_t am, an;
-    khip_csr_shape(A->csr, &am, &an, nullptr);
-    if (am != ws->m || (an != ws->n && !A->csr->dist)) {                   // a row-partitioned handle counts global columns
-      char msg[160];
-      snprintf(msg, sizeof(msg), "(workspace.m, workspace.n) = (%lld, %lld) is inconsistent with size(A) = (%lld, %lld)",
-               (long long)ws->m, (long long)ws->n, (long long)am, (long long)an);
-      return ws->box.fail(KHIP_ERR_INVALID, msg);
-    }
-  }
+  if (int rc = check_shape(ws, {A})) return rc;                                                            // :137-138
   if (ws->m != ws->n) return ws->box.fail(KHIP_ERR_INVALID, "System must be square");                     // :139
   if (o.variant != 0) return ws->box.fail(KHIP_ERR_INVALID, "minres_qlp: options.variant must be 0 (there is no other recurrence)");
   if (o.verbose > 0) klogf(o.log_fd, "MINRES-QLP: system of size %lld\n", (long long)n);                  // :141
@@ -390,30 +380,9 @@ int khip_minres_qlp_solve(khip_minres_qlp_workspace *ws, const khip_operator *A,
   double *vM = ws->vk;                                                    // vₖ with M (:162); with M = I it is M⁻¹vₖ
   ws->box.path = o.fused ? 1 : 0;
 
-  // every return past the checks (:193-201, :509-536)
-  auto finish = [&](int64_t iter, int solved, int inconsistent, const char *status) -> int {
-    if (warm_start) K(khip_axpy(ctx, n, 1.0, ws->dx, x));
-    ws->warm_start = false;
-    K(khip_ctx_sync(ctx));
-    st->niter = (int)iter;
-    st->solved = solved;
-    st->inconsistent = inconsistent;
-    st->timer = now_s() - t0;
-    st->allocation_timer += take_alloc_seconds();
-    snprintf(st->status, sizeof(st->status), "%s", status);
-    ws->box.publish();
-    return KHIP_OK;
-  };
-
   // set-up, the same primitives on every path (:166-236)
   K(khip_fill(ctx, n, x, 0.0));
-  if (warm_start) {
-    K(apply_op(ctx, A, ws->dx, B.Mvk));
-    if (lambda != 0) K(khip_axpy(ctx, n, lambda, ws->dx, B.Mvk));
-    K(khip_axpby(ctx, n, 1.0, b, -1.0, B.Mvk));
-  } else {
-    K(khip_copy(ctx, n, B.Mvk, b));
-  }
+  K(residual0(ws, A, lambda, b, warm_start, B.Mvk));
   double *v = MisI ? B.Mvk : vM;
   if (!MisI) K(apply_op(ctx, M, B.Mvk, v));                                                                // :177
   double beta1;
@@ -434,7 +403,7 @@ int khip_minres_qlp_solve(khip_minres_qlp_workspace *ws, const khip_operator *A,
   s.beta = beta1; s.rNorm = beta1;                                                                         // :185-192
   s.atol = atol; s.Artol = Artol; s.MisI = MisI ? 1 : 0;
   if (history) { ws->box.push(s.rNorm); ws->aconds.push_back(0.0); }
-  if (s.rNorm == 0) return finish(0, 1, 0, "x is a zero-residual solution");                              // :193-201
+  if (s.rNorm == 0) return ws_end(ws, {0, 1, 0, "x is a zero-residual solution", warm_start, t0, true});   // :193-201
 
   int64_t iter = 0;
   const int64_t itmax = o.itmax == 0 ? 2 * global_rows(ctx, A, n) : o.itmax;      // 2n of the GLOBAL system on every rank (:204)
@@ -466,13 +435,9 @@ int khip_minres_qlp_solve(khip_minres_qlp_workspace *ws, const khip_operator *A,
     return true;
   };
   // :484-490, :505 (after the vectors of the iteration are in place)
-  auto host_exit = [&](int64_t k) {
-    if (o.callback) {
-      ws->Mvkm1 = B.Mvkm1; ws->Mvk = B.Mvk; ws->p = B.p; ws->wkm1 = B.wkm1; ws->wk = B.wk;   // the names follow the roles
-      ws->box.publish();                          // the callback reads stats.residuals
-      user_exit = o.callback(ws, o.callback_data) != 0;
-    }
-    overtimed = time_limit_reached(ctx, now_s() - t0, timemax);
+  auto iteration_end = [&](int64_t k) {
+    if (o.callback) { ws->Mvkm1 = B.Mvkm1; ws->Mvk = B.Mvk; ws->p = B.p; ws->wkm1 = B.wkm1; ws->wk = B.wk; }   // the names follow the roles
+    host_exit(ws, o, t0, timemax, &user_exit, &overtimed);
     if (kdisplay(k, o.verbose)) verbose_row(o, k, s, t0, false);
   };
   const char *not_pd_msg = "Preconditioner is not positive definite";
@@ -525,7 +490,7 @@ int khip_minres_qlp_solve(khip_minres_qlp_workspace *ws, const khip_operator *A,
       K(khip_copy(ctx, n, B.Mvk, B.p));
       K(khip_nrm2(ctx, n, x, &xNorm));                                                                    // :468
       if (!host_tail(k, beta2, xNorm)) return ws->box.fail(KHIP_ERR_NUMERIC, not_pd_msg);
-      host_exit(k);
+      iteration_end(k);
     }
   } else if (ws->box.path == 1) {
     // -------------------------------------------------------------- host-driven loop on the fused kernels ---------------
@@ -573,7 +538,7 @@ int khip_minres_qlp_solve(khip_minres_qlp_workspace *ws, const khip_operator *A,
         K(khip_copy(ctx, n, B.Mvkm1, B.Mvk));
         K(khip_copy(ctx, n, B.Mvk, B.p));
       }
-      host_exit(k);
+      iteration_end(k);
     }
     if (carry && iter > 0 && s.beta > s.btol) K(khip_scal(ctx, n, 1.0 / s.beta, B.Mvk));                  // :265 of the last iteration
   } else {
@@ -581,39 +546,23 @@ int khip_minres_qlp_solve(khip_minres_qlp_workspace *ws, const khip_operator *A,
     const Roles first = B;
     auto step = [&](MinresQlpDevState *dev, long long j) {
       const int64_t k = j + 1;
-      int rc = KHIP_OK, slot;
-      if (k >= 2) {
-        ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j, k >= 3 ? EPI_MINRES_QLP_X : EPI_NONE, k >= 3 ? dev : nullptr};
-        slot = take_slots(ctx, 1);
-        rc = launch_p1(ctx, n, dev, B.Mvk, x, B.wkm1, true, k >= 3, slot);                                // :427-430, :468 ; x.x -> xNorm
-        if (rc == KHIP_OK && k >= 3 && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-        if (rc != KHIP_OK) return rc;
-      }
-      ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j + 1, EPI_MINRES_QLP_A, dev};
-      slot = take_slots(ctx, 1);
-      rc = lanczos_product(ctx, A, fuse, n, dev, B.Mvk, B.Mvkm1, B.p, k >= 2, slot);                      // :246-255  v.p -> αₖ
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-      if (rc != KHIP_OK) return rc;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j + 2, EPI_MINRES_QLP_B, dev};
-      slot = take_slots(ctx, 1);
-      rc = launch_p2(ctx, n, dev, B.Mvk, B.Mvk, B.p, B.wk, B.wkm1, k, true, slot);                        // :257-261  p.p -> βₖ₊₁, the tests
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-      ctx->ctl = SeqCtl{};
-      if (rc != KHIP_OK) return rc;
+      // P1 (:427-430, :468 and :265 of k - 1): from iteration 3 on it updates x and x.x -> xNorm; at k = 2 it only scales vₖ
+      auto p1 = [&](int slot) { return launch_p1(ctx, n, dev, B.Mvk, x, B.wkm1, true, k >= 3, slot); };
+      if (k >= 3) KHIP_TRY(dev_stage(ctx, dev, 3 * j, EPI_MINRES_QLP_X, 1, p1));
+      else if (k == 2) KHIP_TRY(dev_pass(ctx, &dev->stop_seq, 3 * j, EPI_NONE, nullptr, [&] { return p1(take_slots(ctx, 1)); }));
+      KHIP_TRY(dev_stage(ctx, dev, 3 * j + 1, EPI_MINRES_QLP_A, 1, [&](int slot) {
+        return lanczos_product(ctx, A, fuse, n, dev, B.Mvk, B.Mvkm1, B.p, k >= 2, slot); }));             // :246-255  v.p -> αₖ
+      KHIP_TRY(dev_stage(ctx, dev, 3 * j + 2, EPI_MINRES_QLP_B, 1, [&](int slot) {
+        return launch_p2(ctx, n, dev, B.Mvk, B.Mvk, B.p, B.wk, B.wkm1, k, true, slot); }));               // :257-261  p.p -> βₖ₊₁, the tests
       if (k >= 2) B.swap_w();
       B.rotate();
       return (int)KHIP_OK;
     };
-    // a finite timemax: the first chunk is ONE iteration, so that a limit already used up stops after iteration 1 as the
-    // host-driven loop does
-    const DeviceLoopArgs loop_args{itmax, t0, timemax, history, {&ws->box.residuals, &ws->aresiduals, &ws->aconds},
-                                   timemax < 1e300 ? 1 : kDevChunk};
-    K(ws->loop.run(ctx, s, loop_args, step, &s, &overtimed));
+    K(ws->loop.run(ctx, s, device_loop_args(itmax, t0, timemax, history, {&ws->box.residuals, &ws->aresiduals, &ws->aconds}), step,
+                   &s, &overtimed));
     iter = s.iter;
     tired = iter >= itmax;
-    // the host rotated the roles for every iteration it enqueued; the device ran s.iter of them
-    B = first;
-    for (int64_t j = 0; j < iter % 3; ++j) B.rotate();
+    B = replay(first, iter, 3, [](Roles &r) { r.rotate(); });
     if (iter >= 2 && (iter - 1) % 2) B.swap_w();
     if (iter > 0 && s.beta > s.btol) K(khip_scal(ctx, n, 1.0 / s.beta, B.Mvk));                           // :265 of the last iteration
   }
@@ -631,7 +580,7 @@ int khip_minres_qlp_solve(khip_minres_qlp_workspace *ws, const khip_operator *A,
   if (s.solved) status = "solution good enough given atol and rtol";
   if (user_exit) status = "user-requested exit";
   if (overtimed) status = "time limit exceeded";
-  return finish(iter, s.solved ? 1 : 0, s.inconsistent ? 1 : 0, status);                                 // :527-536
+  return ws_end(ws, {iter, s.solved ? 1 : 0, s.inconsistent ? 1 : 0, status, warm_start, t0, true});     // :527-536
 }
 
 }  // extern "C"

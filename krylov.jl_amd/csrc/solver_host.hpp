@@ -383,3 +383,5 @@ struct DeviceLoop {
 
 }  // namespace
 }  // namespace khip
+
+#include "solve_frame.hpp"   // the frame around a solver's iterations, on top of the pieces above

@@ -70,16 +70,11 @@ int cg_device_loop(khip_cg_workspace *ws, const khip_csr *A, double gamma, doubl
   double *p2 = ctx->tune.cg_defer_x ? ws->p2 : nullptr;
   auto step = [&](CgDevState *dev, long long j) {
     const bool heavy = p2 && (j & 1);
-    ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j, EPI_CG_STEP1, dev};
-    const int s1 = take_slots(ctx, 1);
-    int rc = spmv_any(ctx, A, heavy ? p2 : ws->p, ws->Ap, s1);                        // :196-197, epilogue :198-213
-    if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, s1, 1);
-    if (rc != KHIP_OK) return rc;
-    ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j + 1, EPI_CG_STEP2, dev};
-    const int s2 = take_slots(ctx, 1);
-    rc = launch_axpy_dev_dot(ctx, n, &dev->alpha, ws->Ap, ws->r, ws->r, s2);          // :240, :242, epilogue :243-262
-    if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, s2, 1);
-    ctx->ctl = SeqCtl{};
+    KHIP_TRY(dev_stage(ctx, dev, 3 * j, EPI_CG_STEP1, 1, [&](int slot) {
+      return spmv_any(ctx, A, heavy ? p2 : ws->p, ws->Ap, slot); }));                  // :196-197, epilogue :198-213
+    const int rc = dev_stage(ctx, dev, 3 * j + 1, EPI_CG_STEP2, 1, [&](int slot) {
+      return launch_axpy_dev_dot(ctx, n, &dev->alpha, ws->Ap, ws->r, ws->r, slot); });   // :240, :242, epilogue :243-262
+    ctx->ctl = SeqCtl{};                       // the update carries its own sequence number
     if (rc != KHIP_OK) return rc;
     if (!p2) return launch_cg_update_dev(ctx, n, dev, 3 * j + 2, ws->r, ws->p, ws->x);   // :239 and :259
     return launch_cg_defer(ctx, n, heavy ? CGD_HEAVY : CGD_LIGHT, dev, 3 * j + 2, 0, ws->r, ws->p, p2, ws->x);
@@ -112,11 +107,8 @@ int cg_single_reduction_loop(khip_cg_workspace *ws, const khip_csr *A, double ga
   auto step = [&](CgcgDevState *dev, long long j) {
     int rc = launch_cgcg_update(ctx, n, dev, 2 * j, w, r, p, s, x);
     if (rc != KHIP_OK) return rc;
-    ctx->ctl = SeqCtl{&dev->stop_seq, 2 * j + 1, EPI_CGCG, dev};
-    const int slot = take_slots(ctx, 2);
-    rc = spmv_any(ctx, A, r, w, slot, nullptr, 2);                                    // w = A r ; (r.w, r.r)
-    if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 2);
-    ctx->ctl = SeqCtl{};
+    rc = dev_stage(ctx, dev, 2 * j + 1, EPI_CGCG, 2, [&](int slot) { return spmv_any(ctx, A, r, w, slot, nullptr, 2); });   // w = A r ; (r.w, r.r)
+    ctx->ctl = SeqCtl{};                       // the next update carries its own sequence number
     return rc;
   };
   return ws->cgcg_loop.run(ctx, cgcg_start(gamma0, delta0, eps_tol), a, step, out, overtimed);
@@ -564,8 +556,7 @@ int khip_cg_solve(khip_cg_workspace *ws, const khip_operator *A, const khip_oper
 
     iter = iter + 1;
     tired = iter >= itmax;
-    if (o.callback) { ws->box.publish(); user_requested_exit = o.callback(ws, o.callback_data) != 0; }    // :264
-    overtimed = time_limit_reached(ctx, now_s() - t0, timemax);
+    host_exit(ws, o, t0, timemax, &user_requested_exit, &overtimed);                                      // :264
     if (kdisplay(iter, verbose)) klogf(o.log_fd, "%5lld  %7.1e", (long long)iter, rNorm);                                 // :267
   }
   if (verbose > 0) { klogf(o.log_fd, "\n\n"); klog_flush(o.log_fd); }                                                         // :269
@@ -578,18 +569,7 @@ int khip_cg_solve(khip_cg_workspace *ws, const khip_operator *A, const khip_oper
   if (user_requested_exit) status = "user-requested exit";
   if (overtimed) status = "time limit exceeded";
 
-  if (warm_start) K(khip_axpy(ctx, n, 1.0, dx, x));
-  ws->warm_start = false;
-  K(khip_ctx_sync(ctx));
-
-  st->niter = (int)iter;
-  st->solved = solved;
-  st->inconsistent = inconsistent;
-  st->timer = now_s() - t0;
-  st->allocation_timer += take_alloc_seconds();                 // lazy allocations of this solve (allocate_if)
-  snprintf(st->status, sizeof(st->status), "%s", status);
-  ws->box.publish();
-  return KHIP_OK;
+  return ws_end(ws, {iter, solved, inconsistent, status, warm_start, t0, true});
 }
 
 }  // extern "C"
@@ -1287,23 +1267,15 @@ int bicgstab_device_loop(khip_bicgstab_workspace *ws, const khip_csr *A, const d
   h.rho = rho0; h.alpha = 1.0; h.omega = 1.0; h.rNorm = rNorm0; h.eps_tol = eps_tol;
   double *x = ws->x, *r = ws->r, *p = ws->p, *v = ws->v, *s = ws->s, *t = ws->qd;
   auto step = [&](BicgDevState *dev, long long j) {
-    ctx->ctl = SeqCtl{&dev->stop_seq, 5 * j, EPI_BICG_A, dev};
-    int slot = take_slots(ctx, 1);
-    int rc = spmv_any(ctx, A, p, v, slot, c, 0);                               // :221-223  v = A p ; c.v -> alpha
-    if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-    ctx->ctl = SeqCtl{};
+    int rc = dev_stage(ctx, dev, 5 * j, EPI_BICG_A, 1, [&](int slot) { return spmv_any(ctx, A, p, v, slot, c, 0); });   // :221-223  v = A p ; c.v -> alpha
+    ctx->ctl = SeqCtl{};                       // the passes between the reductions carry their own sequence numbers
     if (rc != KHIP_OK) return rc;
     rc = launch_bicg_sx(ctx, n, 0.0, r, v, p, s, x, dev, 5 * j + 1);               // :224-226
     if (rc != KHIP_OK) return rc;
-    ctx->ctl = SeqCtl{&dev->stop_seq, 5 * j + 2, EPI_BICG_B, dev};
-    slot = take_slots(ctx, 2);
-    rc = spmv_any(ctx, A, s, t, slot, nullptr, 1);                             // :228-230  t = A s ; t.s, t.t -> omega
-    if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 2);
-    if (rc != KHIP_OK) return rc;
-    ctx->ctl = SeqCtl{&dev->stop_seq, 5 * j + 3, EPI_BICG_C, dev};
-    slot = take_slots(ctx, 2);
-    rc = launch_bicg_xr(ctx, n, 0.0, s, t, s, c, x, r, slot, dev);                // :231-234, :240 -> beta, tests
-    if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 2);
+    KHIP_TRY(dev_stage(ctx, dev, 5 * j + 2, EPI_BICG_B, 2, [&](int slot) {
+      return spmv_any(ctx, A, s, t, slot, nullptr, 1); }));                        // :228-230  t = A s ; t.s, t.t -> omega
+    rc = dev_stage(ctx, dev, 5 * j + 3, EPI_BICG_C, 2, [&](int slot) {
+      return launch_bicg_xr(ctx, n, 0.0, s, t, s, c, x, r, slot, dev); });         // :231-234, :240 -> beta, tests
     ctx->ctl = SeqCtl{};
     if (rc != KHIP_OK) return rc;
     return launch_bicg_p(ctx, n, 0.0, 0.0, v, r, p, dev, 5 * j + 4);              // :236-237
@@ -1503,12 +1475,10 @@ int khip_bicgstab_solve(khip_bicgstab_workspace *ws, const khip_operator *A, con
       K(launch_bicg_p(ctx, n, omega, beta, v, r, p));                              // :236-237
       rNorm = std::sqrt(two[1]);                                                   // :240
       if (o.history) ws->box.push(rNorm);
-      const bool rdm = (rNorm + 1.0 <= 1.0);
-      if (o.callback) { ws->box.publish(); user_requested_exit = o.callback(ws, o.callback_data) != 0; }
-      solved = (rNorm <= eps_tol) || rdm;
+      solved = (rNorm <= eps_tol) || (rNorm + 1.0 <= 1.0);
       tired = iter >= itmax;
       breakdown = (alpha == 0 || std::isnan(alpha));
-      overtimed = time_limit_reached(ctx, now_s() - t0, timemax);
+      host_exit(ws, o, t0, timemax, &user_requested_exit, &overtimed);
       continue;
     }
 
@@ -1554,12 +1524,11 @@ int khip_bicgstab_solve(khip_bicgstab_workspace *ws, const khip_operator *A, con
     if (o.history) ws->box.push(rNorm);
 
     const bool resid_decrease_mach = (rNorm + 1.0 <= 1.0);
-    if (o.callback) { ws->box.publish(); user_requested_exit = o.callback(ws, o.callback_data) != 0; }
     const bool resid_decrease_lim = rNorm <= eps_tol;
     solved = resid_decrease_lim || resid_decrease_mach;
     tired = iter >= itmax;
     breakdown = (alpha == 0 || std::isnan(alpha));
-    overtimed = time_limit_reached(ctx, now_s() - t0, timemax);
+    host_exit(ws, o, t0, timemax, &user_requested_exit, &overtimed);
     if (kdisplay(iter, verbose)) klogf(o.log_fd, "%5lld  %7.1e  %8.1e  %8.1e  %.2fs\n", (long long)iter, rNorm, std::fabs(alpha), std::fabs(omega), now_s() - t0);   // :255
   }
 
@@ -1570,18 +1539,7 @@ int khip_bicgstab_solve(khip_bicgstab_workspace *ws, const khip_operator *A, con
   if (user_requested_exit) status = "user-requested exit";
   if (overtimed) status = "time limit exceeded";
 
-  if (warm_start) K(khip_axpy(ctx, n, 1.0, dx, x));
-  ws->warm_start = false;
-  K(khip_ctx_sync(ctx));
-
-  st->niter = (int)iter;
-  st->solved = solved;
-  st->inconsistent = 0;
-  st->timer = now_s() - t0;
-  st->allocation_timer += take_alloc_seconds();                 // lazy allocations of this solve (allocate_if)
-  snprintf(st->status, sizeof(st->status), "%s", status);
-  ws->box.publish();
-  return KHIP_OK;
+  return ws_end(ws, {iter, solved, 0, status, warm_start, t0, true});
 }
 
 }  // extern "C"

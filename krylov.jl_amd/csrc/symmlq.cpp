@@ -173,25 +173,6 @@ void verbose_row(const khip_options &o, long long iter, const SymmlqDevState &s,
           s.test1, now_s() - t0);
 }
 
-// every return of khip_symmlq_solve past the checks (:180-192, :436-463)
-int symmlq_end(W *ws, int64_t iter, int solved, const char *status, bool warm_start, double Anorm, double Acond, double t0) {
-  khip_ctx *ctx = ws->ctx;
-  if (warm_start) K(khip_axpy(ctx, ws->n, 1.0, ws->dx, ws->x));
-  ws->warm_start = false;
-  K(khip_ctx_sync(ctx));
-  khip_stats *st = &ws->box.st;
-  st->niter = (int)iter;
-  st->solved = solved;
-  st->inconsistent = 0;
-  ws->Anorm = Anorm;
-  ws->Acond = Acond;
-  st->timer = now_s() - t0;
-  st->allocation_timer += take_alloc_seconds();
-  snprintf(st->status, sizeof(st->status), "%s", status);
-  ws->box.publish();
-  return KHIP_OK;
-}
-
 int new_workspace(khip_ctx *ctx, int64_t m, int64_t n, int window, W **out) {
   W *ws = new W();
   ws->ctx = ctx; ws->m = m; ws->n = n; ws->window = window;
@@ -294,16 +275,7 @@ int khip_symmlq_solve(khip_symmlq_workspace *ws, const khip_operator *A, const k
   const int window = ws->window;
   (void)take_alloc_seconds();
 
-  if (A->csr && !A->apply) {                                                                               // :138-139
-    int64_t am, an;
-    khip_csr_shape(A->csr, &am, &an, nullptr);
-    if (am != ws->m || (an != ws->n && !A->csr->dist)) {                   // a row-partitioned handle counts global columns
-      char msg[160];
-      snprintf(msg, sizeof(msg), "(workspace.m, workspace.n) = (%lld, %lld) is inconsistent with size(A) = (%lld, %lld)",
-               (long long)ws->m, (long long)ws->n, (long long)am, (long long)an);
-      return ws->box.fail(KHIP_ERR_INVALID, msg);
-    }
-  }
+  if (int rc = check_shape(ws, {A})) return rc;                                                            // :138-139
   if (ws->m != ws->n) return ws->box.fail(KHIP_ERR_INVALID, "System must be square");
   if (o.variant != 0) return ws->box.fail(KHIP_ERR_INVALID, "symmlq: options.variant must be 0 (there is no other recurrence)");
   if (o.verbose > 0) klogf(o.log_fd, "SYMMLQ: system of size %lld\n", (long long)n);                      // :142
@@ -321,20 +293,14 @@ int khip_symmlq_solve(khip_symmlq_workspace *ws, const khip_operator *A, const k
 
   // set-up, the same primitives on every path (:166-264)
   K(khip_fill(ctx, n, x, 0.0));
-  if (warm_start) {
-    K(apply_op(ctx, A, ws->dx, B.Mvold));
-    if (lambda != 0) K(khip_axpy(ctx, n, lambda, ws->dx, B.Mvold));
-    K(khip_axpby(ctx, n, 1.0, b, -1.0, B.Mvold));
-  } else {
-    K(khip_copy(ctx, n, B.Mvold, b));
-  }
+  K(residual0(ws, A, lambda, b, warm_start, B.Mvold));
   double *vold = MisI ? B.Mvold : vM;
   if (!MisI) K(apply_op(ctx, M, B.Mvold, vold));                                                           // :178
   double beta1;
   K(khip_dot(ctx, n, vold, B.Mvold, &beta1));
   if (beta1 == 0) {                                                                                        // :180-192
     if (history) { ws->box.push(0.0); ws->residualscg.push_back(0.0); }
-    return symmlq_end(ws, 0, 1, "x is a zero-residual solution", warm_start, NAN, NAN, t0);
+    return ws_end(ws, {0, 1, 0, "x is a zero-residual solution", warm_start, t0, true});   // Anorm, Acond stay NaN
   }
   // ⟨b, M b⟩ < 0: the reference takes the square root (:193, a DomainError); the message of its later check (:205) says why
   if (beta1 < 0) return ws->box.fail(KHIP_ERR_INVALID, "Preconditioner is not positive definite");
@@ -428,11 +394,7 @@ int khip_symmlq_solve(khip_symmlq_workspace *ws, const khip_operator *A, const k
     }
     if (kdisplay(k, o.verbose)) verbose_row(o, k, s, c_k, s_k, t0, false);
     tired = k >= itmax;
-    if (o.callback) {
-      ws->box.publish();                          // the callback reads stats.residuals
-      user_exit = o.callback(ws, o.callback_data) != 0;
-    }
-    overtimed = time_limit_reached(ctx, now_s() - t0, timemax);
+    host_exit(ws, o, t0, timemax, &user_exit, &overtimed);
     return KHIP_OK;
   };
   const char *not_pd_msg = "Preconditioner is not positive definite";                                      // :307
@@ -500,33 +462,19 @@ int khip_symmlq_solve(khip_symmlq_workspace *ws, const khip_operator *A, const k
     const Roles first = B;
     const khip_csr *Ac = A->csr;
     auto step = [&](SymmlqDevState *dev, long long j) {
-      ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j, EPI_NONE, nullptr};
-      int rc = launch_p1(ctx, n, dev, B.Mv, x, wbar, j >= 1);                                             // :292-295 (and :309 of k - 1)
-      if (rc != KHIP_OK) return rc;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j + 1, EPI_SYMMLQ_A, dev};
-      int slot = take_slots(ctx, 1);
-      rc = spmv_any(ctx, Ac, B.Mv, B.Mv_next, slot);                                                      // :299-300  v.t -> α
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-      if (rc != KHIP_OK) return rc;
-      ctx->ctl = SeqCtl{&dev->stop_seq, 3 * j + 2, EPI_SYMMLQ_B, dev};
-      slot = take_slots(ctx, 1);
-      rc = launch_p2(ctx, n, dev, B.Mv, B.Mvold, B.Mv_next, true, slot);                                  // :301-306  t.t -> β, the tests
-      if (rc == KHIP_OK && ctx->comm) rc = comm_allreduce_dd_device(ctx, slot, 1);
-      ctx->ctl = SeqCtl{};
-      if (rc != KHIP_OK) return rc;
+      KHIP_TRY(dev_pass(ctx, &dev->stop_seq, 3 * j, EPI_NONE, nullptr, [&] {
+        return launch_p1(ctx, n, dev, B.Mv, x, wbar, j >= 1); }));                                        // :292-295 (and :309 of k - 1)
+      KHIP_TRY(dev_stage(ctx, dev, 3 * j + 1, EPI_SYMMLQ_A, 1, [&](int slot) {
+        return spmv_any(ctx, Ac, B.Mv, B.Mv_next, slot); }));                                             // :299-300  v.t -> α
+      KHIP_TRY(dev_stage(ctx, dev, 3 * j + 2, EPI_SYMMLQ_B, 1, [&](int slot) {
+        return launch_p2(ctx, n, dev, B.Mv, B.Mvold, B.Mv_next, true, slot); }));                         // :301-306  t.t -> β, the tests
       B.rotate();
       return (int)KHIP_OK;
     };
-    // a finite timemax: the first chunk is ONE iteration, so that a limit already used up stops after iteration 1 as the
-    // host-driven loop does
-    const DeviceLoopArgs loop_args{itmax, t0, timemax, history, {&ws->box.residuals, &ws->residualscg, nullptr},
-                                   timemax < 1e300 ? 1 : kDevChunk};
-    K(ws->loop.run(ctx, s, loop_args, step, &s, &overtimed));
+    K(ws->loop.run(ctx, s, device_loop_args(itmax, t0, timemax, history, {&ws->box.residuals, &ws->residualscg}), step, &s, &overtimed));
     iter = s.iter;
     tired = iter >= itmax;
-    // the host rotated the roles for every iteration it enqueued; the device ran s.iter of them
-    B = first;
-    for (int64_t j = 0; j < iter % 3; ++j) B.rotate();
+    B = replay(first, iter, 3, [](Roles &r) { r.rotate(); });
     if (iter > 0) K(khip_scal(ctx, n, 1.0 / s.beta, B.Mv));                                               // :309 of the last iteration
   }
   ws->Mvold = B.Mvold; ws->Mv = B.Mv; ws->Mv_next = B.Mv_next;
@@ -543,7 +491,9 @@ int khip_symmlq_solve(khip_symmlq_workspace *ws, const khip_operator *A, const k
   if (s.solved_cg) status = "solution x\xe1\xb6\x9c good enough given atol and rtol";
   if (user_exit) status = "user-requested exit";
   if (overtimed) status = "time limit exceeded";
-  return symmlq_end(ws, iter, s.solved ? 1 : 0, status, warm_start, s.ANorm, s.Acond, t0);              // :453-463
+  ws->Anorm = s.ANorm;
+  ws->Acond = s.Acond;
+  return ws_end(ws, {iter, s.solved ? 1 : 0, 0, status, warm_start, t0, true});                           // :453-463
 }
 
 }  // extern "C"
