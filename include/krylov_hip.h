@@ -214,7 +214,8 @@ int khip_profile_spmv(khip_ctx *ctx, int64_t *launches, double *total_ms);
  * Gram-Schmidt step Q -= V Psi ; Psi' = V' Q), 4 = panel_multi_nn (X += sum V_i Y_i), 5 = panel_gemm_nn, 6 = the panel QR's passes
  * (scale + Gram), 7 = halo pack kernel, 8 = halo transfer (grouped ncclSend / ncclRecv or the all-gather of x, bracketed on the
  * stream it runs on), 9 = a dot's 16-byte all-gather + combine kernel, 10 = the boundary rows' SpMV launch of a row-partitioned
- * product (tag 0 then is the interior launch); at most 11 families.  Synchronises the context's streams and resets every counter. */
+ * product (tag 0 then is the interior launch), 11 / 12 / 13 = the fused passes P1, P2 and P3 of usymqr! (the pass's own kernel, without
+ * the reduction's finish kernel); at most 14 families.  Synchronises the context's streams and resets every counter. */
 int khip_profile_kernels(khip_ctx *ctx, int ntags, int64_t *launches, double *total_ms);
 
 /* ------------------------------------------------ BLAS-1 shim ---------------- */
@@ -671,6 +672,39 @@ int khip_bilqr_last_path(khip_bilqr_workspace *ws);
 /* named work vectors: "u_prev", "u", "q", "v_prev", "v", "p", "x", "y", "dbar", "w_prev3", "w_prev2", "dx", "dy" (NULL while not allocated) */
 double           *khip_bilqr_vector(khip_bilqr_workspace *ws, const char *name);
 size_t            khip_bilqr_workspace_bytes(khip_bilqr_workspace *ws);   /* 11n doubles without warm start */
+
+/* ---- usymqr! (src/usymqr.jl:130-365), real Float64: A x = b with A of m rows and n columns by the orthogonal tridiagonalisation of
+ * Saunders, Simon and Yip, started from b and c; the minimum-residual iterate, with ‖rₖ‖ and ‖Aᴴrₖ₋₁‖ both tested (stats.solved,
+ * stats.inconsistent).  There is no M or N.  UsymqrWorkspace (src/krylov_workspaces.jl): vₖ₋₁, vₖ, q (m doubles each), x, wₖ₋₂, wₖ₋₁,
+ * uₖ₋₁, uₖ, p (n doubles each); Δx ("dx", n doubles) stays empty until a warm start.  The adjoint travels as its own operator, as for
+ * qmr!.  options.radius, linesearch, restart, reorthogonalization and variant are ignored.  The fused loops rotate the roles of
+ * (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and (wₖ₋₂, wₖ₋₁) instead of copying or swapping, and khip_usymqr_vector returns a name's pointer by its current
+ * role: after k iterations every name holds what the reference's variable of that name holds ("w_prev" = wₖ, "w_prev2" = wₖ₋₁), in
+ * whichever buffer. */
+typedef struct khip_usymqr_workspace khip_usymqr_workspace;
+int khip_usymqr_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_usymqr_workspace **out);   /* m != n is allowed */
+/* UsymqrWorkspace on the caller's nine vectors, in the reference's order; every pointer must be distinct.  adopt_vector names: "dx"
+ * (Δx: warm_start! fills it on the caller's side and hands it over, then khip_usymqr_warm_start(ws, dx) only sets the flag) */
+int khip_usymqr_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *v_prev, double *v, double *q, double *x, double *w_prev2,
+                                double *w_prev, double *u_prev, double *u, double *p, khip_usymqr_workspace **out);
+int khip_usymqr_workspace_adopt_vector(khip_usymqr_workspace *ws, const char *name, double *ptr);
+int khip_usymqr_workspace_destroy(khip_usymqr_workspace *ws);
+int khip_usymqr_warm_start(khip_usymqr_workspace *ws, const double *x0);
+/* usymqr!(ws, A, b, c; atol, rtol, itmax, timemax, verbose, history, callback).  At = A' (n rows, m columns) and c (n doubles) are
+ * required (NULL: KHIP_ERR_INVALID); itmax = 0 means m + n of the global system.
+ * Loops (khip_usymqr_last_path): 2 = device-resident (m = n, A and At CSR handles, no callback, verbose = 0), 1 = host-driven on the
+ * same kernels (same bits as 2), 0 = one launch per primitive (options.fused = 0).  A rectangular system (m != n) runs loop 0
+ * whatever options.fused says, and last_path reports 0; a row-partitioned rectangular handle is KHIP_ERR_UNSUPPORTED. */
+int khip_usymqr_solve(khip_usymqr_workspace *ws, const khip_operator *A, const khip_operator *At, const double *b, const double *c,
+                      const khip_options *opts);
+double           *khip_usymqr_solution(khip_usymqr_workspace *ws);
+const khip_stats *khip_usymqr_stats(khip_usymqr_workspace *ws);           /* residuals = the reference's stats.residuals */
+/* stats.Aresiduals of the last solve (history = true), owned by the workspace until its next solve */
+int khip_usymqr_aresiduals(khip_usymqr_workspace *ws, const double **aresiduals, int *naresiduals);
+int khip_usymqr_last_path(khip_usymqr_workspace *ws);
+/* named work vectors: "v_prev", "v", "q", "x", "w_prev2", "w_prev", "u_prev", "u", "p", "dx" (NULL while not allocated) */
+double           *khip_usymqr_vector(khip_usymqr_workspace *ws, const char *name);
+size_t            khip_usymqr_workspace_bytes(khip_usymqr_workspace *ws);   /* 3m + 6n doubles without warm start */
 
 /* ---- cgs! (src/cgs.jl:126-281), real Float64: square nonsymmetric systems by the conjugate gradient squared recurrence; transpose-
  * free (no A'), two products with A per iteration.  CgsWorkspace (src/krylov_workspaces.jl): x, r, u, p, q, ts; Δx, yz and vw ("dx",

@@ -648,6 +648,60 @@ function Krylov.qmr!(ws::QmrWs, A::HIPCsr, b::HIPVector; c::HIPVector = b, M = I
   return ws
 end
 
+# ------------------------------------------------------------------------------------------------ usymqr!  (src/usymqr.jl:130-365)
+const UsymqrWs = UsymqrWorkspace{Float64,Float64,HIPVector,HIPVector}
+function usymqr_handle(ws::UsymqrWs)
+  get!(HANDLES, ws) do
+    r = Ref{Ptr{Cvoid}}()
+    ck(ccall((:khip_usymqr_workspace_adopt, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                                                        Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Ptr{Cvoid}}),
+             CTX[].h, ws.m, ws.n, ws.vₖ₋₁.ptr, ws.vₖ.ptr, ws.q.ptr, ws.x.ptr, ws.wₖ₋₂.ptr, ws.wₖ₋₁.ptr, ws.uₖ₋₁.ptr, ws.uₖ.ptr, ws.p.ptr, r))
+    h = r[]
+    finalizer(_ -> ccall((:khip_usymqr_workspace_destroy, lib), Cint, (Ptr{Cvoid},), h), ws)
+    h
+  end
+end
+usymqr_adopt(h, name, v::HIPVector) = ck(ccall((:khip_usymqr_workspace_adopt_vector, lib), Cint, (Ptr{Cvoid}, Cstring, Ptr{Cdouble}), h, name, dptr(v)))
+
+# A has m rows and n columns; b has m entries, c has n.  The adjoint is `A'`, built once per matrix and cached in `A.adj`.  A
+# rectangular system runs the library's primitive sequence (LAST_PATH[] == 0) whatever `fused` says.  After the solve only ws.x and
+# ws.stats are defined: the library rotates the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and (wₖ₋₂, wₖ₋₁) among the adopted vectors.
+function Krylov.usymqr!(ws::UsymqrWs, A::HIPCsr, b::HIPVector, c::HIPVector;
+                        atol::Float64 = √eps(Float64), rtol::Float64 = √eps(Float64), itmax::Int = 0, timemax::Float64 = Inf,
+                        verbose::Int = 0, history::Bool = false, callback = nothing, iostream::IO = Krylov.kstdout, fused::Int = 2)
+  if !native_log(verbose, iostream)
+    GENERIC_SOLVES[] += 1
+    return invoke(Krylov.usymqr!, Tuple{UsymqrWs,Any,AbstractVector{Float64},AbstractVector{Float64}}, ws, A, b, c; atol, rtol, itmax, timemax,
+                  verbose, history, callback = callback === nothing ? (w -> false) : callback, iostream)
+  end
+  m, n = size(A)                                                                            # :133-136
+  (m == ws.m && n == ws.n) || error("(workspace.m, workspace.n) = ($(ws.m), $(ws.n)) is inconsistent with size(A) = ($m, $n)")
+  length(b) == m || error("Inconsistent problem size")
+  length(c) == n || error("Inconsistent problem size")
+  At = A'
+  h = usymqr_handle(ws)
+  usymqr_adopt(h, "dx", ws.Δx)
+  ws.warm_start && ck(ccall((:khip_usymqr_warm_start, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h, ws.Δx.ptr))
+  sp = ccall((:khip_usymqr_stats, lib), Ptr{Stats}, (Ptr{Cvoid},), h)
+  cbf, cbd, box = callback_args(user_callback(callback), ws, sp, history)
+  opts = Ref(Options(; atol, rtol, itmax, timemax, history, fused, verbose, log_fd = logfd(iostream), callback = cbf, callback_data = cbd))
+  opA = Ref(Operator(A));  opAt = Ref(Operator(At))
+  rc = GC.@preserve ws A At b c opts opA opAt box ccall((:khip_usymqr_solve, lib), Cint,
+         (Ptr{Cvoid}, Ref{Operator}, Ref{Operator}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Options}),
+         h, opA, opAt, b.ptr, c.ptr, opts)
+  st = fill_stats!(ws.stats, sp, history)
+  if history                                                                                # stats.Aresiduals
+    ar, nar = Ref{Ptr{Cvoid}}(), Ref{Cint}(0)
+    ck(ccall((:khip_usymqr_aresiduals, lib), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Cint}), h, ar, nar))
+    nar[] > 0 && append!(ws.stats.Aresiduals, unsafe_wrap(Array, Ptr{Float64}(ar[]), Int(nar[])))
+  end
+  NATIVE_SOLVES[] += 1;  LAST_PATH[] = ccall((:khip_usymqr_last_path, lib), Cint, (Ptr{Cvoid},), h)
+  ws.warm_start = false
+  finish_callback(box)
+  rc == 0 || failed(st)
+  return ws
+end
+
 # ------------------------------------------------------------------------------------------------ cgs!  (src/cgs.jl:126-281)
 const CgsWs = CgsWorkspace{Float64,Float64,HIPVector}
 function cgs_handle(ws::CgsWs)

@@ -269,3 +269,4 @@ include("bilqr.jl")                                                  # bilqr! ag
 include("cgs.jl")                                                    # cgs! against the generic method, its endings and breakdowns
 include("symmlq.jl")                                                 # symmlq! against the generic method, its histories and error estimates
 include("minres_qlp.jl")                                             # minres_qlp! against the generic method, singular and inconsistent systems
+include("usymqr.jl")                                                 # usymqr! against the generic method, rectangular and inconsistent systems

@@ -290,6 +290,18 @@ SIGNATURES = {
     "khip_qmr_last_path": (_int, [_vp]),
     "khip_qmr_vector": (_vp, [_vp, C.c_char_p]),
     "khip_qmr_workspace_bytes": (_sz, [_vp]),
+    "khip_usymqr_workspace_create": (_int, [_vp, _i64, _i64, c_void_pp]),
+    "khip_usymqr_workspace_adopt": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_void_pp]),
+    "khip_usymqr_workspace_adopt_vector": (_int, [_vp, C.c_char_p, _vp]),
+    "khip_usymqr_workspace_destroy": (_int, [_vp]),
+    "khip_usymqr_warm_start": (_int, [_vp, _vp]),
+    "khip_usymqr_solve": (_int, [_vp, C.POINTER(COperator), C.POINTER(COperator), _vp, _vp, C.POINTER(COptions)]),
+    "khip_usymqr_solution": (_vp, [_vp]),
+    "khip_usymqr_stats": (C.POINTER(CStats), [_vp]),
+    "khip_usymqr_aresiduals": (_int, [_vp, C.POINTER(c_double_p), C.POINTER(_int)]),
+    "khip_usymqr_last_path": (_int, [_vp]),
+    "khip_usymqr_vector": (_vp, [_vp, C.c_char_p]),
+    "khip_usymqr_workspace_bytes": (_sz, [_vp]),
     "khip_cgs_workspace_create": (_int, [_vp, _i64, _i64, c_void_pp]),
     "khip_cgs_workspace_adopt": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, c_void_pp]),
     "khip_cgs_workspace_adopt_vector": (_int, [_vp, C.c_char_p, _vp]),
@@ -513,7 +525,7 @@ class Context:
         return n.value, ms.value
 
     PROFILE_TAGS = ("spmv", "spmm", "panel_gemm_tn", "panel_nn_tn", "panel_multi_nn", "panel_gemm_nn", "panel_qr_scale_gram",
-                    "halo_pack", "halo_transfer", "dot_allgather_combine", "spmv_boundary")
+                    "halo_pack", "halo_transfer", "dot_allgather_combine", "spmv_boundary", "ssy_p1", "ssy_p2", "usymqr_p3")
 
     def profile_kernels(self):
         """{family: (launches, total_ms)} of the HIP-event brackets recorded since the last call (option profile_spmv = 1):
@@ -1692,6 +1704,46 @@ class QmrWorkspace(_BiLanczosWorkspace):
     VECTORS = ("u_prev", "u", "q", "v_prev", "v", "p", "x", "w_prev2", "w_prev")
 
 
+class UsymqrWorkspace(_Workspace):
+    """UsymqrWorkspace(m, n, Sm, Sn) (src/krylov_workspaces.jl): vₖ₋₁, vₖ, q of m entries and x, wₖ₋₂, wₖ₋₁, uₖ₋₁, uₖ, p of n; Δx ("dx")
+    stays empty until a warm start.  stats carries Aresiduals.  The fused loops rotate the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and
+    (wₖ₋₂, wₖ₋₁), and `vector(name)` follows the role (khip_usymqr_vector): after k iterations a name holds what the reference's
+    variable of that name holds.  A rectangular system (m ≠ n) runs the primitive sequence whatever `fused` says: `last_path`
+    reports 0."""
+    _prefix = "usymqr"
+    VECTORS = ("v_prev", "v", "q", "x", "w_prev2", "w_prev", "u_prev", "u", "p")
+    ROW_SIDE = ("v_prev", "v", "q")                                             # m entries; every other vector has n
+
+    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
+        self.ctx, self.m, self.n = ctx, m, n
+        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
+        self._h = C.c_void_p()
+        if self.adopted:
+            t0 = time.perf_counter()
+            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(self._len(k)) for k in self.VECTORS}   # dx stays empty
+            self._alloc_s = time.perf_counter() - t0
+            _ck(lib().khip_usymqr_workspace_adopt(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
+        else:
+            _ck(lib().khip_usymqr_workspace_create(ctx._h, m, n, C.byref(self._h)))
+
+    def _len(self, name: str) -> int:
+        return self.m if name in self.ROW_SIDE else self.n
+
+    @property
+    def stats(self) -> SimpleStats:
+        st = super().stats
+        ar, nar = c_double_p(), _int()
+        _ck(lib().khip_usymqr_aresiduals(self._h, C.byref(ar), C.byref(nar)))
+        st.Aresiduals = np.array(ar[:nar.value]) if nar.value else np.zeros(0)
+        return st
+
+    def vector(self, name: str):
+        if name == "x":
+            return self.x
+        p = lib().khip_usymqr_vector(self._h, name.encode())
+        return DeviceVector(self.ctx, self._len(name), ptr=p, owner=self) if p else None
+
+
 class CgsWorkspace(_BiLanczosWorkspace):
     """CgsWorkspace(m, n, S) (src/krylov_workspaces.jl): x, r, u, p, q, ts; Δx, yz, vw stay empty until needed.  cgs! rotates no
     roles: every name keeps its buffer."""
@@ -2024,6 +2076,27 @@ def qmr_(ws: QmrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, M=
     return _bilq_qmr_solve(ws, lib().khip_qmr_default_params(), A, b, c, M, N, At, Mt, Nt, kw)
 
 
+def usymqr_(ws: UsymqrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, **kw):
+    """usymqr!(workspace, A, b, c; atol, rtol, itmax, timemax, verbose, history, callback, iostream) (src/usymqr.jl:130-365) for A of m
+    rows and n columns, b of m entries and c of n.  At: the adjoint of A (default: A.transpose(), built once and kept on A); a
+    matrix-free A is callable(x[n], y[m]) and brings At = callable(x[m], y[n]).  Returns the workspace."""
+    keep = []
+    if c is None:
+        raise KhipError(-1, "usymqr: c (the starting vector of the second Krylov space) is required")
+    if len(b) != ws.m or len(c) != ws.n:
+        raise KhipError(-1, "Inconsistent problem size")
+    if At is None:
+        At = _adjoint_of(A, solver="usymqr")
+    opts = _make_options(keep=keep, ws=ws, **kw)
+
+    def operator(op, nin, nout):
+        if op is None or isinstance(op, CsrMatrix):
+            return _make_operator(ws.ctx, op, nin, keep)
+        return _make_operator_mn(ws.ctx, op, nin, nout, keep)
+    rc = lib().khip_usymqr_solve(ws._h, operator(A, ws.n, ws.m), operator(At, ws.m, ws.n), _p(b), _p(c), C.byref(opts))
+    return _finish(ws, rc)
+
+
 def bilqr_(ws: BilqrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, transfer_to_bicg=True, **kw):
     """bilqr!(workspace, A, b, c; transfer_to_bicg, atol, rtol, itmax, timemax, verbose, history, callback, iostream)
     (src/bilqr.jl:116-484): x of A x = b by BiLQ and y of A' y = c by QMR from one two-sided Lanczos process.  At: the adjoint of A
@@ -2081,6 +2154,8 @@ FORWARDED_DEFAULTS = {
                        timemax=math.inf, verbose=0, history=False, callback=default_callback, iostream=None),
     "bilqr": dict(transfer_to_bicg=True, atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0, timemax=math.inf, verbose=0, history=False,
                   callback=default_callback, iostream=None),
+    "usymqr": dict(atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0, timemax=math.inf, verbose=0, history=False,
+                   callback=default_callback, iostream=None),
 }
 WORKSPACE_KWARGS = {"gmres": dict(memory=20), "block_gmres": dict(memory=5)}      # kwargs_workspace_gmres, _block_gmres
 # kwargs_workspace_minres (src/minres.jl:159): kept apart from WORKSPACE_KWARGS, whose contents tests/test_abi.py pins
@@ -2107,7 +2182,10 @@ def krylov_workspace(method: str, *args, ctx: Context | None = None, **kw):
     cls = {"cg": CgWorkspace, "gmres": GmresWorkspace, "bicgstab": BicgstabWorkspace, "block_gmres": BlockGmresWorkspace,
            "minres": MinresWorkspace, "cg_lanczos_shift": CgLanczosShiftWorkspace, "bilq": BilqWorkspace,
            "qmr": QmrWorkspace, "bilqr": BilqrWorkspace, "cgs": CgsWorkspace,
-           "symmlq": SymmlqWorkspace, "minres_qlp": MinresQlpWorkspace}[method]
+           "symmlq": SymmlqWorkspace, "minres_qlp": MinresQlpWorkspace, "usymqr": UsymqrWorkspace}[method]
+    if method == "usymqr" and len(args) == 3:                                   # (A, b, c): m = length(b), n = length(c)
+        A, b, c = args
+        return cls(b.ctx, len(b), len(c), **kw)
     if method == "cg_lanczos_shift":                                            # (A, b, nshifts) / (m, n, nshifts)
         if isinstance(args[1], DeviceVector):
             A, b, nshifts = args
@@ -2170,6 +2248,10 @@ def krylov_solve(method: str, A, b, x0=None, ctx: Context | None = None, **kw):
         ctx = ctx or A.ctx
         ws = krylov_workspace(method, A, B, ctx=ctx, **wkw)
         b = ctx.array(np.asfortranarray(B).ravel(order="F"))
+    elif method == "usymqr":                              # krylov_solve(Val(:usymqr), A, b, c[, x0]; kwargs...): c travels as a keyword here
+        if kw.get("c") is None:
+            raise KhipError(-1, "usymqr: c (the starting vector of the second Krylov space) is required")
+        ws = krylov_workspace(method, A, b, kw["c"], **wkw)
     else:
         ws = krylov_workspace(method, A, b, **wkw)
     if x0 is not None:
@@ -2208,6 +2290,11 @@ def bilq(A, b: DeviceVector, x0=None, **kw):
 def qmr(A, b: DeviceVector, x0=None, **kw):
     """Out-of-place qmr(A, b[, x0]; kwargs...) -> (x, stats, workspace) (src/qmr.jl:124-132); A' is taken once and kept on A."""
     return krylov_solve("qmr", A, b, x0, **kw)
+
+
+def usymqr(A, b: DeviceVector, c: DeviceVector, x0=None, **kw):
+    """Out-of-place usymqr(A, b, c[, x0]; kwargs...) -> (x, stats, workspace) (src/usymqr.jl:16-23); A' is taken once and kept on A."""
+    return krylov_solve("usymqr", A, b, x0, c=c, **kw)
 
 
 def cgs(A, b: DeviceVector, x0=None, **kw):
@@ -2693,7 +2780,7 @@ def block_gmres(A, B, X0=None, ctx=None, **kw):
 
 _INPLACE.update({CgWorkspace: ("cg", cg_), GmresWorkspace: ("gmres", gmres_), BicgstabWorkspace: ("bicgstab", bicgstab_),
                  BlockGmresWorkspace: ("block_gmres", block_gmres_), MinresWorkspace: ("minres", minres_), BilqWorkspace: ("bilq", bilq_),
-                 QmrWorkspace: ("qmr", qmr_), CgsWorkspace: ("cgs", cgs_),
+                 QmrWorkspace: ("qmr", qmr_), CgsWorkspace: ("cgs", cgs_), UsymqrWorkspace: ("usymqr", usymqr_),
                  SymmlqWorkspace: ("symmlq", symmlq_),
                  MinresQlpWorkspace: ("minres_qlp", minres_qlp_),
                  BilqrWorkspace: ("bilqr", bilqr_),

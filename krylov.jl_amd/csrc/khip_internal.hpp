@@ -506,7 +506,8 @@ enum ProfTag { kProfSpmv = 0, kProfSpmm = 1, kProfPanelTn = 2, kProfPanelNnTn = 
                kProfHaloXfer = 8,       // grouped ncclSend / ncclRecv (or the all-gather of x), on the stream it runs on
                kProfDotGather = 9,      // 16-byte all-gather of a dot's (hi, lo) partials + combine kernel
                kProfSpmvBoundary = 10,  // the boundary rows' launch of a row-partitioned product (after the halo has arrived)
-               kProfTags = 11 };
+               kProfSsyP1 = 11, kProfSsyP2 = 12, kProfUsymqrP3 = 13,   // the fused passes of usymqr! (ssy.hpp, usymqr.cpp), without their finish kernels
+               kProfTags = 14 };
 struct ProfScope {
   khip_ctx *ctx;
   hipEvent_t stop = nullptr;

@@ -18,7 +18,8 @@ enum Epilogue { EPI_NONE = 0, EPI_CG_STEP1 = 1, EPI_CG_STEP2 = 2, EPI_BICG_A = 3
                EPI_MINRES_A = 7, EPI_MINRES_B = 8, EPI_MINRES_C = 9, EPI_LZSHIFT_A = 10, EPI_LZSHIFT_B = 11,
                EPI_BILQ_A = 12, EPI_BILQ_B = 13, EPI_BILQ_C = 14, EPI_QMR_A = 15, EPI_QMR_B = 16, EPI_QMR_C = 17,
                EPI_BILQR_A = 18, EPI_BILQR_B = 19, EPI_BILQR_C = 20, EPI_CGS_A = 21, EPI_CGS_B = 22,
-               EPI_SYMMLQ_A = 23, EPI_SYMMLQ_B = 24, EPI_MINRES_QLP_X = 25, EPI_MINRES_QLP_A = 26, EPI_MINRES_QLP_B = 27 };
+               EPI_SYMMLQ_A = 23, EPI_SYMMLQ_B = 24, EPI_MINRES_QLP_X = 25, EPI_MINRES_QLP_A = 26, EPI_MINRES_QLP_B = 27,
+               EPI_USYMQR_A = 28, EPI_USYMQR_B = 29 };
 
 struct CgDevState {
   double gamma;        // r.z of the current iterate              (src/cg.jl:162, 257)
@@ -961,6 +962,86 @@ __host__ __device__ inline bool minres_qlp_step_b(MinresQlpDevState &st, double 
   return stop;
 }
 
+// usymqr! (src/usymqr.jl:130-365), real Float64: the scalars of the orthogonal tridiagonalisation of Saunders, Simon and Yip, of the
+// QR factorisation of Tₖ₊₁.ₖ, the two residual norms and the stopping tests.  As for qmr!: the same two steps run on the host (loops 0
+// and 1) and as the epilogues of the two reductions of an iteration (device-resident loop), so loops 1 and 2 produce the same bits.
+// The coefficients of the process that P1 and P2 (ssy.hpp) read: the leading part of the state of every solver built on it.
+struct SsyCoef {
+  double gamma, beta;            // γₖ, βₖ: P1                                   (src/usymqr.jl:215-216)
+  double alpha;                  // αₖ: P2                                       (:219-222)
+};
+
+struct UsymqrDevState : SsyCoef {
+  // coefficients the vector kernels read (γₖ, βₖ, αₖ: SsyCoef)
+  double beta_next, gamma_next;  // βₖ₊₁, γₖ₊₁: the divisors of P3               (:224-225, :312-317)
+  double neg_eps, neg_lambda;    // -ϵₖ₋₂, -λₖ₋₁: kscal! and the first kaxpy! of wₖ (:283, :289, :291)
+  double delta, inv_delta;       // δₖ: kdivcopy!(w₁, u₁, δ₁) (:278); one(T) / δₖ: kdiv!(wₖ, δₖ) = kscal!(one(T) / δₖ) (:285, :293)
+  double zeta;                   // ζₖ: x = x + ζₖ wₖ                             (:298)
+  // constants of the solve
+  double eps_tol, kappa;         // ε = atol + rtol ‖r₀‖ (:178); κ = atol + rtol ‖Aᴴr₀‖, known after iteration 1 (:336)
+  double atol, rtol;
+  // recurrences
+  double c_km2, c_km1, s_km2, s_km1;   // cₖ₋₂, cₖ₋₁, sₖ₋₂, sₖ₋₁
+  double epsilon, lambda;        // ϵₖ₋₂, λₖ₋₁
+  double dbar;                   // δbarₖ
+  double zbar;                   // ζbarₖ
+  double rNorm, ArNorm;          // ‖rₖ‖, ‖Aᴴrₖ₋₁‖
+  long long stop_seq, iter, hist_base, hist_cap;
+  double *hist_r, *hist_ar;      // device history windows of residuals and Aresiduals (null: no history)
+  int solved, inconsistent;
+};
+
+// after αₖ = ⟨vₖ, q⟩ (:219)
+__host__ __device__ inline void usymqr_step_a(UsymqrDevState &s, double vq) { s.alpha = vq; }
+
+// after ‖q‖² and ‖p‖²: βₖ₊₁, γₖ₊₁, the two previous reflections, the new one, ζₖ and ζbarₖ₊₁, the two residual norms, their history
+// entries, κ at k = 1, the shifts and the tests (:224-339); k = iter.  True when the loop stops (tired / overtimed / the callback are
+// the driver's).  P3 of this iteration still runs: the reference updates x, vₖ₊₁ and uₖ₊₁ before it tests.
+__host__ __device__ inline bool usymqr_step_b(UsymqrDevState &s, double qq, double pp, long long k) {
+  s.beta_next = sqrt(qq);
+  s.gamma_next = sqrt(pp);
+  double lbar = 0.0;             // λbarₖ₋₁
+  if (k >= 3) {
+    s.epsilon = s.s_km2 * s.gamma;
+    lbar = -s.c_km2 * s.gamma;
+  }
+  if (k >= 2) {
+    if (k == 2) lbar = s.gamma;
+    s.lambda = s.c_km1 * lbar + s.s_km1 * s.alpha;
+    s.dbar = s.s_km1 * lbar - s.c_km1 * s.alpha;
+  } else {
+    s.dbar = s.alpha;
+  }
+  double c, sn;
+  sym_givens(s.dbar, s.beta_next, c, sn, s.delta);
+  s.zeta = c * s.zbar;
+  const double zbar_next = sn * s.zbar;
+  s.rNorm = fabs(zbar_next);
+  const double cg = s.c_km1 * s.gamma_next;                  // cₖ₋₁ of before the shift, γₖ₊₁ of this iteration (:305)
+  s.ArNorm = fabs(s.zbar) * sqrt(s.dbar * s.dbar + cg * cg);
+  if (s.hist_r) {
+    const long long idx = k - 1 - s.hist_base;
+    if (idx >= 0 && idx < s.hist_cap) { s.hist_r[idx] = s.rNorm; s.hist_ar[idx] = s.ArNorm; }
+  }
+  if (k == 1) s.kappa = s.atol + s.rtol * s.ArNorm;
+  s.neg_eps = -s.epsilon;
+  s.neg_lambda = -s.lambda;
+  s.inv_delta = 1.0 / s.delta;
+  if (k >= 2) {
+    s.s_km2 = s.s_km1;
+    s.c_km2 = s.c_km1;
+  }
+  s.s_km1 = sn;
+  s.c_km1 = c;
+  s.zbar = zbar_next;
+  s.gamma = s.gamma_next;        // P3 divides by gamma_next and beta_next; the next P1 reads gamma and beta
+  s.beta = s.beta_next;
+  s.solved = (s.rNorm <= s.eps_tol) ? 1 : 0;
+  s.inconsistent = (!s.solved && s.ArNorm <= s.kappa) ? 1 : 0;
+  s.iter = k;
+  return s.solved || s.inconsistent;
+}
+
 __device__ __forceinline__ bool seq_skip(const long long *stop_seq, long long seq) {
   return stop_seq != nullptr && seq >= *stop_seq;
 }
@@ -1113,6 +1194,11 @@ __device__ inline void solver_epilogue(int epi, void *state, const double *v, lo
   } else if (epi == EPI_MINRES_QLP_B) {            // v[0] = p.p = βₖ₊₁²         :261-504
     MinresQlpDevState *st = static_cast<MinresQlpDevState *>(state);
     if (minres_qlp_step_b(*st, v[0], st->xNorm, st->iter + 1)) st->stop_seq = seq + 1;
+  } else if (epi == EPI_USYMQR_A) {                // v[0] = v.q                 src/usymqr.jl:219
+    usymqr_step_a(*static_cast<UsymqrDevState *>(state), v[0]);
+  } else if (epi == EPI_USYMQR_B) {                // v = (q.q, p.p)             :224-339
+    UsymqrDevState *st = static_cast<UsymqrDevState *>(state);
+    if (usymqr_step_b(*st, v[0], v[1], st->iter + 1)) st->stop_seq = seq + 2;   // P3 of this iteration (seq + 1) still runs (:276-317)
   }
 }
 

@@ -244,6 +244,10 @@ void set_history(SymmlqDevState &s, double *w) {
   s.hist = w;
   s.hist_cg = w ? w + kHistWindowMax : nullptr;
 }
+void set_history(UsymqrDevState &s, double *w) {
+  s.hist_r = w;
+  s.hist_ar = w ? w + kHistWindowMax : nullptr;
+}
 void set_history(BilqrDevState &s, double *w) {
   s.hist_p = w;
   s.hist_d = w ? w + kHistWindowMax : nullptr;
