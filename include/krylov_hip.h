@@ -215,7 +215,7 @@ int khip_profile_spmv(khip_ctx *ctx, int64_t *launches, double *total_ms);
  * (scale + Gram), 7 = halo pack kernel, 8 = halo transfer (grouped ncclSend / ncclRecv or the all-gather of x, bracketed on the
  * stream it runs on), 9 = a dot's 16-byte all-gather + combine kernel, 10 = the boundary rows' SpMV launch of a row-partitioned
  * product (tag 0 then is the interior launch), 11 / 12 / 13 = the fused passes P1, P2 and P3 of usymqr! (the pass's own kernel, without
- * the reduction's finish kernel); at most 14 families.  Synchronises the context's streams and resets every counter. */
+ * the reduction's finish kernel), 14 = P3 of usymlq! (its P1 and P2 are 11 and 12); at most 15 families.  Synchronises the context's streams and resets every counter. */
 int khip_profile_kernels(khip_ctx *ctx, int ntags, int64_t *launches, double *total_ms);
 
 /* ------------------------------------------------ BLAS-1 shim ---------------- */
@@ -705,6 +705,41 @@ int khip_usymqr_last_path(khip_usymqr_workspace *ws);
 /* named work vectors: "v_prev", "v", "q", "x", "w_prev2", "w_prev", "u_prev", "u", "p", "dx" (NULL while not allocated) */
 double           *khip_usymqr_vector(khip_usymqr_workspace *ws, const char *name);
 size_t            khip_usymqr_workspace_bytes(khip_usymqr_workspace *ws);   /* 3m + 6n doubles without warm start */
+
+/* ---- usymlq! (src/usymlq.jl:124-366), real Float64: the minimum-error counterpart of usymqr! on the same process, A of m rows and
+ * n columns, started from b and c; with transfer_to_usymcg the USYMCG point xᶜ is tested as well and returned when it is the one that
+ * meets the tolerance.  There is no M or N.  UsymlqWorkspace (src/krylov_workspaces.jl): uₖ₋₁, uₖ, p, x, d̅ (n doubles each), vₖ₋₁, vₖ,
+ * q (m doubles each); Δx ("dx", n doubles) stays empty until a warm start.  The adjoint travels as its own operator.
+ * options.radius, linesearch, restart, reorthogonalization and variant are ignored.  The fused loops rotate the roles of (vₖ₋₁, vₖ)
+ * and (uₖ₋₁, uₖ) instead of copying, and khip_usymlq_vector returns a name's pointer by its current role: after k iterations every
+ * name holds what the reference's variable of that name holds ("dbar" = d̅ₖ), in whichever buffer. */
+typedef struct khip_usymlq_workspace khip_usymlq_workspace;
+typedef struct khip_usymlq_params {
+  int transfer_to_usymcg;      /* also test and return the USYMCG point xᶜ; default 1      (src/usymlq.jl:107) */
+} khip_usymlq_params;
+khip_usymlq_params khip_usymlq_default_params(void);   /* transfer_to_usymcg = 1 */
+int khip_usymlq_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_usymlq_workspace **out);   /* m != n is allowed */
+/* UsymlqWorkspace on the caller's eight vectors, in the reference's order; every pointer must be distinct.  adopt_vector names: "dx"
+ * (Δx: warm_start! fills it on the caller's side and hands it over, then khip_usymlq_warm_start(ws, dx) only sets the flag) */
+int khip_usymlq_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *u_prev, double *u, double *p, double *x, double *dbar,
+                                double *v_prev, double *v, double *q, khip_usymlq_workspace **out);
+int khip_usymlq_workspace_adopt_vector(khip_usymlq_workspace *ws, const char *name, double *ptr);
+int khip_usymlq_workspace_destroy(khip_usymlq_workspace *ws);
+int khip_usymlq_warm_start(khip_usymlq_workspace *ws, const double *x0);
+/* usymlq!(ws, A, b, c; transfer_to_usymcg, atol, rtol, itmax, timemax, verbose, history, callback).  At = A' (n rows, m columns) and
+ * c (n doubles) are required (NULL: KHIP_ERR_INVALID); itmax = 0 means m + n of the global system; params = NULL means the defaults.
+ * stats.inconsistent is always 0.
+ * Loops (khip_usymlq_last_path): 2 = device-resident (m = n, A and At CSR handles, no callback, verbose = 0), 1 = host-driven on the
+ * same kernels (same bits as 2), 0 = one launch per primitive (options.fused = 0).  A rectangular system (m != n) runs loop 0
+ * whatever options.fused says, and last_path reports 0; a row-partitioned rectangular handle is KHIP_ERR_UNSUPPORTED. */
+int khip_usymlq_solve(khip_usymlq_workspace *ws, const khip_operator *A, const khip_operator *At, const double *b, const double *c,
+                      const khip_options *opts, const khip_usymlq_params *params);
+double           *khip_usymlq_solution(khip_usymlq_workspace *ws);
+const khip_stats *khip_usymlq_stats(khip_usymlq_workspace *ws);           /* residuals = the reference's stats.residuals */
+int khip_usymlq_last_path(khip_usymlq_workspace *ws);
+/* named work vectors: "u_prev", "u", "p", "x", "dbar", "v_prev", "v", "q", "dx" (NULL while not allocated) */
+double           *khip_usymlq_vector(khip_usymlq_workspace *ws, const char *name);
+size_t            khip_usymlq_workspace_bytes(khip_usymlq_workspace *ws);   /* 5n + 3m doubles without warm start */
 
 /* ---- cgs! (src/cgs.jl:126-281), real Float64: square nonsymmetric systems by the conjugate gradient squared recurrence; transpose-
  * free (no A'), two products with A per iteration.  CgsWorkspace (src/krylov_workspaces.jl): x, r, u, p, q, ts; Δx, yz and vw ("dx",

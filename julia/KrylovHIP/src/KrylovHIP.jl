@@ -702,6 +702,59 @@ function Krylov.usymqr!(ws::UsymqrWs, A::HIPCsr, b::HIPVector, c::HIPVector;
   return ws
 end
 
+# ------------------------------------------------------------------------------------------------ usymlq!  (src/usymlq.jl:124-366)
+struct UsymlqParams                # khip_usymlq_params: transfer_to_usymcg
+  transfer_to_usymcg::Cint
+end
+const UsymlqWs = UsymlqWorkspace{Float64,Float64,HIPVector,HIPVector}
+function usymlq_handle(ws::UsymlqWs)
+  get!(HANDLES, ws) do
+    r = Ref{Ptr{Cvoid}}()
+    ck(ccall((:khip_usymlq_workspace_adopt, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                                                        Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Ptr{Cvoid}}),
+             CTX[].h, ws.m, ws.n, ws.uₖ₋₁.ptr, ws.uₖ.ptr, ws.p.ptr, ws.x.ptr, ws.d̅.ptr, ws.vₖ₋₁.ptr, ws.vₖ.ptr, ws.q.ptr, r))
+    h = r[]
+    finalizer(_ -> ccall((:khip_usymlq_workspace_destroy, lib), Cint, (Ptr{Cvoid},), h), ws)
+    h
+  end
+end
+usymlq_adopt(h, name, v::HIPVector) = ck(ccall((:khip_usymlq_workspace_adopt_vector, lib), Cint, (Ptr{Cvoid}, Cstring, Ptr{Cdouble}), h, name, dptr(v)))
+
+# A has m rows and n columns; b has m entries, c has n.  The adjoint is `A'`, built once per matrix and cached in `A.adj`.  A
+# rectangular system runs the library's primitive sequence (LAST_PATH[] == 0) whatever `fused` says.  After the solve only ws.x and
+# ws.stats are defined: the library rotates the roles of (vₖ₋₁, vₖ) and (uₖ₋₁, uₖ) among the adopted vectors.
+function Krylov.usymlq!(ws::UsymlqWs, A::HIPCsr, b::HIPVector, c::HIPVector; transfer_to_usymcg::Bool = true,
+                        atol::Float64 = √eps(Float64), rtol::Float64 = √eps(Float64), itmax::Int = 0, timemax::Float64 = Inf,
+                        verbose::Int = 0, history::Bool = false, callback = nothing, iostream::IO = Krylov.kstdout, fused::Int = 2)
+  if !native_log(verbose, iostream)
+    GENERIC_SOLVES[] += 1
+    return invoke(Krylov.usymlq!, Tuple{UsymlqWs,Any,AbstractVector{Float64},AbstractVector{Float64}}, ws, A, b, c; transfer_to_usymcg, atol,
+                  rtol, itmax, timemax, verbose, history, callback = callback === nothing ? (w -> false) : callback, iostream)
+  end
+  m, n = size(A)                                                                            # :130-133
+  (m == ws.m && n == ws.n) || error("(workspace.m, workspace.n) = ($(ws.m), $(ws.n)) is inconsistent with size(A) = ($m, $n)")
+  length(b) == m || error("Inconsistent problem size")
+  length(c) == n || error("Inconsistent problem size")
+  At = A'
+  h = usymlq_handle(ws)
+  usymlq_adopt(h, "dx", ws.Δx)
+  ws.warm_start && ck(ccall((:khip_usymlq_warm_start, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), h, ws.Δx.ptr))
+  sp = ccall((:khip_usymlq_stats, lib), Ptr{Stats}, (Ptr{Cvoid},), h)
+  cbf, cbd, box = callback_args(user_callback(callback), ws, sp, history)
+  opts = Ref(Options(; atol, rtol, itmax, timemax, history, fused, verbose, log_fd = logfd(iostream), callback = cbf, callback_data = cbd))
+  prm = Ref(UsymlqParams(Cint(transfer_to_usymcg)))
+  opA = Ref(Operator(A));  opAt = Ref(Operator(At))
+  rc = GC.@preserve ws A At b c opts prm opA opAt box ccall((:khip_usymlq_solve, lib), Cint,
+         (Ptr{Cvoid}, Ref{Operator}, Ref{Operator}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Options}, Ptr{Cvoid}),
+         h, opA, opAt, b.ptr, c.ptr, opts, prm)
+  st = fill_stats!(ws.stats, sp, history)
+  NATIVE_SOLVES[] += 1;  LAST_PATH[] = ccall((:khip_usymlq_last_path, lib), Cint, (Ptr{Cvoid},), h)
+  ws.warm_start = false
+  finish_callback(box)
+  rc == 0 || failed(st)
+  return ws
+end
+
 # ------------------------------------------------------------------------------------------------ cgs!  (src/cgs.jl:126-281)
 const CgsWs = CgsWorkspace{Float64,Float64,HIPVector}
 function cgs_handle(ws::CgsWs)

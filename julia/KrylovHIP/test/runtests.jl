@@ -270,3 +270,4 @@ include("cgs.jl")                                                    # cgs! agai
 include("symmlq.jl")                                                 # symmlq! against the generic method, its histories and error estimates
 include("minres_qlp.jl")                                             # minres_qlp! against the generic method, singular and inconsistent systems
 include("usymqr.jl")                                                 # usymqr! against the generic method, rectangular and inconsistent systems
+include("usymlq.jl")                                                 # usymlq! against the generic method, both points, the breakdown system

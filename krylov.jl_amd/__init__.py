@@ -83,6 +83,10 @@ class CBilqrParams(C.Structure):
     _fields_ = [("transfer_to_bicg", C.c_int)]
 
 
+class CUsymlqParams(C.Structure):
+    _fields_ = [("transfer_to_usymcg", C.c_int)]
+
+
 class CStats(C.Structure):
     _fields_ = [("niter", C.c_int), ("solved", C.c_int), ("inconsistent", C.c_int), ("indefinite", C.c_int),
                 ("npcCount", C.c_int), ("timer", C.c_double), ("status", C.c_char * 96),
@@ -302,6 +306,19 @@ SIGNATURES = {
     "khip_usymqr_last_path": (_int, [_vp]),
     "khip_usymqr_vector": (_vp, [_vp, C.c_char_p]),
     "khip_usymqr_workspace_bytes": (_sz, [_vp]),
+    "khip_usymlq_default_params": (CUsymlqParams, []),
+    "khip_usymlq_workspace_create": (_int, [_vp, _i64, _i64, c_void_pp]),
+    "khip_usymlq_workspace_adopt": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_void_pp]),
+    "khip_usymlq_workspace_adopt_vector": (_int, [_vp, C.c_char_p, _vp]),
+    "khip_usymlq_workspace_destroy": (_int, [_vp]),
+    "khip_usymlq_warm_start": (_int, [_vp, _vp]),
+    "khip_usymlq_solve": (_int, [_vp, C.POINTER(COperator), C.POINTER(COperator), _vp, _vp, C.POINTER(COptions),
+                                 C.POINTER(CUsymlqParams)]),
+    "khip_usymlq_solution": (_vp, [_vp]),
+    "khip_usymlq_stats": (C.POINTER(CStats), [_vp]),
+    "khip_usymlq_last_path": (_int, [_vp]),
+    "khip_usymlq_vector": (_vp, [_vp, C.c_char_p]),
+    "khip_usymlq_workspace_bytes": (_sz, [_vp]),
     "khip_cgs_workspace_create": (_int, [_vp, _i64, _i64, c_void_pp]),
     "khip_cgs_workspace_adopt": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, c_void_pp]),
     "khip_cgs_workspace_adopt_vector": (_int, [_vp, C.c_char_p, _vp]),
@@ -525,7 +542,8 @@ class Context:
         return n.value, ms.value
 
     PROFILE_TAGS = ("spmv", "spmm", "panel_gemm_tn", "panel_nn_tn", "panel_multi_nn", "panel_gemm_nn", "panel_qr_scale_gram",
-                    "halo_pack", "halo_transfer", "dot_allgather_combine", "spmv_boundary", "ssy_p1", "ssy_p2", "usymqr_p3")
+                    "halo_pack", "halo_transfer", "dot_allgather_combine", "spmv_boundary", "ssy_p1", "ssy_p2", "usymqr_p3",
+                    "usymlq_p3")
 
     def profile_kernels(self):
         """{family: (launches, total_ms)} of the HIP-event brackets recorded since the last call (option profile_spmv = 1):
@@ -1744,6 +1762,37 @@ class UsymqrWorkspace(_Workspace):
         return DeviceVector(self.ctx, self._len(name), ptr=p, owner=self) if p else None
 
 
+class UsymlqWorkspace(_Workspace):
+    """UsymlqWorkspace(m, n, Sm, Sn) (src/krylov_workspaces.jl): uₖ₋₁, uₖ, p, x, d̅ of n entries and vₖ₋₁, vₖ, q of m; Δx ("dx") stays
+    empty until a warm start.  The fused loops rotate the roles of (vₖ₋₁, vₖ) and (uₖ₋₁, uₖ), and `vector(name)` follows the role
+    (khip_usymlq_vector): after k iterations a name holds what the reference's variable of that name holds ("dbar" = d̅ₖ).  A
+    rectangular system (m ≠ n) runs the primitive sequence whatever `fused` says: `last_path` reports 0."""
+    _prefix = "usymlq"
+    VECTORS = ("u_prev", "u", "p", "x", "dbar", "v_prev", "v", "q")
+    ROW_SIDE = ("v_prev", "v", "q")                                             # m entries; every other vector has n
+
+    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
+        self.ctx, self.m, self.n = ctx, m, n
+        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
+        self._h = C.c_void_p()
+        if self.adopted:
+            t0 = time.perf_counter()
+            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(self._len(k)) for k in self.VECTORS}   # dx stays empty
+            self._alloc_s = time.perf_counter() - t0
+            _ck(lib().khip_usymlq_workspace_adopt(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
+        else:
+            _ck(lib().khip_usymlq_workspace_create(ctx._h, m, n, C.byref(self._h)))
+
+    def _len(self, name: str) -> int:
+        return self.m if name in self.ROW_SIDE else self.n
+
+    def vector(self, name: str):
+        if name == "x":
+            return self.x
+        p = lib().khip_usymlq_vector(self._h, name.encode())
+        return DeviceVector(self.ctx, self._len(name), ptr=p, owner=self) if p else None
+
+
 class CgsWorkspace(_BiLanczosWorkspace):
     """CgsWorkspace(m, n, S) (src/krylov_workspaces.jl): x, r, u, p, q, ts; Δx, yz, vw stay empty until needed.  cgs! rotates no
     roles: every name keeps its buffer."""
@@ -2097,6 +2146,30 @@ def usymqr_(ws: UsymqrWorkspace, A, b: DeviceVector, c: DeviceVector | None = No
     return _finish(ws, rc)
 
 
+def usymlq_(ws: UsymlqWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, transfer_to_usymcg=True, **kw):
+    """usymlq!(workspace, A, b, c; transfer_to_usymcg, atol, rtol, itmax, timemax, verbose, history, callback, iostream)
+    (src/usymlq.jl:124-366) for A of m rows and n columns, b of m entries and c of n.  At: the adjoint of A (default: A.transpose(),
+    built once and kept on A); a matrix-free A is callable(x[n], y[m]) and brings At = callable(x[m], y[n]).  Returns the workspace."""
+    keep = []
+    if c is None:
+        raise KhipError(-1, "usymlq: c (the starting vector of the second Krylov space) is required")
+    if len(b) != ws.m or len(c) != ws.n:
+        raise KhipError(-1, "Inconsistent problem size")
+    if At is None:
+        At = _adjoint_of(A, solver="usymlq")
+    opts = _make_options(keep=keep, ws=ws, **kw)
+    prm = lib().khip_usymlq_default_params()
+    prm.transfer_to_usymcg = int(bool(transfer_to_usymcg))
+
+    def operator(op, nin, nout):
+        if op is None or isinstance(op, CsrMatrix):
+            return _make_operator(ws.ctx, op, nin, keep)
+        return _make_operator_mn(ws.ctx, op, nin, nout, keep)
+    rc = lib().khip_usymlq_solve(ws._h, operator(A, ws.n, ws.m), operator(At, ws.m, ws.n), _p(b), _p(c), C.byref(opts),
+                                 C.byref(prm))
+    return _finish(ws, rc)
+
+
 def bilqr_(ws: BilqrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, transfer_to_bicg=True, **kw):
     """bilqr!(workspace, A, b, c; transfer_to_bicg, atol, rtol, itmax, timemax, verbose, history, callback, iostream)
     (src/bilqr.jl:116-484): x of A x = b by BiLQ and y of A' y = c by QMR from one two-sided Lanczos process.  At: the adjoint of A
@@ -2156,6 +2229,8 @@ FORWARDED_DEFAULTS = {
                   callback=default_callback, iostream=None),
     "usymqr": dict(atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0, timemax=math.inf, verbose=0, history=False,
                    callback=default_callback, iostream=None),
+    "usymlq": dict(transfer_to_usymcg=True, atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0, timemax=math.inf, verbose=0, history=False,
+                   callback=default_callback, iostream=None),
 }
 WORKSPACE_KWARGS = {"gmres": dict(memory=20), "block_gmres": dict(memory=5)}      # kwargs_workspace_gmres, _block_gmres
 # kwargs_workspace_minres (src/minres.jl:159): kept apart from WORKSPACE_KWARGS, whose contents tests/test_abi.py pins
@@ -2182,8 +2257,9 @@ def krylov_workspace(method: str, *args, ctx: Context | None = None, **kw):
     cls = {"cg": CgWorkspace, "gmres": GmresWorkspace, "bicgstab": BicgstabWorkspace, "block_gmres": BlockGmresWorkspace,
            "minres": MinresWorkspace, "cg_lanczos_shift": CgLanczosShiftWorkspace, "bilq": BilqWorkspace,
            "qmr": QmrWorkspace, "bilqr": BilqrWorkspace, "cgs": CgsWorkspace,
-           "symmlq": SymmlqWorkspace, "minres_qlp": MinresQlpWorkspace, "usymqr": UsymqrWorkspace}[method]
-    if method == "usymqr" and len(args) == 3:                                   # (A, b, c): m = length(b), n = length(c)
+           "symmlq": SymmlqWorkspace, "minres_qlp": MinresQlpWorkspace, "usymqr": UsymqrWorkspace,
+           "usymlq": UsymlqWorkspace}[method]
+    if method in ("usymqr", "usymlq") and len(args) == 3:                                   # (A, b, c): m = length(b), n = length(c)
         A, b, c = args
         return cls(b.ctx, len(b), len(c), **kw)
     if method == "cg_lanczos_shift":                                            # (A, b, nshifts) / (m, n, nshifts)
@@ -2248,9 +2324,9 @@ def krylov_solve(method: str, A, b, x0=None, ctx: Context | None = None, **kw):
         ctx = ctx or A.ctx
         ws = krylov_workspace(method, A, B, ctx=ctx, **wkw)
         b = ctx.array(np.asfortranarray(B).ravel(order="F"))
-    elif method == "usymqr":                              # krylov_solve(Val(:usymqr), A, b, c[, x0]; kwargs...): c travels as a keyword here
+    elif method in ("usymqr", "usymlq"):                  # krylov_solve(Val(:usymqr), A, b, c[, x0]; kwargs...): c travels as a keyword here
         if kw.get("c") is None:
-            raise KhipError(-1, "usymqr: c (the starting vector of the second Krylov space) is required")
+            raise KhipError(-1, f"{method}: c (the starting vector of the second Krylov space) is required")
         ws = krylov_workspace(method, A, b, kw["c"], **wkw)
     else:
         ws = krylov_workspace(method, A, b, **wkw)
@@ -2295,6 +2371,11 @@ def qmr(A, b: DeviceVector, x0=None, **kw):
 def usymqr(A, b: DeviceVector, c: DeviceVector, x0=None, **kw):
     """Out-of-place usymqr(A, b, c[, x0]; kwargs...) -> (x, stats, workspace) (src/usymqr.jl:16-23); A' is taken once and kept on A."""
     return krylov_solve("usymqr", A, b, x0, c=c, **kw)
+
+
+def usymlq(A, b: DeviceVector, c: DeviceVector, x0=None, **kw):
+    """Out-of-place usymlq(A, b, c[, x0]; kwargs...) -> (x, stats, workspace) (src/usymlq.jl:16-24); A' is taken once and kept on A."""
+    return krylov_solve("usymlq", A, b, x0, c=c, **kw)
 
 
 def cgs(A, b: DeviceVector, x0=None, **kw):
@@ -2781,6 +2862,7 @@ def block_gmres(A, B, X0=None, ctx=None, **kw):
 _INPLACE.update({CgWorkspace: ("cg", cg_), GmresWorkspace: ("gmres", gmres_), BicgstabWorkspace: ("bicgstab", bicgstab_),
                  BlockGmresWorkspace: ("block_gmres", block_gmres_), MinresWorkspace: ("minres", minres_), BilqWorkspace: ("bilq", bilq_),
                  QmrWorkspace: ("qmr", qmr_), CgsWorkspace: ("cgs", cgs_), UsymqrWorkspace: ("usymqr", usymqr_),
+                 UsymlqWorkspace: ("usymlq", usymlq_),
                  SymmlqWorkspace: ("symmlq", symmlq_),
                  MinresQlpWorkspace: ("minres_qlp", minres_qlp_),
                  BilqrWorkspace: ("bilqr", bilqr_),

@@ -507,7 +507,8 @@ enum ProfTag { kProfSpmv = 0, kProfSpmm = 1, kProfPanelTn = 2, kProfPanelNnTn = 
                kProfDotGather = 9,      // 16-byte all-gather of a dot's (hi, lo) partials + combine kernel
                kProfSpmvBoundary = 10,  // the boundary rows' launch of a row-partitioned product (after the halo has arrived)
                kProfSsyP1 = 11, kProfSsyP2 = 12, kProfUsymqrP3 = 13,   // the fused passes of usymqr! (ssy.hpp, usymqr.cpp), without their finish kernels
-               kProfTags = 14 };
+               kProfUsymlqP3 = 14,      // P3 of usymlq! (usymlq.cpp); its P1 and P2 are the two Ssy brackets
+               kProfTags = 15 };
 struct ProfScope {
   khip_ctx *ctx;
   hipEvent_t stop = nullptr;

@@ -19,7 +19,7 @@ enum Epilogue { EPI_NONE = 0, EPI_CG_STEP1 = 1, EPI_CG_STEP2 = 2, EPI_BICG_A = 3
                EPI_BILQ_A = 12, EPI_BILQ_B = 13, EPI_BILQ_C = 14, EPI_QMR_A = 15, EPI_QMR_B = 16, EPI_QMR_C = 17,
                EPI_BILQR_A = 18, EPI_BILQR_B = 19, EPI_BILQR_C = 20, EPI_CGS_A = 21, EPI_CGS_B = 22,
                EPI_SYMMLQ_A = 23, EPI_SYMMLQ_B = 24, EPI_MINRES_QLP_X = 25, EPI_MINRES_QLP_A = 26, EPI_MINRES_QLP_B = 27,
-               EPI_USYMQR_A = 28, EPI_USYMQR_B = 29 };
+               EPI_USYMQR_A = 28, EPI_USYMQR_B = 29, EPI_USYMLQ_A = 30, EPI_USYMLQ_B = 31 };
 
 struct CgDevState {
   double gamma;        // r.z of the current iterate              (src/cg.jl:162, 257)
@@ -1042,6 +1042,92 @@ __host__ __device__ inline bool usymqr_step_b(UsymqrDevState &s, double qq, doub
   return s.solved || s.inconsistent;
 }
 
+// usymlq! (src/usymlq.jl:124-366), real Float64: the same process, the LQ factorisation of Tₖ, the residual norms of the LQ and the
+// USYMCG points and the stopping tests.  As for usymqr!: the same two steps run on the host (loops 0 and 1) and as the epilogues of
+// the two reductions of an iteration (device-resident loop), so loops 1 and 2 produce the same bits.
+struct UsymlqDevState : SsyCoef {
+  // coefficients the vector kernels read (γₖ, βₖ, αₖ: SsyCoef)
+  double beta_next, gamma_next;  // βₖ₊₁, γₖ₊₁: the divisors of P3               (src/usymlq.jl:221-222, :297-302)
+  double zc, zs, neg_c, sn;      // ζₖ₋₁cₖ, ζₖ₋₁sₖ, -cₖ, sₖ: the x and d̅ updates (:285-290)
+  // constants of the solve
+  double eps_tol;                // ε = atol + rtol ‖r₀‖                          (:175)
+  // recurrences
+  double bNorm;                  // ‖r₀‖: rNorm_lq of iteration 1                 (:307)
+  double cs, cs_prev, sn_prev;   // cₖ, cₖ₋₁, sₖ₋₁
+  double delta, lambda, epsilon; // δₖ₋₁, λₖ₋₁, ϵₖ₋₂
+  double dbar, dbar_prev;        // δbarₖ, δbarₖ₋₁
+  double eta, eta_prev;          // ηₖ, ηₖ₋₁
+  double zeta_m2, zeta_m1, zbar; // ζₖ₋₂, ζₖ₋₁, ζbarₖ
+  double rNorm_lq, rNorm_cg;
+  long long stop_seq, iter, hist_base, hist_cap;
+  double *hist_r;                // device history window (null: no history)
+  int transfer, solved_lq, solved_cg;   // transfer: transfer_to_usymcg
+};
+
+// after αₖ = ⟨vₖ, q⟩ (:216)
+__host__ __device__ inline void usymlq_step_a(UsymlqDevState &s, double vq) { s.alpha = vq; }
+
+// after ‖q‖² and ‖p‖²: βₖ₊₁, γₖ₊₁, the LQ update (:234-254), ζ and η (:258-274), rNorm_lq (:306-312) and its history entry, the
+// USYMCG residual (:317-321), the shifts (:324-329) and the two tests (:333-334); k = iter.  True when the loop stops (tired /
+// overtimed / the callback are the driver's).  P3 of this iteration still runs: the reference updates x, d̅, vₖ₊₁ and uₖ₊₁ before
+// it tests.
+__host__ __device__ inline bool usymlq_step_b(UsymlqDevState &s, double qq, double pp, long long k) {
+  s.beta_next = sqrt(qq);
+  s.gamma_next = sqrt(pp);
+  if (k == 1) {
+    s.dbar = s.alpha;
+  } else if (k == 2) {
+    sym_givens(s.dbar_prev, s.gamma, s.cs, s.sn, s.delta);
+    s.lambda = s.cs * s.beta + s.sn * s.alpha;
+    s.dbar = s.sn * s.beta - s.cs * s.alpha;
+  } else {
+    sym_givens(s.dbar_prev, s.gamma, s.cs, s.sn, s.delta);
+    s.epsilon = s.sn_prev * s.beta;
+    s.lambda = -s.cs_prev * s.cs * s.beta + s.sn * s.alpha;
+    s.dbar = -s.cs_prev * s.sn * s.beta - s.cs * s.alpha;
+  }
+  if (k == 1) s.eta = s.beta;
+  if (k == 2) {
+    s.zeta_m1 = s.eta_prev / s.delta;
+    s.eta = -s.lambda * s.zeta_m1;
+  }
+  if (k >= 3) {
+    s.zeta_m2 = s.zeta_m1;
+    s.zeta_m1 = s.eta_prev / s.delta;
+    s.eta = -s.epsilon * s.zeta_m2 - s.lambda * s.zeta_m1;
+  }
+  s.zc = s.zeta_m1 * s.cs;
+  s.zs = s.zeta_m1 * s.sn;
+  s.neg_c = -s.cs;
+  if (k == 1) {
+    s.rNorm_lq = s.bNorm;
+  } else {
+    const double mu = s.beta * (s.sn_prev * s.zeta_m2 - s.cs_prev * s.cs * s.zeta_m1) + s.alpha * s.sn * s.zeta_m1;
+    const double omega = s.beta_next * s.sn * s.zeta_m1;
+    s.rNorm_lq = sqrt(mu * mu + omega * omega);
+  }
+  if (s.hist_r) {
+    const long long idx = k - 1 - s.hist_base;
+    if (idx >= 0 && idx < s.hist_cap) s.hist_r[idx] = s.rNorm_lq;
+  }
+  const bool cg_point = s.transfer && (fabs(s.dbar) > 2.220446049250313e-16);
+  if (cg_point) {
+    s.zbar = s.eta / s.dbar;
+    const double rho = s.beta_next * (s.sn * s.zeta_m1 - s.cs * s.zbar);
+    s.rNorm_cg = fabs(rho);
+  }
+  s.sn_prev = s.sn;
+  s.cs_prev = s.cs;
+  s.eta_prev = s.eta;
+  s.gamma = s.gamma_next;        // P3 divides by gamma_next and beta_next; the next P1 reads gamma and beta
+  s.beta = s.beta_next;
+  s.dbar_prev = s.dbar;
+  s.solved_lq = (s.rNorm_lq <= s.eps_tol) ? 1 : 0;
+  s.solved_cg = (cg_point && s.rNorm_cg <= s.eps_tol) ? 1 : 0;
+  s.iter = k;
+  return s.solved_lq || s.solved_cg;
+}
+
 __device__ __forceinline__ bool seq_skip(const long long *stop_seq, long long seq) {
   return stop_seq != nullptr && seq >= *stop_seq;
 }
@@ -1199,6 +1285,11 @@ __device__ inline void solver_epilogue(int epi, void *state, const double *v, lo
   } else if (epi == EPI_USYMQR_B) {                // v = (q.q, p.p)             :224-339
     UsymqrDevState *st = static_cast<UsymqrDevState *>(state);
     if (usymqr_step_b(*st, v[0], v[1], st->iter + 1)) st->stop_seq = seq + 2;   // P3 of this iteration (seq + 1) still runs (:276-317)
+  } else if (epi == EPI_USYMLQ_A) {                // v[0] = v.q                 src/usymlq.jl:216
+    usymlq_step_a(*static_cast<UsymlqDevState *>(state), v[0]);
+  } else if (epi == EPI_USYMLQ_B) {                // v = (q.q, p.p)             :221-334
+    UsymlqDevState *st = static_cast<UsymlqDevState *>(state);
+    if (usymlq_step_b(*st, v[0], v[1], st->iter + 1)) st->stop_seq = seq + 2;   // P3 of this iteration (seq + 1) still runs (:279-302)
   }
 }
 

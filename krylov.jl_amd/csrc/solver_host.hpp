@@ -248,6 +248,7 @@ void set_history(UsymqrDevState &s, double *w) {
   s.hist_r = w;
   s.hist_ar = w ? w + kHistWindowMax : nullptr;
 }
+void set_history(UsymlqDevState &s, double *w) { s.hist_r = w; }
 void set_history(BilqrDevState &s, double *w) {
   s.hist_p = w;
   s.hist_d = w ? w + kHistWindowMax : nullptr;
