@@ -215,7 +215,7 @@ int khip_profile_spmv(khip_ctx *ctx, int64_t *launches, double *total_ms);
  * (scale + Gram), 7 = halo pack kernel, 8 = halo transfer (grouped ncclSend / ncclRecv or the all-gather of x, bracketed on the
  * stream it runs on), 9 = a dot's 16-byte all-gather + combine kernel, 10 = the boundary rows' SpMV launch of a row-partitioned
  * product (tag 0 then is the interior launch), 11 / 12 / 13 = the fused passes P1, P2 and P3 of usymqr! (the pass's own kernel, without
- * the reduction's finish kernel), 14 = P3 of usymlq! (its P1 and P2 are 11 and 12); at most 15 families.  Synchronises the context's streams and resets every counter. */
+ * the reduction's finish kernel), 14 = P3 of usymlq! (its P1 and P2 are 11 and 12), 15 = P3 of trilqr! (likewise); at most 16 families.  Synchronises the context's streams and resets every counter. */
 int khip_profile_kernels(khip_ctx *ctx, int ntags, int64_t *launches, double *total_ms);
 
 /* ------------------------------------------------ BLAS-1 shim ---------------- */
@@ -740,6 +740,53 @@ int khip_usymlq_last_path(khip_usymlq_workspace *ws);
 /* named work vectors: "u_prev", "u", "p", "x", "dbar", "v_prev", "v", "q", "dx" (NULL while not allocated) */
 double           *khip_usymlq_vector(khip_usymlq_workspace *ws, const char *name);
 size_t            khip_usymlq_workspace_bytes(khip_usymlq_workspace *ws);   /* 5n + 3m doubles without warm start */
+
+/* ---- trilqr! (src/trilqr.jl:115-460), real Float64: the adjoint pair A x = b and Aᴴ t = c, A of m rows and n columns, from ONE
+ * orthogonal tridiagonalisation: x by USYMLQ (with transfer_to_usymcg the USYMCG point xᶜ is tested as well and returned when it is the
+ * one that meets the tolerance), t by USYMQR.  Two products per iteration where usymlq! followed by usymqr! takes four.  There is no
+ * M or N.  TrilqrWorkspace (src/krylov_workspaces.jl): uₖ₋₁, uₖ, p, d̅, x (n doubles each), vₖ₋₁, vₖ, q, t, wₖ₋₃, wₖ₋₂ (m doubles each)
+ * ("u_prev", "u", "p", "dbar", "x", "v_prev", "v", "q", "y", "w_prev3", "w_prev2"); Δx ("dx", n doubles) and Δy ("dy", m doubles)
+ * stay empty until a warm start.  The adjoint travels as its own operator.  options.radius, linesearch, restart,
+ * reorthogonalization and variant are ignored.  A side that is solved is frozen; the solve ends when both are.  There is no early
+ * return for b = 0 or c = 0, as in the reference: that side starts solved and the process goes on from 0 / 0.  The fused loops rotate
+ * the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and (wₖ₋₃, wₖ₋₂) instead of copying or swapping, and khip_trilqr_vector returns a name's pointer
+ * by its current role: after k iterations every name holds what the reference's variable of that name holds, in whichever buffer. */
+typedef struct khip_trilqr_workspace khip_trilqr_workspace;
+typedef struct khip_trilqr_params {
+  int transfer_to_usymcg;      /* also test and return the USYMCG point xᶜ; default 1      (src/trilqr.jl:99) */
+} khip_trilqr_params;
+khip_trilqr_params khip_trilqr_default_params(void);   /* transfer_to_usymcg = 1 */
+int khip_trilqr_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_trilqr_workspace **out);   /* m != n is allowed */
+/* TrilqrWorkspace on the caller's eleven vectors, in the reference's order; every pointer must be distinct.  adopt_vector names:
+ * "dx" and "dy" (Δx, Δy: warm_start! fills them on the caller's side and hands them over, then khip_trilqr_warm_start(ws, dx, dy)
+ * only sets the flag) */
+int khip_trilqr_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *u_prev, double *u, double *p, double *dbar, double *x,
+                                double *v_prev, double *v, double *q, double *y, double *w_prev3, double *w_prev2,
+                                khip_trilqr_workspace **out);
+int khip_trilqr_workspace_adopt_vector(khip_trilqr_workspace *ws, const char *name, double *ptr);
+int khip_trilqr_workspace_destroy(khip_trilqr_workspace *ws);
+int khip_trilqr_warm_start(khip_trilqr_workspace *ws, const double *x0, const double *y0);   /* both are required: n and m doubles */
+/* trilqr!(ws, A, b, c; transfer_to_usymcg, atol, rtol, itmax, timemax, verbose, history, callback).  At = A' (n rows, m columns) and
+ * c (n doubles) are required (NULL: KHIP_ERR_INVALID); itmax = 0 means m + n of the global system; params = NULL means the defaults.
+ * Loops (khip_trilqr_last_path): 2 = device-resident (m = n, A and At CSR handles, no callback, verbose = 0), 1 = host-driven on the
+ * same kernels (same bits as 2), 0 = one launch per primitive (options.fused = 0).  A rectangular system (m != n) runs loop 0
+ * whatever options.fused says, and last_path reports 0; a row-partitioned rectangular handle is KHIP_ERR_UNSUPPORTED. */
+int khip_trilqr_solve(khip_trilqr_workspace *ws, const khip_operator *A, const khip_operator *At, const double *b, const double *c,
+                      const khip_options *opts, const khip_trilqr_params *params);
+double           *khip_trilqr_solution_x(khip_trilqr_workspace *ws);
+double           *khip_trilqr_solution_y(khip_trilqr_workspace *ws);      /* t, m doubles */
+/* AdjointStats does not fit khip_stats: there solved = solved_primal && solved_dual, residuals = the primal history and status = the
+ * first bytes of the full status, cut at a UTF-8 character boundary (four of the reference's strings are longer than status[96]).
+ * stats.inconsistent carries the dual side's `inconsistent` flag (‖A sₖ₋₁‖ <= ξ), which the reference counts into solved_dual and
+ * does not report: an addition to its AdjointStats.  The status can stay "unknown" when the dual side ends by that flag alone. */
+const khip_stats *khip_trilqr_stats(khip_trilqr_workspace *ws);
+/* the whole AdjointStats; the arrays and the string belong to the workspace until its next solve; any out pointer may be NULL */
+int khip_trilqr_adjoint_stats(khip_trilqr_workspace *ws, int *solved_primal, int *solved_dual, const double **residuals_primal,
+                              int *nprimal, const double **residuals_dual, int *ndual, const char **status);
+int khip_trilqr_last_path(khip_trilqr_workspace *ws);
+/* named work vectors: "u_prev", "u", "p", "dbar", "x", "v_prev", "v", "q", "y", "w_prev3", "w_prev2", "dx", "dy" (NULL while not allocated) */
+double           *khip_trilqr_vector(khip_trilqr_workspace *ws, const char *name);
+size_t            khip_trilqr_workspace_bytes(khip_trilqr_workspace *ws);   /* 5n + 6m doubles without warm start */
 
 /* ---- cgs! (src/cgs.jl:126-281), real Float64: square nonsymmetric systems by the conjugate gradient squared recurrence; transpose-
  * free (no A'), two products with A per iteration.  CgsWorkspace (src/krylov_workspaces.jl): x, r, u, p, q, ts; Δx, yz and vw ("dx",

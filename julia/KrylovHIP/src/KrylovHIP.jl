@@ -755,6 +755,80 @@ function Krylov.usymlq!(ws::UsymlqWs, A::HIPCsr, b::HIPVector, c::HIPVector; tra
   return ws
 end
 
+# ------------------------------------------------------------------------------------------------ trilqr!  (src/trilqr.jl:115-460)
+struct TrilqrParams                # khip_trilqr_params: transfer_to_usymcg
+  transfer_to_usymcg::Cint
+end
+const TrilqrWs = TrilqrWorkspace{Float64,Float64,HIPVector,HIPVector}
+function trilqr_handle(ws::TrilqrWs)
+  get!(HANDLES, ws) do
+    r = Ref{Ptr{Cvoid}}()
+    ck(ccall((:khip_trilqr_workspace_adopt, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                                                        Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                                                        Ptr{Cdouble}, Ref{Ptr{Cvoid}}),
+             CTX[].h, ws.m, ws.n, ws.uₖ₋₁.ptr, ws.uₖ.ptr, ws.p.ptr, ws.d̅.ptr, ws.x.ptr, ws.vₖ₋₁.ptr, ws.vₖ.ptr, ws.q.ptr, ws.y.ptr, ws.wₖ₋₃.ptr, ws.wₖ₋₂.ptr, r))
+    h = r[]
+    finalizer(_ -> ccall((:khip_trilqr_workspace_destroy, lib), Cint, (Ptr{Cvoid},), h), ws)
+    h
+  end
+end
+trilqr_adopt(h, name, v::HIPVector) = ck(ccall((:khip_trilqr_workspace_adopt_vector, lib), Cint, (Ptr{Cvoid}, Cstring, Ptr{Cdouble}), h, name, dptr(v)))
+# AdjointStats from khip_trilqr_adjoint_stats: both histories, both flags and the FULL status (khip_stats.status[96] cannot hold four
+# of the reference's strings); niter and timer from khip_stats.  (khip_stats.inconsistent, the dual side's flag, has no field there.)
+function fill_trilqr_stats!(stats::Krylov.AdjointStats{Float64}, h::Ptr{Cvoid}, sp::Ptr{Stats}, history::Bool)
+  st = unsafe_load(sp)
+  sprim, sdual, np, nd = Ref{Cint}(0), Ref{Cint}(0), Ref{Cint}(0), Ref{Cint}(0)
+  rp, rd, status = Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL)
+  ck(ccall((:khip_trilqr_adjoint_stats, lib), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cint}, Ref{Ptr{Cvoid}}, Ref{Cint}, Ref{Ptr{Cvoid}},
+                                                     Ref{Cint}, Ref{Ptr{Cvoid}}), h, sprim, sdual, rp, np, rd, nd, status))
+  Krylov.reset!(stats)
+  history && np[] > 0 && append!(stats.residuals_primal, unsafe_wrap(Array, Ptr{Float64}(rp[]), Int(np[])))
+  history && nd[] > 0 && append!(stats.residuals_dual, unsafe_wrap(Array, Ptr{Float64}(rd[]), Int(nd[])))
+  stats.niter = st.niter;  stats.solved_primal = sprim[] != 0;  stats.solved_dual = sdual[] != 0
+  stats.timer = st.timer;  stats.status = unsafe_string(Ptr{UInt8}(status[]))
+  return st
+end
+# a user's callback reads both histories: they are brought over before it runs (the shared trampoline knows stats.residuals only)
+trilqr_callback(cb, h, sp, history) = cb === nothing ? nothing : (w -> (fill_trilqr_stats!(w.stats, h, sp, history); cb(w)))
+
+# A has m rows and n columns; b has m entries, c has n.  The adjoint is `A'`, built once per matrix and cached in `A.adj`.  trilqr!
+# has no M or N.  A rectangular system runs the library's primitive sequence (LAST_PATH[] == 0) whatever `fused` says.  After the
+# solve only ws.x, ws.y and ws.stats are defined: the library rotates the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and (wₖ₋₃, wₖ₋₂) among the
+# adopted vectors.
+function Krylov.trilqr!(ws::TrilqrWs, A::HIPCsr, b::HIPVector, c::HIPVector; transfer_to_usymcg::Bool = true,
+                        atol::Float64 = √eps(Float64), rtol::Float64 = √eps(Float64), itmax::Int = 0, timemax::Float64 = Inf,
+                        verbose::Int = 0, history::Bool = false, callback = nothing, iostream::IO = Krylov.kstdout, fused::Int = 2)
+  if !native_log(verbose, iostream)
+    GENERIC_SOLVES[] += 1
+    return invoke(Krylov.trilqr!, Tuple{TrilqrWs,Any,AbstractVector{Float64},AbstractVector{Float64}}, ws, A, b, c; transfer_to_usymcg, atol,
+                  rtol, itmax, timemax, verbose, history, callback = callback === nothing ? (w -> false) : callback, iostream)
+  end
+  m, n = size(A)                                                                            # :121-124
+  (m == ws.m && n == ws.n) || error("(workspace.m, workspace.n) = ($(ws.m), $(ws.n)) is inconsistent with size(A) = ($m, $n)")
+  length(b) == m || error("Inconsistent problem size")
+  length(c) == n || error("Inconsistent problem size")
+  At = A'
+  h = trilqr_handle(ws)
+  for (name, v) in (("dx", ws.Δx), ("dy", ws.Δy))
+    trilqr_adopt(h, name, v)
+  end
+  ws.warm_start && ck(ccall((:khip_trilqr_warm_start, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), h, ws.Δx.ptr, ws.Δy.ptr))
+  sp = ccall((:khip_trilqr_stats, lib), Ptr{Stats}, (Ptr{Cvoid},), h)
+  cbf, cbd, box = callback_args(trilqr_callback(user_callback(callback), h, sp, history), ws, sp, false)
+  opts = Ref(Options(; atol, rtol, itmax, timemax, history, fused, verbose, log_fd = logfd(iostream), callback = cbf, callback_data = cbd))
+  prm = Ref(TrilqrParams(Cint(transfer_to_usymcg)))
+  opA = Ref(Operator(A));  opAt = Ref(Operator(At))
+  rc = GC.@preserve ws A At b c opts prm opA opAt box ccall((:khip_trilqr_solve, lib), Cint,
+         (Ptr{Cvoid}, Ref{Operator}, Ref{Operator}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Options}, Ptr{Cvoid}),
+         h, opA, opAt, b.ptr, c.ptr, opts, prm)
+  st = fill_trilqr_stats!(ws.stats, h, sp, history)
+  NATIVE_SOLVES[] += 1;  LAST_PATH[] = ccall((:khip_trilqr_last_path, lib), Cint, (Ptr{Cvoid},), h)
+  ws.warm_start = false
+  finish_callback(box)
+  rc == 0 || failed(st)
+  return ws
+end
+
 # ------------------------------------------------------------------------------------------------ cgs!  (src/cgs.jl:126-281)
 const CgsWs = CgsWorkspace{Float64,Float64,HIPVector}
 function cgs_handle(ws::CgsWs)

@@ -271,3 +271,4 @@ include("symmlq.jl")                                                 # symmlq! a
 include("minres_qlp.jl")                                             # minres_qlp! against the generic method, singular and inconsistent systems
 include("usymqr.jl")                                                 # usymqr! against the generic method, rectangular and inconsistent systems
 include("usymlq.jl")                                                 # usymlq! against the generic method, both points, the breakdown system
+include("trilqr.jl")                                                 # trilqr! against the generic method: both sides, the rectangular adjoint system

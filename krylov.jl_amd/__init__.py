@@ -87,6 +87,10 @@ class CUsymlqParams(C.Structure):
     _fields_ = [("transfer_to_usymcg", C.c_int)]
 
 
+class CTrilqrParams(C.Structure):
+    _fields_ = [("transfer_to_usymcg", C.c_int)]
+
+
 class CStats(C.Structure):
     _fields_ = [("niter", C.c_int), ("solved", C.c_int), ("inconsistent", C.c_int), ("indefinite", C.c_int),
                 ("npcCount", C.c_int), ("timer", C.c_double), ("status", C.c_char * 96),
@@ -319,6 +323,22 @@ SIGNATURES = {
     "khip_usymlq_last_path": (_int, [_vp]),
     "khip_usymlq_vector": (_vp, [_vp, C.c_char_p]),
     "khip_usymlq_workspace_bytes": (_sz, [_vp]),
+    "khip_trilqr_default_params": (CTrilqrParams, []),
+    "khip_trilqr_workspace_create": (_int, [_vp, _i64, _i64, c_void_pp]),
+    "khip_trilqr_workspace_adopt": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_void_pp]),
+    "khip_trilqr_workspace_adopt_vector": (_int, [_vp, C.c_char_p, _vp]),
+    "khip_trilqr_workspace_destroy": (_int, [_vp]),
+    "khip_trilqr_warm_start": (_int, [_vp, _vp, _vp]),
+    "khip_trilqr_solve": (_int, [_vp, C.POINTER(COperator), C.POINTER(COperator), _vp, _vp, C.POINTER(COptions),
+                                 C.POINTER(CTrilqrParams)]),
+    "khip_trilqr_solution_x": (_vp, [_vp]),
+    "khip_trilqr_solution_y": (_vp, [_vp]),
+    "khip_trilqr_stats": (C.POINTER(CStats), [_vp]),
+    "khip_trilqr_adjoint_stats": (_int, [_vp, C.POINTER(_int), C.POINTER(_int), C.POINTER(c_double_p), C.POINTER(_int),
+                                         C.POINTER(c_double_p), C.POINTER(_int), C.POINTER(C.c_char_p)]),
+    "khip_trilqr_last_path": (_int, [_vp]),
+    "khip_trilqr_vector": (_vp, [_vp, C.c_char_p]),
+    "khip_trilqr_workspace_bytes": (_sz, [_vp]),
     "khip_cgs_workspace_create": (_int, [_vp, _i64, _i64, c_void_pp]),
     "khip_cgs_workspace_adopt": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, c_void_pp]),
     "khip_cgs_workspace_adopt_vector": (_int, [_vp, C.c_char_p, _vp]),
@@ -544,14 +564,17 @@ class Context:
     PROFILE_TAGS = ("spmv", "spmm", "panel_gemm_tn", "panel_nn_tn", "panel_multi_nn", "panel_gemm_nn", "panel_qr_scale_gram",
                     "halo_pack", "halo_transfer", "dot_allgather_combine", "spmv_boundary", "ssy_p1", "ssy_p2", "usymqr_p3",
                     "usymlq_p3")
+    # the families added since: PROFILE_TAGS keeps the length its tests pin (tests/test_usymlq_host.py), profile_kernels reports
+    # PROFILE_FAMILIES
+    PROFILE_FAMILIES = PROFILE_TAGS + ("trilqr_p3",)
 
     def profile_kernels(self):
         """{family: (launches, total_ms)} of the HIP-event brackets recorded since the last call (option profile_spmv = 1):
-        khip_profile_kernels -- SpMV, SpMM, and the panel kernels of block_gmres!."""
-        k = len(self.PROFILE_TAGS)
+        khip_profile_kernels -- SpMV, SpMM, the panel kernels of block_gmres! and the fused passes of usymqr!, usymlq! and trilqr!."""
+        k = len(self.PROFILE_FAMILIES)
         n, ms = (C.c_int64 * k)(), (C.c_double * k)()
         _ck(lib().khip_profile_kernels(self._h, k, n, ms))
-        return {t: (int(n[i]), float(ms[i])) for i, t in enumerate(self.PROFILE_TAGS)}
+        return {t: (int(n[i]), float(ms[i])) for i, t in enumerate(self.PROFILE_FAMILIES)}
 
     # --- multi-GPU (one process per GPU) ---
     @staticmethod
@@ -1198,6 +1221,7 @@ class AdjointStats:
         self.solved_primal = bool(solved_primal)
         self.solved_dual = bool(solved_dual)
         self.solved = bool(st.solved)
+        self.inconsistent = bool(st.inconsistent)         # trilqr!: the dual side's flag (always False for bilqr!)
         self.residuals_primal = residuals_primal
         self.residuals_dual = residuals_dual
         self.residuals = residuals_primal
@@ -1793,6 +1817,83 @@ class UsymlqWorkspace(_Workspace):
         return DeviceVector(self.ctx, self._len(name), ptr=p, owner=self) if p else None
 
 
+class TrilqrWorkspace(_Workspace):
+    """TrilqrWorkspace(m, n, Sm, Sn) (src/krylov_workspaces.jl): uₖ₋₁, uₖ, p, d̅, x of n entries and vₖ₋₁, vₖ, q, t ("y"), wₖ₋₃, wₖ₋₂ of m;
+    Δx ("dx", n) and Δy ("dy", m) stay empty until a warm start.  stats is an AdjointStats, with `inconsistent` (the dual side's flag)
+    beside the reference's fields.  The fused loops rotate the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and (wₖ₋₃, wₖ₋₂), and `vector(name)`
+    follows the role (khip_trilqr_vector): after k iterations a name holds what the reference's variable of that name holds.  A
+    rectangular system (m ≠ n) runs the primitive sequence whatever `fused` says: `last_path` reports 0."""
+    _prefix = "trilqr"
+    VECTORS = ("u_prev", "u", "p", "dbar", "x", "v_prev", "v", "q", "y", "w_prev3", "w_prev2")
+    ROW_SIDE = ("v_prev", "v", "q", "y", "w_prev3", "w_prev2", "dy")            # m entries; every other vector has n
+    SOLUTIONS = ("x", "y")
+
+    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
+        self.ctx, self.m, self.n = ctx, m, n
+        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
+        self._h = C.c_void_p()
+        if self.adopted:
+            t0 = time.perf_counter()
+            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(self._len(k)) for k in self.VECTORS}   # dx, dy stay empty
+            self._alloc_s = time.perf_counter() - t0
+            _ck(lib().khip_trilqr_workspace_adopt(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
+        else:
+            _ck(lib().khip_trilqr_workspace_create(ctx._h, m, n, C.byref(self._h)))
+
+    def _len(self, name: str) -> int:
+        return self.m if name in self.ROW_SIDE else self.n
+
+    @property
+    def x(self) -> DeviceVector:
+        if self.adopted:
+            return self._vec["x"]
+        return DeviceVector(self.ctx, self.n, ptr=lib().khip_trilqr_solution_x(self._h), owner=self)
+
+    @property
+    def y(self) -> DeviceVector:
+        if self.adopted:
+            return self._vec["y"]
+        return DeviceVector(self.ctx, self.m, ptr=lib().khip_trilqr_solution_y(self._h), owner=self)
+
+    @property
+    def stats(self) -> AdjointStats:
+        sp, sd, np_, nd = _int(), _int(), _int(), _int()
+        rp, rd, status = c_double_p(), c_double_p(), C.c_char_p()
+        _ck(lib().khip_trilqr_adjoint_stats(self._h, C.byref(sp), C.byref(sd), C.byref(rp), C.byref(np_), C.byref(rd), C.byref(nd),
+                                            C.byref(status)))
+        st = AdjointStats(lib().khip_trilqr_stats(self._h).contents, sp.value, sd.value,
+                          np.array(rp[:np_.value]) if np_.value else np.zeros(0), np.array(rd[:nd.value]) if nd.value else np.zeros(0),
+                          (status.value or b"").decode("utf-8"))
+        if self.adopted:
+            st.allocation_timer += self._alloc_s
+        st.timer += getattr(self, "_timer_extra", 0.0)
+        return st
+
+    def vector(self, name: str):
+        if name in self.SOLUTIONS:
+            return getattr(self, name)
+        p = lib().khip_trilqr_vector(self._h, name.encode())
+        return DeviceVector(self.ctx, self._len(name), ptr=p, owner=self) if p else None
+
+    def warm_start_(self, x0: DeviceVector, y0: DeviceVector | None = None):
+        """warm_start!(workspace, x0, y0) (src/workspace_accessors.jl): Δx (n) and Δy (m) are allocated on first need; both are
+        required."""
+        if y0 is None or x0 is None:
+            raise KhipError(-1, "trilqr: warm_start needs x0 and y0")
+        if self.adopted:
+            for name, src in (("dx", x0), ("dy", y0)):
+                if name not in self._vec:
+                    t0 = time.perf_counter()
+                    v = self.ctx.empty(self._len(name))
+                    self._alloc_s += time.perf_counter() - t0
+                    self._adopt_vector(name, v)
+                kcopy_(self._len(name), self._vec[name], src)
+            _ck(lib().khip_trilqr_warm_start(self._h, self._vec["dx"].ptr, self._vec["dy"].ptr))     # same pointers: only the flag
+        else:
+            _ck(lib().khip_trilqr_warm_start(self._h, _p(x0), _p(y0)))
+        return self
+
+
 class CgsWorkspace(_BiLanczosWorkspace):
     """CgsWorkspace(m, n, S) (src/krylov_workspaces.jl): x, r, u, p, q, ts; Δx, yz, vw stay empty until needed.  cgs! rotates no
     roles: every name keeps its buffer."""
@@ -2170,6 +2271,31 @@ def usymlq_(ws: UsymlqWorkspace, A, b: DeviceVector, c: DeviceVector | None = No
     return _finish(ws, rc)
 
 
+def trilqr_(ws: TrilqrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, transfer_to_usymcg=True, **kw):
+    """trilqr!(workspace, A, b, c; transfer_to_usymcg, atol, rtol, itmax, timemax, verbose, history, callback, iostream)
+    (src/trilqr.jl:115-460): x of A x = b by USYMLQ and t of Aᴴ t = c by USYMQR from one orthogonal tridiagonalisation, for A of m rows
+    and n columns, b of m entries and c of n.  At: the adjoint of A (default: A.transpose(), built once and kept on A); a matrix-free
+    A is callable(x[n], y[m]) and brings At = callable(x[m], y[n]).  Returns the workspace."""
+    keep = []
+    if c is None:
+        raise KhipError(-1, "trilqr: c (the right-hand side of the dual system) is required")
+    if len(b) != ws.m or len(c) != ws.n:
+        raise KhipError(-1, "Inconsistent problem size")
+    if At is None:
+        At = _adjoint_of(A, solver="trilqr")
+    opts = _make_options(keep=keep, ws=ws, **kw)
+    prm = lib().khip_trilqr_default_params()
+    prm.transfer_to_usymcg = int(bool(transfer_to_usymcg))
+
+    def operator(op, nin, nout):
+        if op is None or isinstance(op, CsrMatrix):
+            return _make_operator(ws.ctx, op, nin, keep)
+        return _make_operator_mn(ws.ctx, op, nin, nout, keep)
+    rc = lib().khip_trilqr_solve(ws._h, operator(A, ws.n, ws.m), operator(At, ws.m, ws.n), _p(b), _p(c), C.byref(opts),
+                                 C.byref(prm))
+    return _finish(ws, rc)
+
+
 def bilqr_(ws: BilqrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, transfer_to_bicg=True, **kw):
     """bilqr!(workspace, A, b, c; transfer_to_bicg, atol, rtol, itmax, timemax, verbose, history, callback, iostream)
     (src/bilqr.jl:116-484): x of A x = b by BiLQ and y of A' y = c by QMR from one two-sided Lanczos process.  At: the adjoint of A
@@ -2231,6 +2357,8 @@ FORWARDED_DEFAULTS = {
                    callback=default_callback, iostream=None),
     "usymlq": dict(transfer_to_usymcg=True, atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0, timemax=math.inf, verbose=0, history=False,
                    callback=default_callback, iostream=None),
+    "trilqr": dict(transfer_to_usymcg=True, atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0, timemax=math.inf, verbose=0, history=False,
+                   callback=default_callback, iostream=None),
 }
 WORKSPACE_KWARGS = {"gmres": dict(memory=20), "block_gmres": dict(memory=5)}      # kwargs_workspace_gmres, _block_gmres
 # kwargs_workspace_minres (src/minres.jl:159): kept apart from WORKSPACE_KWARGS, whose contents tests/test_abi.py pins
@@ -2258,8 +2386,8 @@ def krylov_workspace(method: str, *args, ctx: Context | None = None, **kw):
            "minres": MinresWorkspace, "cg_lanczos_shift": CgLanczosShiftWorkspace, "bilq": BilqWorkspace,
            "qmr": QmrWorkspace, "bilqr": BilqrWorkspace, "cgs": CgsWorkspace,
            "symmlq": SymmlqWorkspace, "minres_qlp": MinresQlpWorkspace, "usymqr": UsymqrWorkspace,
-           "usymlq": UsymlqWorkspace}[method]
-    if method in ("usymqr", "usymlq") and len(args) == 3:                                   # (A, b, c): m = length(b), n = length(c)
+           "usymlq": UsymlqWorkspace, "trilqr": TrilqrWorkspace}[method]
+    if method in ("usymqr", "usymlq", "trilqr") and len(args) == 3:                                   # (A, b, c): m = length(b), n = length(c)
         A, b, c = args
         return cls(b.ctx, len(b), len(c), **kw)
     if method == "cg_lanczos_shift":                                            # (A, b, nshifts) / (m, n, nshifts)
@@ -2405,6 +2533,22 @@ def bilqr(A, b: DeviceVector, c: DeviceVector, x0=None, y0=None, **kw):
     full = _forward("bilqr", kw)
     full["timemax"] = full["timemax"] - elapsed
     bilqr_(ws, A, b, c, **full)
+    ws._timer_extra = elapsed
+    return ws.x, ws.y, ws.stats, ws
+
+
+def trilqr(A, b: DeviceVector, c: DeviceVector, x0=None, y0=None, **kw):
+    """Out-of-place trilqr(A, b, c[, x0, y0]; kwargs...) -> (x, t, stats, workspace) (src/trilqr.jl:16-26); A' is taken once and kept
+    on A.  The workspace's creation and the warm start are charged to `timemax` and `stats.timer`, as krylov_solve does."""
+    wkw = {k: kw.pop(k) for k in list(kw) if k in ("adopt", "vectors")}
+    t0 = time.perf_counter()
+    ws = TrilqrWorkspace(b.ctx, len(b), len(c), **wkw)
+    if x0 is not None or y0 is not None:
+        ws.warm_start_(x0, y0)
+    elapsed = time.perf_counter() - t0
+    full = _forward("trilqr", kw)
+    full["timemax"] = full["timemax"] - elapsed
+    trilqr_(ws, A, b, c, **full)
     ws._timer_extra = elapsed
     return ws.x, ws.y, ws.stats, ws
 
@@ -2863,6 +3007,7 @@ _INPLACE.update({CgWorkspace: ("cg", cg_), GmresWorkspace: ("gmres", gmres_), Bi
                  BlockGmresWorkspace: ("block_gmres", block_gmres_), MinresWorkspace: ("minres", minres_), BilqWorkspace: ("bilq", bilq_),
                  QmrWorkspace: ("qmr", qmr_), CgsWorkspace: ("cgs", cgs_), UsymqrWorkspace: ("usymqr", usymqr_),
                  UsymlqWorkspace: ("usymlq", usymlq_),
+                 TrilqrWorkspace: ("trilqr", trilqr_),
                  SymmlqWorkspace: ("symmlq", symmlq_),
                  MinresQlpWorkspace: ("minres_qlp", minres_qlp_),
                  BilqrWorkspace: ("bilqr", bilqr_),

@@ -508,7 +508,8 @@ enum ProfTag { kProfSpmv = 0, kProfSpmm = 1, kProfPanelTn = 2, kProfPanelNnTn = 
                kProfSpmvBoundary = 10,  // the boundary rows' launch of a row-partitioned product (after the halo has arrived)
                kProfSsyP1 = 11, kProfSsyP2 = 12, kProfUsymqrP3 = 13,   // the fused passes of usymqr! (ssy.hpp, usymqr.cpp), without their finish kernels
                kProfUsymlqP3 = 14,      // P3 of usymlq! (usymlq.cpp); its P1 and P2 are the two Ssy brackets
-               kProfTags = 15 };
+               kProfTrilqrP3 = 15,      // P3 of trilqr! (trilqr.cpp); its P1 and P2 are the two Ssy brackets
+               kProfTags = 16 };
 struct ProfScope {
   khip_ctx *ctx;
   hipEvent_t stop = nullptr;

@@ -19,7 +19,8 @@ enum Epilogue { EPI_NONE = 0, EPI_CG_STEP1 = 1, EPI_CG_STEP2 = 2, EPI_BICG_A = 3
                EPI_BILQ_A = 12, EPI_BILQ_B = 13, EPI_BILQ_C = 14, EPI_QMR_A = 15, EPI_QMR_B = 16, EPI_QMR_C = 17,
                EPI_BILQR_A = 18, EPI_BILQR_B = 19, EPI_BILQR_C = 20, EPI_CGS_A = 21, EPI_CGS_B = 22,
                EPI_SYMMLQ_A = 23, EPI_SYMMLQ_B = 24, EPI_MINRES_QLP_X = 25, EPI_MINRES_QLP_A = 26, EPI_MINRES_QLP_B = 27,
-               EPI_USYMQR_A = 28, EPI_USYMQR_B = 29, EPI_USYMLQ_A = 30, EPI_USYMLQ_B = 31 };
+               EPI_USYMQR_A = 28, EPI_USYMQR_B = 29, EPI_USYMLQ_A = 30, EPI_USYMLQ_B = 31,
+               EPI_TRILQR_A = 32, EPI_TRILQR_B = 33 };
 
 struct CgDevState {
   double gamma;        // r.z of the current iterate              (src/cg.jl:162, 257)
@@ -1128,6 +1129,143 @@ __host__ __device__ inline bool usymlq_step_b(UsymlqDevState &s, double qq, doub
   return s.solved_lq || s.solved_cg;
 }
 
+// trilqr! (src/trilqr.jl:115-460), real Float64: ONE orthogonal tridiagonalisation that advances the USYMLQ iterate of A x = b (with
+// the transfer to the USYMCG point) and the USYMQR iterate of Aᴴ t = c.  As for usymlq!: the same two steps run on the host (loops 0
+// and 1) and as the epilogues of the two reductions of an iteration (device-resident loop), so loops 1 and 2 produce the same bits.
+// The primal block is frozen once solved_primal is set, the dual block once solved_dual is set; the LQ factorisation and the
+// shifts go on.  Both tests belong to P2's epilogue, which runs BEFORE P3: primal_on / dual_on keep for P3 which sides were
+// unsolved when the iteration began.
+struct TrilqrDevState : SsyCoef {
+  // coefficients the vector kernels read (γₖ, βₖ, αₖ: SsyCoef)
+  double beta_next, gamma_next;  // βₖ₊₁, γₖ₊₁: the divisors of P3               (src/trilqr.jl:223-224, :392-397)
+  double zc, zs, neg_c, sn;      // ζₖ₋₁cₖ, ζₖ₋₁sₖ, -cₖ, sₖ: the x and d̅ updates (:289-294)
+  double neg_eps3, neg_lambda2;  // -ϵₖ₋₃, -λₖ₋₂: kscal! and the second kaxpy! of wₖ₋₁ (:347, :352, :355)
+  double delta, inv_delta;       // δₖ₋₁: kdivcopy!(w₁, v₁, δ₁) (:341); one(T) / δₖ₋₁: kdiv! = kscal!(one(T) / δₖ₋₁) (:348, :356)
+  double psi;                    // ψₖ₋₁: t = t + ψₖ₋₁ wₖ₋₁                       (:367)
+  // constants of the solve
+  double bNorm, eps_L, eps_Q;    // ‖r₀‖, εL = atol + rtol ‖r₀‖, εQ = atol + rtol ‖s₀‖ (:154, :165-166)
+  double atol, rtol, xi;         // ξ = atol + rtol ‖A s₀‖, known after iteration 1 of an unsolved dual side (:381)
+  // recurrences
+  double cs, cs_prev, sn_prev;   // cₖ, cₖ₋₁, sₖ₋₁
+  double lambda, epsilon;        // λₖ₋₁, ϵₖ₋₂
+  double lambda2, eps3;          // λₖ₋₂, ϵₖ₋₃
+  double dbar, dbar_prev;        // δbarₖ, δbarₖ₋₁
+  double zeta_m1, zeta_m2, zbar; // ζₖ₋₁, ζₖ₋₂, ζbarₖ
+  double eta;                    // ηₖ
+  double psibar, psibar_prev;    // ψbarₖ, ψbarₖ₋₁
+  double rNorm_lq, rNorm_cg, sNorm, AsNorm;
+  long long stop_seq, iter, hist_base, hist_cap;
+  long long nhist_p, nhist_d;    // the last iteration that pushed to the primal / dual history: each side stops when it is solved
+  double *hist_p, *hist_d;       // device history windows (null: no history)
+  int transfer;                  // transfer_to_usymcg
+  int primal_on, dual_on;        // the sides that were unsolved when this iteration began: what P3 updates
+  int solved_lq, solved_cg, solved_primal, solved_dual, inconsistent;
+  int solved_lq_tol, solved_lq_mach, solved_cg_tol, solved_cg_mach, solved_qr_tol, solved_qr_mach;
+};
+
+// after αₖ = ⟨vₖ, q⟩ (:218)
+__host__ __device__ inline void trilqr_step_a(TrilqrDevState &s, double vq) { s.alpha = vq; }
+
+// after ‖q‖² and ‖p‖²: βₖ₊₁, γₖ₊₁ and the LQ update always (:223-255); ζ, η, the two residual norms and the tests of a primal side
+// still unsolved (:257-324); ψ, ‖sₖ₋₁‖, ‖A sₖ₋₁‖, ξ at k = 1 and the tests of a dual side still unsolved (:326-386); the shifts always
+// (:399-410); k = iter.  True when the loop stops (tired / overtimed / the callback are the driver's).  P3 of this iteration
+// still runs: the reference updates x, d̅, wₖ₋₁, t, vₖ₊₁ and uₖ₊₁ before it tests.
+__host__ __device__ inline bool trilqr_step_b(TrilqrDevState &s, double qq, double pp, long long k) {
+  const double epsM = 2.220446049250313e-16;
+  s.beta_next = sqrt(qq);
+  s.gamma_next = sqrt(pp);
+  if (k == 1) {
+    s.dbar = s.alpha;
+  } else if (k == 2) {
+    sym_givens(s.dbar_prev, s.gamma, s.cs, s.sn, s.delta);
+    s.lambda = s.cs * s.beta + s.sn * s.alpha;
+    s.dbar = s.sn * s.beta - s.cs * s.alpha;
+  } else {
+    sym_givens(s.dbar_prev, s.gamma, s.cs, s.sn, s.delta);
+    s.epsilon = s.sn_prev * s.beta;
+    s.lambda = -s.cs_prev * s.cs * s.beta + s.sn * s.alpha;
+    s.dbar = -s.cs_prev * s.sn * s.beta - s.cs * s.alpha;
+  }
+  s.primal_on = s.solved_primal ? 0 : 1;
+  s.dual_on = s.solved_dual ? 0 : 1;
+  if (s.primal_on) {
+    if (k == 1) s.eta = s.beta;
+    if (k == 2) {
+      const double eta_prev = s.eta;
+      s.zeta_m1 = eta_prev / s.delta;
+      s.eta = -s.lambda * s.zeta_m1;
+    }
+    if (k >= 3) {
+      s.zeta_m2 = s.zeta_m1;
+      const double eta_prev = s.eta;
+      s.zeta_m1 = eta_prev / s.delta;
+      s.eta = -s.epsilon * s.zeta_m2 - s.lambda * s.zeta_m1;
+    }
+    s.zc = s.zeta_m1 * s.cs;
+    s.zs = s.zeta_m1 * s.sn;
+    s.neg_c = -s.cs;
+    if (k == 1) {
+      s.rNorm_lq = s.bNorm;
+    } else {
+      const double mu = s.beta * (s.sn_prev * s.zeta_m2 - s.cs_prev * s.cs * s.zeta_m1) + s.alpha * s.sn * s.zeta_m1;
+      const double omega = s.beta_next * s.sn * s.zeta_m1;
+      s.rNorm_lq = sqrt(mu * mu + omega * omega);
+    }
+    if (s.hist_p) {
+      const long long idx = k - 1 - s.hist_base;
+      if (idx >= 0 && idx < s.hist_cap) s.hist_p[idx] = s.rNorm_lq;
+    }
+    s.nhist_p = k;
+    const bool cg_point = s.transfer && (fabs(s.dbar) > epsM);
+    if (cg_point) {
+      s.zbar = s.eta / s.dbar;
+      const double rho = s.beta_next * (s.sn * s.zeta_m1 - s.cs * s.zbar);
+      s.rNorm_cg = fabs(rho);
+    }
+    s.solved_lq_tol = (s.rNorm_lq <= s.eps_L) ? 1 : 0;
+    s.solved_lq_mach = (s.rNorm_lq + 1.0 <= 1.0) ? 1 : 0;
+    s.solved_lq = (s.solved_lq_tol || s.solved_lq_mach) ? 1 : 0;
+    s.solved_cg_tol = (cg_point && s.rNorm_cg <= s.eps_L) ? 1 : 0;
+    s.solved_cg_mach = (cg_point && s.rNorm_cg + 1.0 <= 1.0) ? 1 : 0;
+    s.solved_cg = (s.solved_cg_tol || s.solved_cg_mach) ? 1 : 0;
+    s.solved_primal = (s.solved_lq || s.solved_cg) ? 1 : 0;
+  }
+  if (s.dual_on) {
+    if (k == 1) {
+      s.psibar = s.gamma;
+    } else {
+      s.psi = s.cs * s.psibar_prev;
+      s.psibar = s.sn * s.psibar_prev;
+    }
+    s.neg_eps3 = -s.eps3;
+    s.neg_lambda2 = -s.lambda2;
+    s.inv_delta = 1.0 / s.delta;
+    s.psibar_prev = s.psibar;
+    s.sNorm = fabs(s.psibar);
+    if (s.hist_d) {
+      const long long idx = k - 1 - s.hist_base;
+      if (idx >= 0 && idx < s.hist_cap) s.hist_d[idx] = s.sNorm;
+    }
+    s.nhist_d = k;
+    const double cb = s.cs * s.beta_next;
+    s.AsNorm = fabs(s.psibar) * sqrt(s.dbar * s.dbar + cb * cb);
+    if (k == 1) s.xi = s.atol + s.rtol * s.AsNorm;
+    s.solved_qr_tol = (s.sNorm <= s.eps_Q) ? 1 : 0;
+    s.solved_qr_mach = (s.sNorm + 1.0 <= 1.0) ? 1 : 0;
+    s.inconsistent = (s.AsNorm <= s.xi) ? 1 : 0;
+    s.solved_dual = (s.solved_qr_tol || s.solved_qr_mach || s.inconsistent) ? 1 : 0;
+  }
+  if (k >= 3) s.eps3 = s.epsilon;
+  if (k >= 2) s.lambda2 = s.lambda;
+  s.dbar_prev = s.dbar;
+  s.cs_prev = s.cs;
+  s.sn_prev = s.sn;
+  s.gamma = s.gamma_next;        // P3 divides by gamma_next and beta_next; the next P1 reads gamma and beta
+  s.beta = s.beta_next;
+  s.iter = k;
+  return s.solved_primal && s.solved_dual;
+}
+
 __device__ __forceinline__ bool seq_skip(const long long *stop_seq, long long seq) {
   return stop_seq != nullptr && seq >= *stop_seq;
 }
@@ -1290,6 +1428,11 @@ __device__ inline void solver_epilogue(int epi, void *state, const double *v, lo
   } else if (epi == EPI_USYMLQ_B) {                // v = (q.q, p.p)             :221-334
     UsymlqDevState *st = static_cast<UsymlqDevState *>(state);
     if (usymlq_step_b(*st, v[0], v[1], st->iter + 1)) st->stop_seq = seq + 2;   // P3 of this iteration (seq + 1) still runs (:279-302)
+  } else if (epi == EPI_TRILQR_A) {                // v[0] = v.q                 src/trilqr.jl:218
+    trilqr_step_a(*static_cast<TrilqrDevState *>(state), v[0]);
+  } else if (epi == EPI_TRILQR_B) {                // v = (q.q, p.p)             :223-410
+    TrilqrDevState *st = static_cast<TrilqrDevState *>(state);
+    if (trilqr_step_b(*st, v[0], v[1], st->iter + 1)) st->stop_seq = seq + 2;   // P3 of this iteration (seq + 1) still runs (:283-397)
   }
 }
 

@@ -253,12 +253,17 @@ void set_history(BilqrDevState &s, double *w) {
   s.hist_p = w;
   s.hist_d = w ? w + kHistWindowMax : nullptr;
 }
+void set_history(TrilqrDevState &s, double *w) {
+  s.hist_p = w;
+  s.hist_d = w ? w + kHistWindowMax : nullptr;
+}
 
-// entries of column c of a history row (cg_lanczos_shift!: each shift's history is a prefix) or of stream c (bilqr!: each side's
+// entries of column c of a history row (cg_lanczos_shift!: each shift's history is a prefix) or of stream c (bilqr!, trilqr!: each side's
 // history ends with the iteration that solved it) that belong to a state's history
 template <class S> long long hist_rows(const S &, int) { return std::numeric_limits<long long>::max(); }
 long long hist_rows(const LanczosShiftDevState &s, int c) { return s.nhist[c]; }
 long long hist_rows(const BilqrDevState &s, int c) { return c == 0 ? s.nhist_p : s.nhist_d; }
+long long hist_rows(const TrilqrDevState &s, int c) { return c == 0 ? s.nhist_p : s.nhist_d; }
 
 struct DeviceLoopArgs {
   int64_t itmax;

@@ -159,6 +159,7 @@ template <class S, class W>
 struct SsyPolicy {
   using State = S;
   using Workspace = W;
+  void begin_iteration(const S &) {}                       // host-driven loops: before the products of an iteration
   void rotate(int64_t /*k*/) {}                            // the policy's own buffers, after P3 of iteration k
   void fix_after_device_loop(const S &) {}                 // ... which the host rotated once per ENQUEUED iteration
   void store(W *) const {}                                 // the roles of its own buffers back into the workspace
@@ -307,6 +308,7 @@ struct Ssy {
       // -------------------------------------------------------------- the reference's primitive sequence --------------
       while (running()) {
         const int64_t k = ++iter;
+        pol.begin_iteration(s);
         K(primitive_head(k));
         K(pol.primitive_tail(*this, k));
         host_tail(k);
@@ -320,6 +322,7 @@ struct Ssy {
       if (running()) K(ws->loop.upload(ctx, s));
       while (running()) {
         const int64_t k = ++iter;
+        pol.begin_iteration(s);
         K(products(r.v, r.u, r.q, r.p));
         int slot = take_slots(ctx, 1);
         K(launch_ssy_p1(ctx, n, ws->loop.dev, r.v_prev, r.u_prev, r.v, r.q, r.p, k == 1, slot));

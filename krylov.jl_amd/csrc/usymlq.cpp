@@ -24,6 +24,7 @@
 // This file owns P3, the set-up scalars, the LQ part of a primitive iteration, the USYMCG point and the status strings; the loops
 // are ssy.hpp's.
 #include "ssy.hpp"   // P1, P2 and the driver of the three loops
+#include "usymlq_xd.hpp"
 
 using namespace khip;
 
@@ -36,11 +37,7 @@ namespace khip {   // (named, not anonymous: stable kernel names in traces)
 // cacheable.  A store is non-temporal when nothing reads it before the next iteration's P3 (x, d̅); vₖ₊₁ and uₖ₊₁ are read by
 // the next products.
 
-// x and d̅ of one element from iteration 2 on (:285-290): kaxpy!(ζₖ₋₁cₖ, d̅, x) ; kaxpy!(ζₖ₋₁sₖ, uₖ, x) ; kaxpby!(-cₖ, uₖ, sₖ, d̅)
-__device__ __forceinline__ void usymlq_xd(double u, double &x, double &d, double zc, double zs, double nc, double sn) {
-  x = fma(zs, u, fma(zc, d, x));
-  d = fma(nc, u, sn * d);
-}
+// x and d̅ of one element from iteration 2 on (:285-290): usymlq_xd (usymlq_xd.hpp, shared with trilqr.cpp)
 
 // P3: first ? d̅ = u : usymlq_xd ; v_next = βₖ₊₁ ≠ 0 ? q / βₖ₊₁ : v ; u_next = γₖ₊₁ ≠ 0 ? p / γₖ₊₁ : u                (:279-302)
 // The two guards are independent.  No reduction: the sequence number comes as an argument.
