@@ -215,7 +215,7 @@ int khip_profile_spmv(khip_ctx *ctx, int64_t *launches, double *total_ms);
  * (scale + Gram), 7 = halo pack kernel, 8 = halo transfer (grouped ncclSend / ncclRecv or the all-gather of x, bracketed on the
  * stream it runs on), 9 = a dot's 16-byte all-gather + combine kernel, 10 = the boundary rows' SpMV launch of a row-partitioned
  * product (tag 0 then is the interior launch), 11 / 12 / 13 = the fused passes P1, P2 and P3 of usymqr! (the pass's own kernel, without
- * the reduction's finish kernel), 14 = P3 of usymlq! (its P1 and P2 are 11 and 12), 15 = P3 of trilqr! (likewise); at most 16 families.  Synchronises the context's streams and resets every counter. */
+ * the reduction's finish kernel), 14 = P3 of usymlq! (its P1 and P2 are 11 and 12), 15 = P3 of trilqr! (likewise), 16 = P3 of tricg! (likewise); at most 17 families.  Synchronises the context's streams and resets every counter. */
 int khip_profile_kernels(khip_ctx *ctx, int ntags, int64_t *launches, double *total_ms);
 
 /* ------------------------------------------------ BLAS-1 shim ---------------- */
@@ -787,6 +787,54 @@ int khip_trilqr_last_path(khip_trilqr_workspace *ws);
 /* named work vectors: "u_prev", "u", "p", "dbar", "x", "v_prev", "v", "q", "y", "w_prev3", "w_prev2", "dx", "dy" (NULL while not allocated) */
 double           *khip_trilqr_vector(khip_trilqr_workspace *ws, const char *name);
 size_t            khip_trilqr_workspace_bytes(khip_trilqr_workspace *ws);   /* 5n + 6m doubles without warm start */
+
+/* ---- tricg! (src/tricg.jl:149-484), real Float64, M = N = I: the 2 x 2 block system [τI A; Aᴴ νI] [x; y] = [b; c] for A of m rows and
+ * n columns (symmetric quasi-definite, saddle-point, regularised least-squares and least-norm systems), by the Galerkin iterate on
+ * the orthogonal tridiagonalisation started from b and c.  x and b have m entries, y and c have n: x is on the ROW side, unlike in
+ * usymqr!, usymlq! and trilqr!.  TricgWorkspace (src/krylov_workspaces.jl): y, uₖ₋₁, uₖ, p, gy₂ₖ₋₁, gy₂ₖ (n doubles each), x, vₖ₋₁, vₖ, q,
+ * gx₂ₖ₋₁, gx₂ₖ (m doubles each) ("y", "u_prev", "u", "p", "gy_prev", "gy", "x", "v_prev", "v", "q", "gx_prev", "gx"); Δx ("dx", m
+ * doubles) and Δy ("dy", n doubles) stay empty until a warm start.  The adjoint travels as its own operator.  options.radius,
+ * linesearch, restart, reorthogonalization and variant are ignored.  β₁ = 0 gives v₁ = 0 by a fill (likewise γ₁ and u₁), so b = 0 or
+ * c = 0 is an ordinary solve, and b = c = 0 starts solved.  τ = 0 or ν = 0 divides as the reference divides.  The fused loops rotate
+ * the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ), (gx₂ₖ₋₁, gx₂ₖ) and (gy₂ₖ₋₁, gy₂ₖ) instead of copying or swapping, and khip_tricg_vector returns a
+ * name's pointer by its current role: after k iterations every name holds what the reference's variable of that name holds, in
+ * whichever buffer -- EXCEPT "q" and "p": the reference divides them in place by βₖ₊₁ and γₖ₊₁ before it copies them into vₖ₊₁ and
+ * uₖ₊₁, loop 0 does the same, and the fused loops write the quotient into vₖ₊₁ and uₖ₊₁ only and leave q and p undivided.
+ * Out of scope: M and N other than I, complex types, fused kernels for m != n, a second fused pass that carries the third's work. */
+typedef struct khip_tricg_workspace khip_tricg_workspace;
+typedef struct khip_tricg_params {
+  double tau, nu;              /* τ, ν; defaults 1 and -1                                  (src/tricg.jl:131-132) */
+  int spd, snd, flip;          /* spd: τ = ν = 1; snd: τ = ν = -1; flip: τ = -1, ν = 1; at most one (:162-164, :176-178) */
+} khip_tricg_params;
+khip_tricg_params khip_tricg_default_params(void);   /* τ = 1, ν = -1, no flag */
+int khip_tricg_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_tricg_workspace **out);   /* m != n is allowed */
+/* TricgWorkspace on the caller's twelve vectors, in the reference's order; every pointer must be distinct.  adopt_vector names:
+ * "dx" and "dy" (Δx, Δy: warm_start! fills them on the caller's side and hands them over, then khip_tricg_warm_start(ws, dx, dy)
+ * only sets the flag) */
+int khip_tricg_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *y, double *u_prev, double *u, double *p, double *gy_prev,
+                               double *gy, double *x, double *v_prev, double *v, double *q, double *gx_prev, double *gx,
+                               khip_tricg_workspace **out);
+int khip_tricg_workspace_adopt_vector(khip_tricg_workspace *ws, const char *name, double *ptr);
+int khip_tricg_workspace_destroy(khip_tricg_workspace *ws);
+int khip_tricg_warm_start(khip_tricg_workspace *ws, const double *x0, const double *y0);   /* both are required: m and n doubles */
+/* tricg!(ws, A, b, c; spd, snd, flip, τ, ν, atol, rtol, itmax, timemax, verbose, history, callback).  At = A' (n rows, m columns) and
+ * c (n doubles) are required (NULL: KHIP_ERR_INVALID); two of spd, snd, flip together are KHIP_ERR_INVALID with the reference's
+ * message; itmax = 0 means m + n of the global system; params = NULL means the defaults.  After a warm start the right-hand sides
+ * are b - τΔx - AΔy and c - AᴴΔx - νΔy (the τ and ν terms only when the coefficient is not zero).
+ * Loops (khip_tricg_last_path): 2 = device-resident (m = n, A and At CSR handles, no callback, verbose = 0), 1 = host-driven on the
+ * same kernels (same bits as 2), 0 = one launch per primitive (options.fused = 0).  A rectangular system (m != n) runs loop 0
+ * whatever options.fused says, and last_path reports 0; a row-partitioned rectangular handle is KHIP_ERR_UNSUPPORTED.
+ * stats: residuals holds ‖r₀‖ and one entry per iteration; inconsistent = !solved && breakdown (βₖ₊₁ and γₖ₊₁ both <= eps^(3/4)). */
+int khip_tricg_solve(khip_tricg_workspace *ws, const khip_operator *A, const khip_operator *At, const double *b, const double *c,
+                     const khip_options *opts, const khip_tricg_params *params);
+double           *khip_tricg_solution_x(khip_tricg_workspace *ws);        /* m doubles */
+double           *khip_tricg_solution_y(khip_tricg_workspace *ws);        /* n doubles */
+const khip_stats *khip_tricg_stats(khip_tricg_workspace *ws);
+int khip_tricg_last_path(khip_tricg_workspace *ws);
+/* named work vectors: "y", "u_prev", "u", "p", "gy_prev", "gy", "x", "v_prev", "v", "q", "gx_prev", "gx", "dx", "dy" (NULL while not
+ * allocated) */
+double           *khip_tricg_vector(khip_tricg_workspace *ws, const char *name);
+size_t            khip_tricg_workspace_bytes(khip_tricg_workspace *ws);   /* 6n + 6m doubles without warm start */
 
 /* ---- cgs! (src/cgs.jl:126-281), real Float64: square nonsymmetric systems by the conjugate gradient squared recurrence; transpose-
  * free (no A'), two products with A per iteration.  CgsWorkspace (src/krylov_workspaces.jl): x, r, u, p, q, ts; Δx, yz and vw ("dx",

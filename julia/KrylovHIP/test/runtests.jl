@@ -272,3 +272,4 @@ include("minres_qlp.jl")                                             # minres_ql
 include("usymqr.jl")                                                 # usymqr! against the generic method, rectangular and inconsistent systems
 include("usymlq.jl")                                                 # usymlq! against the generic method, both points, the breakdown system
 include("trilqr.jl")                                                 # trilqr! against the generic method: both sides, the rectangular adjoint system
+include("tricg.jl")                                                  # tricg! against the generic method: the parameters, rectangular and breakdown systems

@@ -509,7 +509,8 @@ enum ProfTag { kProfSpmv = 0, kProfSpmm = 1, kProfPanelTn = 2, kProfPanelNnTn = 
                kProfSsyP1 = 11, kProfSsyP2 = 12, kProfUsymqrP3 = 13,   // the fused passes of usymqr! (ssy.hpp, usymqr.cpp), without their finish kernels
                kProfUsymlqP3 = 14,      // P3 of usymlq! (usymlq.cpp); its P1 and P2 are the two Ssy brackets
                kProfTrilqrP3 = 15,      // P3 of trilqr! (trilqr.cpp); its P1 and P2 are the two Ssy brackets
-               kProfTags = 16 };
+               kProfTricgP3 = 16,       // P3 of tricg! (tricg.cpp); its P1 and P2 are the two Ssy brackets
+               kProfTags = 17 };
 struct ProfScope {
   khip_ctx *ctx;
   hipEvent_t stop = nullptr;

@@ -20,7 +20,7 @@ enum Epilogue { EPI_NONE = 0, EPI_CG_STEP1 = 1, EPI_CG_STEP2 = 2, EPI_BICG_A = 3
                EPI_BILQR_A = 18, EPI_BILQR_B = 19, EPI_BILQR_C = 20, EPI_CGS_A = 21, EPI_CGS_B = 22,
                EPI_SYMMLQ_A = 23, EPI_SYMMLQ_B = 24, EPI_MINRES_QLP_X = 25, EPI_MINRES_QLP_A = 26, EPI_MINRES_QLP_B = 27,
                EPI_USYMQR_A = 28, EPI_USYMQR_B = 29, EPI_USYMLQ_A = 30, EPI_USYMLQ_B = 31,
-               EPI_TRILQR_A = 32, EPI_TRILQR_B = 33 };
+               EPI_TRILQR_A = 32, EPI_TRILQR_B = 33, EPI_TRICG_A = 34, EPI_TRICG_B = 35 };
 
 struct CgDevState {
   double gamma;        // r.z of the current iterate              (src/cg.jl:162, 257)
@@ -1266,6 +1266,84 @@ __host__ __device__ inline bool trilqr_step_b(TrilqrDevState &s, double qq, doub
   return s.solved_primal && s.solved_dual;
 }
 
+// tricg! (src/tricg.jl:149-484), real Float64, M = N = I: the Galerkin iterate of [τI A; Aᴴ νI] [x; y] = [b; c] on the same
+// orthogonal tridiagonalisation, by an LDLᴴ factorisation of the projected 2k × 2k matrix.  As for its siblings, the same two
+// steps run on the host (loops 0 and 1) and as the epilogues of the two reductions of an iteration (device-resident loop).
+// Step A needs αₖ only and does the whole LDLᴴ and π update; step B needs the two norms.  P3 of an iteration runs AFTER its
+// step B and reads σₖ, ηₖ, λₖ, δₖ, π₂ₖ₋₁, π₂ₖ, βₖ₊₁ and γₖ₊₁: step B leaves them alone, the next step A (after that P3) rewrites them.
+struct TricgDevState : SsyCoef {
+  // coefficients the vector kernels read (γₖ, βₖ, αₖ: SsyCoef)
+  double beta_next, gamma_next;  // βₖ₊₁, γₖ₊₁                                      (src/tricg.jl:411-412)
+  double inv_beta_next, inv_gamma_next;   // kdiv! = kscal!(one(T) / ·)             (:416, :424)
+  double sigma, eta, lambda, delta;       // σₖ, ηₖ, λₖ, δₖ                          (:332-339)
+  double neg_sigma, neg_delta;            // the coefficients as the primitives get them (:368, :387-392)
+  double pi1, pi2;               // π₂ₖ₋₁, π₂ₖ                                      (:356-360)
+  // constants of the solve
+  double tau, nu;                // τ, ν after flip / spd / snd                    (:176-178)
+  double eps_tol, btol;          // ε = atol + rtol ‖r₀‖ (:261), eps^(3/4) (:272)
+  // recurrences
+  double d1, d2;                 // d₂ₖ₋₁, d₂ₖ
+  double d_m3, d_m2;             // d₂ₖ₋₃, d₂ₖ₋₂
+  double pi_m3, pi_m2;           // π₂ₖ₋₃, π₂ₖ₋₂
+  double delta_prev;             // δₖ₋₁
+  double rNorm;
+  long long stop_seq, iter, hist_base, hist_cap;
+  double *hist;                  // device history window (null: no history)
+  int solved, breakdown;
+};
+
+// after αₖ = ⟨vₖ, q⟩ (:298): the LDLᴴ factorisation (:330-341) and π₂ₖ₋₁, π₂ₖ (:355-361); k = iter + 1.  τ = 0 or ν = 0 divides as
+// the reference divides.
+__host__ __device__ inline void tricg_step_a(TricgDevState &s, double vq) {
+  s.alpha = vq;
+  if (s.iter == 0) {
+    s.d1 = s.tau;
+    s.delta = s.alpha / s.d1;
+    s.d2 = s.nu - (s.delta * s.delta) * s.d1;
+    s.pi1 = s.beta / s.d1;
+    s.pi2 = (s.gamma - s.delta * s.beta) / s.d2;
+  } else {
+    s.sigma = s.beta / s.d_m2;
+    s.eta = s.gamma / s.d_m3;
+    s.lambda = -(s.eta * s.delta_prev * s.d_m3) / s.d_m2;
+    s.d1 = s.tau - (s.sigma * s.sigma) * s.d_m2;
+    s.delta = (s.alpha - s.lambda * s.sigma * s.d_m2) / s.d1;
+    s.d2 = s.nu - (s.eta * s.eta) * s.d_m3 - (s.lambda * s.lambda) * s.d_m2 - (s.delta * s.delta) * s.d1;
+    s.pi1 = -(s.sigma * s.d_m2 * s.pi_m2) / s.d1;
+    s.pi2 = -(s.delta * s.d1 * s.pi1 + s.lambda * s.d_m2 * s.pi_m2 + s.eta * s.d_m3 * s.pi_m3) / s.d2;
+  }
+  s.neg_sigma = -s.sigma;
+  s.neg_delta = -s.delta;
+}
+
+// after ‖q‖² and ‖p‖²: βₖ₊₁, γₖ₊₁ (:411-412), ζ₂ₖ₋₁, ‖rₖ‖ (:435-438), the shift of the "previous" scalars (:441-447) and the tests
+// (:451-457); k = iter.  True when the loop stops (tired / overtimed / the callback are the driver's).  P3 of this iteration
+// still runs: the reference updates the g, x, y, vₖ₊₁ and uₖ₊₁ before it tests.
+__host__ __device__ inline bool tricg_step_b(TricgDevState &s, double qq, double pp, long long k) {
+  s.beta_next = sqrt(qq);
+  s.gamma_next = sqrt(pp);
+  s.inv_beta_next = 1.0 / s.beta_next;
+  s.inv_gamma_next = 1.0 / s.gamma_next;
+  const double zeta1 = s.pi1 - s.delta * s.pi2;
+  const double gz = s.gamma_next * zeta1, bz = s.beta_next * s.pi2;
+  s.rNorm = sqrt(gz * gz + bz * bz);
+  if (s.hist) {
+    const long long idx = k - 1 - s.hist_base;
+    if (idx >= 0 && idx < s.hist_cap) s.hist[idx] = s.rNorm;
+  }
+  s.beta = s.beta_next;          // P3 reads beta_next and gamma_next; the next P1 reads beta and gamma
+  s.gamma = s.gamma_next;
+  s.pi_m3 = s.pi1;
+  s.pi_m2 = s.pi2;
+  s.d_m3 = s.d1;
+  s.d_m2 = s.d2;
+  s.delta_prev = s.delta;
+  s.breakdown = (s.beta_next <= s.btol && s.gamma_next <= s.btol) ? 1 : 0;
+  s.solved = (s.rNorm <= s.eps_tol || s.rNorm + 1.0 <= 1.0) ? 1 : 0;
+  s.iter = k;
+  return s.solved || s.breakdown;
+}
+
 __device__ __forceinline__ bool seq_skip(const long long *stop_seq, long long seq) {
   return stop_seq != nullptr && seq >= *stop_seq;
 }
@@ -1433,6 +1511,11 @@ __device__ inline void solver_epilogue(int epi, void *state, const double *v, lo
   } else if (epi == EPI_TRILQR_B) {                // v = (q.q, p.p)             :223-410
     TrilqrDevState *st = static_cast<TrilqrDevState *>(state);
     if (trilqr_step_b(*st, v[0], v[1], st->iter + 1)) st->stop_seq = seq + 2;   // P3 of this iteration (seq + 1) still runs (:283-397)
+  } else if (epi == EPI_TRICG_A) {                 // v[0] = v.q                 src/tricg.jl:298
+    tricg_step_a(*static_cast<TricgDevState *>(state), v[0]);
+  } else if (epi == EPI_TRICG_B) {                 // v = (q.q, p.p)             :411-457
+    TricgDevState *st = static_cast<TricgDevState *>(state);
+    if (tricg_step_b(*st, v[0], v[1], st->iter + 1)) st->stop_seq = seq + 2;    // P3 of this iteration (seq + 1) still runs (:364-432)
   }
 }
 
