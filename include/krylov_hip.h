@@ -215,7 +215,7 @@ int khip_profile_spmv(khip_ctx *ctx, int64_t *launches, double *total_ms);
  * (scale + Gram), 7 = halo pack kernel, 8 = halo transfer (grouped ncclSend / ncclRecv or the all-gather of x, bracketed on the
  * stream it runs on), 9 = a dot's 16-byte all-gather + combine kernel, 10 = the boundary rows' SpMV launch of a row-partitioned
  * product (tag 0 then is the interior launch), 11 / 12 / 13 = the fused passes P1, P2 and P3 of usymqr! (the pass's own kernel, without
- * the reduction's finish kernel), 14 = P3 of usymlq! (its P1 and P2 are 11 and 12), 15 = P3 of trilqr! (likewise), 16 = P3 of tricg! (likewise); at most 17 families.  Synchronises the context's streams and resets every counter. */
+ * the reduction's finish kernel), 14 = P3 of usymlq! (its P1 and P2 are 11 and 12), 15 = P3 of trilqr! (likewise), 16 = P3 of tricg! (likewise), 17 = P3 of trimr! (likewise); at most 18 families.  Synchronises the context's streams and resets every counter. */
 int khip_profile_kernels(khip_ctx *ctx, int ntags, int64_t *launches, double *total_ms);
 
 /* ------------------------------------------------ BLAS-1 shim ---------------- */
@@ -835,6 +835,55 @@ int khip_tricg_last_path(khip_tricg_workspace *ws);
  * allocated) */
 double           *khip_tricg_vector(khip_tricg_workspace *ws, const char *name);
 size_t            khip_tricg_workspace_bytes(khip_tricg_workspace *ws);   /* 6n + 6m doubles without warm start */
+
+/* ---- trimr! (src/trimr.jl:150-577), real Float64, M = N = I: the same 2 x 2 block system [τI A; Aᴴ νI] [x; y] = [b; c] as tricg!, by
+ * the minimal-residual iterate on the orthogonal tridiagonalisation started from b and c (a QR factorisation in scalars).  It never
+ * divides by τ or ν: saddle-point systems (ν = 0, the sp flag) and adjoint systems (τ = ν = 0) are ordinary solves, and the residual
+ * history is non-increasing.  x and b have m entries, y and c have n: x is on the ROW side, as in tricg!.  TrimrWorkspace
+ * (src/krylov_workspaces.jl): y, uₖ₋₁, uₖ, p, gy₂ₖ₋₃, gy₂ₖ₋₂, gy₂ₖ₋₁, gy₂ₖ (n doubles each), x, vₖ₋₁, vₖ, q, gx₂ₖ₋₃, gx₂ₖ₋₂, gx₂ₖ₋₁, gx₂ₖ (m doubles each)
+ * ("y", "u_prev", "u", "p", "gy_m3", "gy_m2", "gy_m1", "gy", "x", "v_prev", "v", "q", "gx_m3", "gx_m2", "gx_m1", "gx"); Δx ("dx", m
+ * doubles) and Δy ("dy", n doubles) stay empty until a warm start.  The adjoint travels as its own operator.  options.radius,
+ * linesearch, restart, reorthogonalization and variant are ignored.  β₁ = 0 gives v₁ = 0 by a fill (likewise γ₁ and u₁), so b = 0 or
+ * c = 0 is an ordinary solve, and b = c = 0 starts solved.  The fused loops rotate the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and of the older
+ * and the newer pair of g of each side, (g₂ₖ₋₃, g₂ₖ₋₂) and (g₂ₖ₋₁, g₂ₖ), instead of copying or swapping, and khip_trimr_vector returns a
+ * name's pointer by its current role: after k iterations every name holds what the reference's variable of that name holds, in
+ * whichever buffer -- EXCEPT "q" and "p": the reference divides them in place by βₖ₊₁ and γₖ₊₁ before it copies them into vₖ₊₁ and
+ * uₖ₊₁, loop 0 does the same, and the fused loops write the quotient into vₖ₊₁ and uₖ₊₁ only and leave q and p undivided.
+ * Out of scope: M and N other than I, complex types, fused kernels for m != n, Float32. */
+typedef struct khip_trimr_workspace khip_trimr_workspace;
+typedef struct khip_trimr_params {
+  double tau, nu;              /* τ, ν; defaults 1 and -1                                  (src/trimr.jl:132-133) */
+  int spd, snd, flip, sp;      /* spd: τ = ν = 1; snd: τ = ν = -1; flip: τ = -1, ν = 1; sp: τ = 1, ν = 0; at most one (:163-168, :180-183) */
+} khip_trimr_params;
+khip_trimr_params khip_trimr_default_params(void);   /* τ = 1, ν = -1, no flag */
+int khip_trimr_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_trimr_workspace **out);   /* m != n is allowed */
+/* TrimrWorkspace on the caller's sixteen vectors, in the reference's order; every pointer must be distinct.  adopt_vector names:
+ * "dx" and "dy" (Δx, Δy: warm_start! fills them on the caller's side and hands them over, then khip_trimr_warm_start(ws, dx, dy)
+ * only sets the flag) */
+int khip_trimr_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *y, double *u_prev, double *u, double *p, double *gy_m3,
+                               double *gy_m2, double *gy_m1, double *gy, double *x, double *v_prev, double *v, double *q, double *gx_m3,
+                               double *gx_m2, double *gx_m1, double *gx, khip_trimr_workspace **out);
+int khip_trimr_workspace_adopt_vector(khip_trimr_workspace *ws, const char *name, double *ptr);
+int khip_trimr_workspace_destroy(khip_trimr_workspace *ws);
+int khip_trimr_warm_start(khip_trimr_workspace *ws, const double *x0, const double *y0);   /* both are required: m and n doubles */
+/* trimr!(ws, A, b, c; spd, snd, flip, sp, τ, ν, atol, rtol, itmax, timemax, verbose, history, callback).  At = A' (n rows, m columns)
+ * and c (n doubles) are required (NULL: KHIP_ERR_INVALID); two of spd, snd, flip, sp together are KHIP_ERR_INVALID with the
+ * reference's message; itmax = 0 means m + n of the global system; params = NULL means the defaults.  After a warm start the
+ * right-hand sides are b - τΔx - AΔy and c - AᴴΔx - νΔy (the τ and ν terms only when the coefficient is not zero).
+ * Loops (khip_trimr_last_path): 2 = device-resident (m = n, A and At CSR handles, no callback, verbose = 0), 1 = host-driven on the
+ * same kernels (same bits as 2), 0 = one launch per primitive (options.fused = 0).  A rectangular system (m != n) runs loop 0
+ * whatever options.fused says, and last_path reports 0; a row-partitioned rectangular handle is KHIP_ERR_UNSUPPORTED.
+ * stats: residuals holds ‖r₀‖ and one entry per iteration; inconsistent = !solved && breakdown (βₖ₊₁ and γₖ₊₁ both <= eps^(3/4)). */
+int khip_trimr_solve(khip_trimr_workspace *ws, const khip_operator *A, const khip_operator *At, const double *b, const double *c,
+                     const khip_options *opts, const khip_trimr_params *params);
+double           *khip_trimr_solution_x(khip_trimr_workspace *ws);        /* m doubles */
+double           *khip_trimr_solution_y(khip_trimr_workspace *ws);        /* n doubles */
+const khip_stats *khip_trimr_stats(khip_trimr_workspace *ws);
+int khip_trimr_last_path(khip_trimr_workspace *ws);
+/* named work vectors: "y", "u_prev", "u", "p", "gy_m3", "gy_m2", "gy_m1", "gy", "x", "v_prev", "v", "q", "gx_m3", "gx_m2", "gx_m1", "gx",
+ * "dx", "dy" (NULL while not allocated) */
+double           *khip_trimr_vector(khip_trimr_workspace *ws, const char *name);
+size_t            khip_trimr_workspace_bytes(khip_trimr_workspace *ws);   /* 8n + 8m doubles without warm start */
 
 /* ---- cgs! (src/cgs.jl:126-281), real Float64: square nonsymmetric systems by the conjugate gradient squared recurrence; transpose-
  * free (no A'), two products with A per iteration.  CgsWorkspace (src/krylov_workspaces.jl): x, r, u, p, q, ts; Δx, yz and vw ("dx",

@@ -121,6 +121,19 @@ int khip_test_multi_dot(khip_ctx *ctx, int64_t n, int k, const double *const *V_
 int khip_test_multi_axpy_dev(khip_ctx *ctx, int64_t n, int k, const double *coef_host, const double *const *V_host, double *x);
 int khip_test_divcopy_dev(khip_ctx *ctx, int64_t n, double sumsq, const double *x, double *y);
 
+/* test-only: the two vector kernels of trimr! (csrc/trimr.cpp) with the caller's coefficients and device vectors
+ * (tests/test_gpu_trimr.py compares every output with the NumPy expression, bit for bit).
+ * khip_test_trimr_p3: the fused third pass at stage 1, 2 or 3 (= min(k, 3)).  coef16 (host) = row one (μ₂ₖ₋₅, λ₂ₖ₋₄, η₂ₖ₋₃, σ₂ₖ₋₂, δ₂ₖ₋₁), row
+ * two (μ₂ₖ₋₄, λ₂ₖ₋₃, η₂ₖ₋₂, σ₂ₖ₋₁, δ₂ₖ), -σ₁ / δ₂, π₂ₖ₋₁, π₂ₖ, βₖ₊₁, γₖ₊₁, btol.  g8 (host array of device pointers) = gx₂ₖ₋₃, gx₂ₖ₋₂, gx₂ₖ₋₁, gx₂ₖ,
+ * gy₂ₖ₋₃, gy₂ₖ₋₂, gy₂ₖ₋₁, gy₂ₖ by their role as the iteration begins: stage 1 writes gx₂ₖ₋₁, gx₂ₖ and gy₂ₖ; stages 2 and 3 write the new
+ * (g₂ₖ₋₁, g₂ₖ) into the buffers of (g₂ₖ₋₃, g₂ₖ₋₂).  v_next / u_next take vₖ₊₁ / uₖ₊₁.  All vectors have n entries.
+ * khip_test_trimr_g: one broadcast of the primitive sequence, out = (w - c[0] a0 - c[1] a1 [- c[2] a2 [- c[3] a3]]) / delta with
+ * nterm = 2, 3 or 4 terms; w = NULL puts -(c[0] a0) in front.  out may be one of the a. */
+int khip_test_trimr_p3(khip_ctx *ctx, int64_t n, int stage, const double *coef16, double *x, double *y, double *const *g8, const double *v,
+                       const double *u, const double *q, const double *p, double *v_next, double *u_next);
+int khip_test_trimr_g(khip_ctx *ctx, int64_t n, double *out, const double *w, int nterm, const double *coef4, const double *a0,
+                      const double *a1, const double *a2, const double *a3, double delta);
+
 #ifdef __cplusplus
 }
 #endif

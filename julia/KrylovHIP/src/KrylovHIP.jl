@@ -891,6 +891,70 @@ function Krylov.tricg!(ws::TricgWs, A::HIPCsr, b::HIPVector, c::HIPVector; M = I
   return ws
 end
 
+# ------------------------------------------------------------------------------------------------ trimr!  (src/trimr.jl:150-577)
+struct TrimrParams                 # khip_trimr_params: τ, ν, spd, snd, flip, sp
+  tau::Cdouble
+  nu::Cdouble
+  spd::Cint
+  snd::Cint
+  flip::Cint
+  sp::Cint
+end
+const TrimrWs = TrimrWorkspace{Float64,Float64,HIPVector,HIPVector}
+function trimr_handle(ws::TrimrWs)
+  get!(HANDLES, ws) do
+    r = Ref{Ptr{Cvoid}}()
+    ck(ccall((:khip_trimr_workspace_adopt, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                                                       Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                                                       Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                                                       Ref{Ptr{Cvoid}}),
+             CTX[].h, ws.m, ws.n, ws.y.ptr, ws.N⁻¹uₖ₋₁.ptr, ws.N⁻¹uₖ.ptr, ws.p.ptr, ws.gy₂ₖ₋₃.ptr, ws.gy₂ₖ₋₂.ptr, ws.gy₂ₖ₋₁.ptr, ws.gy₂ₖ.ptr, ws.x.ptr, ws.M⁻¹vₖ₋₁.ptr, ws.M⁻¹vₖ.ptr, ws.q.ptr, ws.gx₂ₖ₋₃.ptr, ws.gx₂ₖ₋₂.ptr, ws.gx₂ₖ₋₁.ptr, ws.gx₂ₖ.ptr, r))
+    h = r[]
+    finalizer(_ -> ccall((:khip_trimr_workspace_destroy, lib), Cint, (Ptr{Cvoid},), h), ws)
+    h
+  end
+end
+trimr_adopt(h, name, v::HIPVector) = ck(ccall((:khip_trimr_workspace_adopt_vector, lib), Cint, (Ptr{Cvoid}, Cstring, Ptr{Cdouble}), h, name, dptr(v)))
+
+# A has m rows and n columns; b and x have m entries, c and y have n.  The adjoint is `A'`, built once per matrix and cached in
+# `A.adj`.  M and N other than I take the generic method (the library has M = N = I only).  A rectangular system runs the library's
+# primitive sequence (LAST_PATH[] == 0) whatever `fused` says.  After the solve only ws.x, ws.y and ws.stats are defined: the library
+# rotates the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and of the pairs (g₂ₖ₋₃, g₂ₖ₋₂) and (g₂ₖ₋₁, g₂ₖ) of each side among the adopted vectors.
+function Krylov.trimr!(ws::TrimrWs, A::HIPCsr, b::HIPVector, c::HIPVector; M = I, N = I, ldiv::Bool = false, spd::Bool = false,
+                       snd::Bool = false, flip::Bool = false, sp::Bool = false, τ::Float64 = 1.0, ν::Float64 = -1.0, atol::Float64 = √eps(Float64),
+                       rtol::Float64 = √eps(Float64), itmax::Int = 0, timemax::Float64 = Inf, verbose::Int = 0, history::Bool = false,
+                       callback = nothing, iostream::IO = Krylov.kstdout, fused::Int = 2)
+  if !native_log(verbose, iostream) || !(M === I) || !(N === I)
+    GENERIC_SOLVES[] += 1
+    return invoke(Krylov.trimr!, Tuple{TrimrWs,Any,AbstractVector{Float64},AbstractVector{Float64}}, ws, A, b, c; M, N, ldiv, spd, snd, flip,
+                  sp, τ, ν, atol, rtol, itmax, timemax, verbose, history, callback = callback === nothing ? (w -> false) : callback, iostream)
+  end
+  m, n = size(A)                                                                            # :156-159
+  (m == ws.m && n == ws.n) || error("(workspace.m, workspace.n) = ($(ws.m), $(ws.n)) is inconsistent with size(A) = ($m, $n)")
+  length(b) == m || error("Inconsistent problem size")
+  length(c) == n || error("Inconsistent problem size")
+  At = A'
+  h = trimr_handle(ws)
+  for (name, v) in (("dx", ws.Δx), ("dy", ws.Δy))
+    trimr_adopt(h, name, v)
+  end
+  ws.warm_start && ck(ccall((:khip_trimr_warm_start, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), h, ws.Δx.ptr, ws.Δy.ptr))
+  stp = ccall((:khip_trimr_stats, lib), Ptr{Stats}, (Ptr{Cvoid},), h)    # (`sp` is the saddle-point keyword here)
+  cbf, cbd, box = callback_args(user_callback(callback), ws, stp, history)
+  opts = Ref(Options(; atol, rtol, itmax, timemax, history, fused, verbose, log_fd = logfd(iostream), callback = cbf, callback_data = cbd))
+  prm = Ref(TrimrParams(τ, ν, Cint(spd), Cint(snd), Cint(flip), Cint(sp)))
+  opA = Ref(Operator(A));  opAt = Ref(Operator(At))
+  rc = GC.@preserve ws A At b c opts prm opA opAt box ccall((:khip_trimr_solve, lib), Cint,
+         (Ptr{Cvoid}, Ref{Operator}, Ref{Operator}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Options}, Ptr{Cvoid}),
+         h, opA, opAt, b.ptr, c.ptr, opts, prm)
+  st = fill_stats!(ws.stats, stp, history)
+  NATIVE_SOLVES[] += 1;  LAST_PATH[] = ccall((:khip_trimr_last_path, lib), Cint, (Ptr{Cvoid},), h)
+  ws.warm_start = false
+  finish_callback(box)
+  rc == 0 || failed(st)
+  return ws
+end
+
 # ------------------------------------------------------------------------------------------------ cgs!  (src/cgs.jl:126-281)
 const CgsWs = CgsWorkspace{Float64,Float64,HIPVector}
 function cgs_handle(ws::CgsWs)

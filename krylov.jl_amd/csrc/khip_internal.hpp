@@ -510,7 +510,8 @@ enum ProfTag { kProfSpmv = 0, kProfSpmm = 1, kProfPanelTn = 2, kProfPanelNnTn = 
                kProfUsymlqP3 = 14,      // P3 of usymlq! (usymlq.cpp); its P1 and P2 are the two Ssy brackets
                kProfTrilqrP3 = 15,      // P3 of trilqr! (trilqr.cpp); its P1 and P2 are the two Ssy brackets
                kProfTricgP3 = 16,       // P3 of tricg! (tricg.cpp); its P1 and P2 are the two Ssy brackets
-               kProfTags = 17 };
+               kProfTrimrP3 = 17,       // P3 of trimr! (trimr.cpp); its P1 and P2 are the two Ssy brackets
+               kProfTags = 18 };
 struct ProfScope {
   khip_ctx *ctx;
   hipEvent_t stop = nullptr;

@@ -20,7 +20,8 @@ enum Epilogue { EPI_NONE = 0, EPI_CG_STEP1 = 1, EPI_CG_STEP2 = 2, EPI_BICG_A = 3
                EPI_BILQR_A = 18, EPI_BILQR_B = 19, EPI_BILQR_C = 20, EPI_CGS_A = 21, EPI_CGS_B = 22,
                EPI_SYMMLQ_A = 23, EPI_SYMMLQ_B = 24, EPI_MINRES_QLP_X = 25, EPI_MINRES_QLP_A = 26, EPI_MINRES_QLP_B = 27,
                EPI_USYMQR_A = 28, EPI_USYMQR_B = 29, EPI_USYMLQ_A = 30, EPI_USYMLQ_B = 31,
-               EPI_TRILQR_A = 32, EPI_TRILQR_B = 33, EPI_TRICG_A = 34, EPI_TRICG_B = 35 };
+               EPI_TRILQR_A = 32, EPI_TRILQR_B = 33, EPI_TRICG_A = 34, EPI_TRICG_B = 35,
+               EPI_TRIMR_A = 36, EPI_TRIMR_B = 37 };
 
 struct CgDevState {
   double gamma;        // r.z of the current iterate              (src/cg.jl:162, 257)
@@ -1344,6 +1345,149 @@ __host__ __device__ inline bool tricg_step_b(TricgDevState &s, double qq, double
   return s.solved || s.breakdown;
 }
 
+// trimr! (src/trimr.jl:150-577), real Float64, M = N = I: the minimal-residual iterate of [τI A; Aᴴ νI] [x; y] = [b; c] on the same
+// orthogonal tridiagonalisation, by a QR factorisation of the projected (2k + 2) × 2k matrix: four reflections per iteration.  τ and
+// ν are never divided by, so ν = 0 (saddle-point systems) and τ = ν = 0 (adjoint systems) are ordinary solves.  As for its siblings,
+// the same two steps run on the host (loops 0 and 1) and as the epilogues of the two reductions of an iteration.
+// Step A only stores αₖ: the QR update needs βₖ₊₁ and γₖ₊₁, which exist after P2.  Step B does all the rest.  P3 of iteration k runs
+// AFTER its step B and reads the twelve coefficients of the two rows of Rₖ that end in δ₂ₖ₋₁ and δ₂ₖ, π₂ₖ₋₁, π₂ₖ, βₖ₊₁ and γₖ₊₁ (at k = 1
+// also −σ₁ / δ₂): step B publishes them in fields of their own (row1, row2, …), apart from the carries its shift has already moved
+// on for k + 1; step B of k + 1 runs after P3 of k on the stream, so nothing overwrites them early.
+struct TrimrRow {
+  double mu, lambda, eta, sigma, delta;   // row one: μ₂ₖ₋₅, λ₂ₖ₋₄, η₂ₖ₋₃, σ₂ₖ₋₂, δ₂ₖ₋₁ ; row two: μ₂ₖ₋₄, λ₂ₖ₋₃, η₂ₖ₋₂, σ₂ₖ₋₁, δ₂ₖ
+};
+struct TrimrDevState : SsyCoef {
+  // coefficients the vector kernels read (γₖ, βₖ, αₖ: SsyCoef)
+  double beta_next, gamma_next;  // βₖ₊₁, γₖ₊₁                                      (src/trimr.jl:321-322)
+  double inv_beta_next, inv_gamma_next;   // kdiv! = kscal!(one(T) / ·)             (:326, :334)
+  TrimrRow row1, row2;           // what the g of iteration k are solved from       (:449-476)
+  double first_scale;            // −σ₁ / δ₂, k = 1 only                            (:450)
+  double pi1, pi2;               // π₂ₖ₋₁, π₂ₖ                                      (:485, :491)
+  // constants of the solve
+  double tau, nu;                // τ, ν after flip / spd / snd / sp               (:180-183)
+  double eps_tol, btol;          // ε = atol + rtol ‖r₀‖ (:271), eps^(3/4) (:284)
+  // carries
+  double old_c1, old_c2, old_c3, old_c4, old_s1, old_s2, old_s3, old_s4;            // :519-526
+  double sigmabar_m2, etabar_m3, lambdabar_m3;   // σbar₂ₖ₋₂, ηbar₂ₖ₋₃, λbar₂ₖ₋₃         (:531-533)
+  double mu_m5, mu_m4, lambda_m4;         // μ₂ₖ₋₅, μ₂ₖ₋₄, λ₂ₖ₋₄ (shifted from k = 2 on)  (:534-538)
+  double pibar1, pibar2;         // πbar₂ₖ₋₁, πbar₂ₖ                                 (:539-540)
+  double rNorm;
+  long long stop_seq, iter, hist_base, hist_cap;
+  double *hist;                  // device history window (null: no history)
+  int solved, breakdown;
+};
+
+// after αₖ = ⟨vₖ, q⟩ (:312): nothing else can be done before the norms
+__host__ __device__ inline void trimr_step_a(TrimrDevState &s, double vq) { s.alpha = vq; }
+
+// after ‖q‖² and ‖p‖²: βₖ₊₁, γₖ₊₁ (:321-322), the four previous reflections (:353-415), the four new ones (:421-443), the π update
+// (:482-492), ‖rₖ‖ (:503), the shifts (:519-540) and the tests (:544-551); k = iter.  True when the loop stops (tired / overtimed / the
+// callback are the driver's).  P3 of this iteration still runs: the reference updates the g, x, y, vₖ₊₁ and uₖ₊₁ before it tests.
+// Every operation in the reference's order; the build has -ffp-contract=off.
+__host__ __device__ inline bool trimr_step_b(TrimrDevState &s, double qq, double pp, long long k) {
+  s.beta_next = sqrt(qq);
+  s.gamma_next = sqrt(pp);
+  s.inv_beta_next = 1.0 / s.beta_next;
+  s.inv_gamma_next = 1.0 / s.gamma_next;
+  const double alpha = s.alpha, beta_next = s.beta_next, gamma_next = s.gamma_next, tau = s.tau, nu = s.nu;
+  double thetabar, deltabar1, deltabar2, sigmabar1, sigmabar2, lambdabar1, etabar1;
+  double eta_m3 = 0.0, lambda_m3 = 0.0, mu_m3 = 0.0, sigma_m2 = 0.0, eta_m2 = 0.0, lambda_m2 = 0.0, mu_m2 = 0.0;
+  if (k == 1) {
+    thetabar = alpha;
+    deltabar1 = tau;
+    deltabar2 = nu;
+    sigmabar1 = alpha;
+    sigmabar2 = beta_next;
+    lambdabar1 = gamma_next;
+    etabar1 = 0.0;
+  } else {
+    const double sigmabis_m2 = s.old_c1 * s.sigmabar_m2 + s.old_s1 * alpha;
+    const double etabis_m2 = s.old_s1 * nu;
+    const double lambdabis_m2 = s.old_s1 * beta_next;
+    const double thetabis = s.old_s1 * s.sigmabar_m2 - s.old_c1 * alpha;
+    const double deltabis2 = -s.old_c1 * nu;
+    const double sigmabis2 = -s.old_c1 * beta_next;
+    eta_m3 = s.old_c2 * s.etabar_m3 + s.old_s2 * sigmabis_m2;
+    lambda_m3 = s.old_c2 * s.lambdabar_m3 + s.old_s2 * etabis_m2;
+    mu_m3 = s.old_s2 * lambdabis_m2;
+    const double sigmahat_m2 = s.old_s2 * s.etabar_m3 - s.old_c2 * sigmabis_m2;
+    const double etahat_m2 = s.old_s2 * s.lambdabar_m3 - s.old_c2 * etabis_m2;
+    const double lambdahat_m2 = -s.old_c2 * lambdabis_m2;
+    const double sigmatmp_m2 = s.old_c3 * sigmahat_m2 + s.old_s3 * thetabis;
+    const double etatmp_m2 = s.old_c3 * etahat_m2 + s.old_s3 * deltabis2;
+    const double lambdatmp_m2 = s.old_c3 * lambdahat_m2 + s.old_s3 * sigmabis2;
+    thetabar = s.old_s3 * sigmahat_m2 - s.old_c3 * thetabis;
+    deltabar2 = s.old_s3 * etahat_m2 - s.old_c3 * deltabis2;
+    sigmabar2 = s.old_s3 * lambdahat_m2 - s.old_c3 * sigmabis2;
+    sigma_m2 = s.old_c4 * sigmatmp_m2 + s.old_s4 * tau;
+    eta_m2 = s.old_c4 * etatmp_m2 + s.old_s4 * alpha;
+    lambda_m2 = s.old_c4 * lambdatmp_m2;
+    mu_m2 = s.old_s4 * gamma_next;
+    deltabar1 = s.old_s4 * sigmatmp_m2 - s.old_c4 * tau;
+    sigmabar1 = s.old_s4 * etatmp_m2 - s.old_c4 * alpha;
+    etabar1 = s.old_s4 * lambdatmp_m2;
+    lambdabar1 = -s.old_c4 * gamma_next;
+  }
+  double c1, s1, theta, c2, s2, delta1, c3, s3, deltahat2, c4, s4, delta2;
+  sym_givens(thetabar, gamma_next, c1, s1, theta);                      // :421-423
+  const double g = s1 * deltabar2;
+  deltabar2 = c1 * deltabar2;
+  sym_givens(deltabar1, theta, c2, s2, delta1);                         // :429-431
+  const double sigma1 = c2 * sigmabar1 + s2 * deltabar2;
+  const double deltabis2 = s2 * sigmabar1 - c2 * deltabar2;
+  sym_givens(deltabis2, g, c3, s3, deltahat2);                          // :437
+  sym_givens(deltahat2, beta_next, c4, s4, delta2);                     // :443
+  // what P3 of this iteration reads: the carries as they are BEFORE the shift below
+  s.row1.mu = s.mu_m5;
+  s.row1.lambda = s.lambda_m4;
+  s.row1.eta = eta_m3;
+  s.row1.sigma = sigma_m2;
+  s.row1.delta = delta1;
+  s.row2.mu = s.mu_m4;
+  s.row2.lambda = lambda_m3;
+  s.row2.eta = eta_m2;
+  s.row2.sigma = sigma1;
+  s.row2.delta = delta2;
+  s.first_scale = -sigma1 / delta2;                                     // :450
+  const double pibis2 = c1 * s.pibar2;                                  // :482-492
+  const double pibis4 = s1 * s.pibar2;
+  s.pi1 = c2 * s.pibar1 + s2 * pibis2;
+  const double pihat2 = s2 * s.pibar1 - c2 * pibis2;
+  const double pitmp2 = c3 * pihat2 + s3 * pibis4;
+  const double pibar4 = s3 * pihat2 - c3 * pibis4;
+  s.pi2 = c4 * pitmp2;
+  const double pibar3 = s4 * pitmp2;
+  s.rNorm = sqrt(pibar3 * pibar3 + pibar4 * pibar4);                    // :503
+  if (s.hist) {
+    const long long idx = k - 1 - s.hist_base;
+    if (idx >= 0 && idx < s.hist_cap) s.hist[idx] = s.rNorm;
+  }
+  s.old_s1 = s1;                                                        // :519-526
+  s.old_s2 = s2;
+  s.old_s3 = s3;
+  s.old_s4 = s4;
+  s.old_c1 = c1;
+  s.old_c2 = c2;
+  s.old_c3 = c3;
+  s.old_c4 = c4;
+  s.beta = beta_next;            // P3 reads beta_next and gamma_next; the next P1 reads beta and gamma      (:529-530)
+  s.gamma = gamma_next;
+  s.sigmabar_m2 = sigmabar2;                                            // :531-533
+  s.etabar_m3 = etabar1;
+  s.lambdabar_m3 = lambdabar1;
+  if (k >= 2) {                                                         // :534-538
+    s.mu_m5 = mu_m3;
+    s.mu_m4 = mu_m2;
+    s.lambda_m4 = lambda_m2;
+  }
+  s.pibar1 = pibar3;                                                    // :539-540
+  s.pibar2 = pibar4;
+  s.breakdown = (beta_next <= s.btol && gamma_next <= s.btol) ? 1 : 0;  // :549
+  s.solved = (s.rNorm <= s.eps_tol || s.rNorm + 1.0 <= 1.0) ? 1 : 0;    // :544-550
+  s.iter = k;
+  return s.solved || s.breakdown;
+}
+
 __device__ __forceinline__ bool seq_skip(const long long *stop_seq, long long seq) {
   return stop_seq != nullptr && seq >= *stop_seq;
 }
@@ -1516,6 +1660,11 @@ __device__ inline void solver_epilogue(int epi, void *state, const double *v, lo
   } else if (epi == EPI_TRICG_B) {                 // v = (q.q, p.p)             :411-457
     TricgDevState *st = static_cast<TricgDevState *>(state);
     if (tricg_step_b(*st, v[0], v[1], st->iter + 1)) st->stop_seq = seq + 2;    // P3 of this iteration (seq + 1) still runs (:364-432)
+  } else if (epi == EPI_TRIMR_A) {                 // v[0] = v.q                 src/trimr.jl:312
+    trimr_step_a(*static_cast<TrimrDevState *>(state), v[0]);
+  } else if (epi == EPI_TRIMR_B) {                 // v = (q.q, p.p)             :321-551
+    TrimrDevState *st = static_cast<TrimrDevState *>(state);
+    if (trimr_step_b(*st, v[0], v[1], st->iter + 1)) st->stop_seq = seq + 2;    // P3 of this iteration (seq + 1) still runs (:446-516)
   }
 }
 
