@@ -215,7 +215,7 @@ int khip_profile_spmv(khip_ctx *ctx, int64_t *launches, double *total_ms);
  * (scale + Gram), 7 = halo pack kernel, 8 = halo transfer (grouped ncclSend / ncclRecv or the all-gather of x, bracketed on the
  * stream it runs on), 9 = a dot's 16-byte all-gather + combine kernel, 10 = the boundary rows' SpMV launch of a row-partitioned
  * product (tag 0 then is the interior launch), 11 / 12 / 13 = the fused passes P1, P2 and P3 of usymqr! (the pass's own kernel, without
- * the reduction's finish kernel), 14 = P3 of usymlq! (its P1 and P2 are 11 and 12), 15 = P3 of trilqr! (likewise), 16 = P3 of tricg! (likewise), 17 = P3 of trimr! (likewise); at most 18 families.  Synchronises the context's streams and resets every counter. */
+ * the reduction's finish kernel), 14 = P3 of usymlq! (its P1 and P2 are 11 and 12), 15 = P3 of trilqr! (likewise), 16 = P3 of tricg! (likewise), 17 = P3 of trimr! (likewise), 18 = P3 of usymlqr! (likewise); at most 19 families.  Synchronises the context's streams and resets every counter. */
 int khip_profile_kernels(khip_ctx *ctx, int ntags, int64_t *launches, double *total_ms);
 
 /* ------------------------------------------------ BLAS-1 shim ---------------- */
@@ -884,6 +884,56 @@ int khip_trimr_last_path(khip_trimr_workspace *ws);
  * "dx", "dy" (NULL while not allocated) */
 double           *khip_trimr_vector(khip_trimr_workspace *ws, const char *name);
 size_t            khip_trimr_workspace_bytes(khip_trimr_workspace *ws);   /* 8n + 8m doubles without warm start */
+
+/* ---- usymlqr! (src/usymlqr.jl:136-509), real Float64, no preconditioners: [I A; Aᴴ 0] [x; y] = [b; c] as the sum of the least-squares
+ * problem [b; 0] (USYMQR, when ls) and the least-norm problem [0; c] (USYMLQ, when ln) on ONE orthogonal tridiagonalisation and one
+ * QR factorisation; each side is frozen once its own test is met.  x and b have m entries, y and c have n: x is on the ROW side, as
+ * in tricg!.  UsymlqrWorkspace (src/krylov_workspaces.jl): r, x (m), y, z (n), vₖ₋₁, vₖ (m), uₖ₋₁, uₖ, p (n), q, d̅ (m), wₖ₋₂, wₖ₋₁ (n)
+ * ("r", "x", "y", "z", "v_prev", "v", "u_prev", "u", "p", "q", "dbar", "w_m2", "w_m1"); Δx ("dx", m doubles) and Δy ("dy", n doubles)
+ * stay empty until a warm start.  The adjoint travels as its own operator.  options.radius, linesearch, restart,
+ * reorthogonalization and variant are ignored; the reference's `ldiv` has no meaning without preconditioners.  β₁ = 0 gives v₁ = 0
+ * by a fill (likewise γ₁ and u₁), and so do βₖ₊₁ = 0 and γₖ₊₁ = 0 in the loop.  The fused loops rotate the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and
+ * (wₖ₋₂, wₖ₋₁) instead of copying or swapping, and khip_usymlqr_vector returns a name's pointer by its current role: after k
+ * iterations every name holds what the reference's variable of that name holds, in whichever buffer ("q" and "p" too: nothing
+ * divides them in place here).  As in the reference: stats.inconsistent is always 0, an `inconsistent` exit leaves the status
+ * "unknown", and βₖ₊₁ = 0 in an active least-squares step makes the r coefficient 0 / 0 (r, then x, become NaN).
+ * Out of scope: complex types, fused kernels for m != n, Float32. */
+typedef struct khip_usymlqr_workspace khip_usymlqr_workspace;
+typedef struct khip_usymlqr_params {
+  int ls, ln;                  /* solve the least-squares / the least-norm problem; defaults 1 and 1 (src/usymlqr.jl:117-118) */
+} khip_usymlqr_params;
+khip_usymlqr_params khip_usymlqr_default_params(void);   /* ls = ln = 1 */
+int khip_usymlqr_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_usymlqr_workspace **out);   /* m != n is allowed */
+/* UsymlqrWorkspace on the caller's thirteen vectors, in the reference's order; every pointer must be distinct.  adopt_vector names:
+ * "dx" and "dy" (Δx, Δy: warm_start! fills them on the caller's side and hands them over, then khip_usymlqr_warm_start(ws, dx, dy)
+ * only sets the flag) */
+int khip_usymlqr_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *r, double *x, double *y, double *z, double *v_prev, double *v,
+                                 double *u_prev, double *u, double *p, double *q, double *dbar, double *w_m2, double *w_m1,
+                                 khip_usymlqr_workspace **out);
+int khip_usymlqr_workspace_adopt_vector(khip_usymlqr_workspace *ws, const char *name, double *ptr);
+int khip_usymlqr_workspace_destroy(khip_usymlqr_workspace *ws);
+int khip_usymlqr_warm_start(khip_usymlqr_workspace *ws, const double *x0, const double *y0);   /* both are required: m and n doubles */
+/* usymlqr!(ws, A, b, c; ls, ln, atol, rtol, itmax, timemax, verbose, history, callback).  At = A' (n rows, m columns) and c (n
+ * doubles) are required (NULL: KHIP_ERR_INVALID); ls = ln = 0 is KHIP_ERR_INVALID with the reference's message; itmax = 0 means
+ * m + n of the global system; params = NULL means the defaults.  After a warm start the right-hand sides are b - Δx - AΔy and
+ * c - AᴴΔx.
+ * Loops (khip_usymlqr_last_path): 2 = device-resident (m = n, A and At CSR handles, no callback, verbose = 0), 1 = host-driven on
+ * the same kernels (same bits as 2), 0 = one launch per primitive (options.fused = 0).  A rectangular system (m != n) runs loop 0
+ * whatever options.fused says, and last_path reports 0; a row-partitioned rectangular handle is KHIP_ERR_UNSUPPORTED.
+ * stats: residuals holds, per iteration, ‖rₖ‖ of the least-squares side and then ‖rₖ‖ of the least-norm side, each while its side is
+ * active, and nothing for iteration 0; khip_usymlqr_aresiduals is ‖Aᴴrₖ₋₁‖ of the least-squares side. */
+int khip_usymlqr_solve(khip_usymlqr_workspace *ws, const khip_operator *A, const khip_operator *At, const double *b, const double *c,
+                       const khip_options *opts, const khip_usymlqr_params *params);
+double           *khip_usymlqr_solution_x(khip_usymlqr_workspace *ws);      /* m doubles */
+double           *khip_usymlqr_solution_y(khip_usymlqr_workspace *ws);      /* n doubles */
+const khip_stats *khip_usymlqr_stats(khip_usymlqr_workspace *ws);
+/* the Aresiduals history (valid until the next solve or destroy) */
+int khip_usymlqr_aresiduals(khip_usymlqr_workspace *ws, const double **aresiduals, int *naresiduals);
+int khip_usymlqr_last_path(khip_usymlqr_workspace *ws);
+/* named work vectors: "r", "x", "y", "z", "v_prev", "v", "u_prev", "u", "p", "q", "dbar", "w_m2", "w_m1", "dx", "dy" (NULL while not
+ * allocated) */
+double           *khip_usymlqr_vector(khip_usymlqr_workspace *ws, const char *name);
+size_t            khip_usymlqr_workspace_bytes(khip_usymlqr_workspace *ws);   /* 6m + 7n doubles without warm start */
 
 /* ---- cgs! (src/cgs.jl:126-281), real Float64: square nonsymmetric systems by the conjugate gradient squared recurrence; transpose-
  * free (no A'), two products with A per iteration.  CgsWorkspace (src/krylov_workspaces.jl): x, r, u, p, q, ts; Δx, yz and vw ("dx",

@@ -134,6 +134,15 @@ int khip_test_trimr_p3(khip_ctx *ctx, int64_t n, int stage, const double *coef16
 int khip_test_trimr_g(khip_ctx *ctx, int64_t n, double *out, const double *w, int nterm, const double *coef4, const double *a0,
                       const double *a1, const double *a2, const double *a3, double delta);
 
+/* test-only: the fused third pass of usymlqr! (csrc/usymlqr.cpp) at stage 1, 2 or 3 (= min(k, 3)) with the caller's activity flags,
+ * coefficients and device vectors (tests/test_gpu_usymlqr.py compares every output with the NumPy expression, bit for bit).
+ * coef14 (host) = -ϵₖ₋₂, -λₖ₋₁, δₖ, ϕₖ, the r coefficient -cₖϕbarₖ₊₁/βₖ₊₁, |sₖ|², ζₖ₋₁cₖ₋₁, ζₖ₋₁sₖ₋₁, -ζₖ₋₁, -cₖ₋₁, sₖ₋₁, βₖ₊₁, γₖ₊₁, 1 / δₖ.  w_m2 / w_m1: the
+ * buffers of the roles wₖ₋₂ / wₖ₋₁ as the iteration begins: stage 1 writes wₖ into w_m1, stages 2 and 3 into w_m2.  v_next / u_next
+ * take vₖ₊₁ / uₖ₊₁.  All vectors have n entries. */
+int khip_test_usymlqr_p3(khip_ctx *ctx, int64_t n, int stage, int do_ls, int do_ln, const double *coef14, double *x, double *r, double *dbar,
+                         double *y, double *z, double *w_m2, double *w_m1, const double *v, const double *u, const double *q,
+                         const double *p, double *v_next, double *u_next);
+
 #ifdef __cplusplus
 }
 #endif

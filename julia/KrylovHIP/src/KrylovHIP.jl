@@ -955,6 +955,70 @@ function Krylov.trimr!(ws::TrimrWs, A::HIPCsr, b::HIPVector, c::HIPVector; M = I
   return ws
 end
 
+# ------------------------------------------------------------------------------------------------ usymlqr!  (src/usymlqr.jl:136-509)
+struct UsymlqrParams               # khip_usymlqr_params: ls, ln
+  ls::Cint
+  ln::Cint
+end
+const UsymlqrWs = UsymlqrWorkspace{Float64,Float64,HIPVector,HIPVector}
+function usymlqr_handle(ws::UsymlqrWs)
+  get!(HANDLES, ws) do
+    r = Ref{Ptr{Cvoid}}()
+    ck(ccall((:khip_usymlqr_workspace_adopt, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                                                         Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                                                         Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Ptr{Cvoid}}),
+             CTX[].h, ws.m, ws.n, ws.r.ptr, ws.x.ptr, ws.y.ptr, ws.z.ptr, ws.vₖ₋₁.ptr, ws.vₖ.ptr, ws.uₖ₋₁.ptr, ws.uₖ.ptr, ws.p.ptr, ws.q.ptr, ws.d̅.ptr, ws.wₖ₋₂.ptr, ws.wₖ₋₁.ptr, r))
+    h = r[]
+    finalizer(_ -> ccall((:khip_usymlqr_workspace_destroy, lib), Cint, (Ptr{Cvoid},), h), ws)
+    h
+  end
+end
+usymlqr_adopt(h, name, v::HIPVector) = ck(ccall((:khip_usymlqr_workspace_adopt_vector, lib), Cint, (Ptr{Cvoid}, Cstring, Ptr{Cdouble}), h, name, dptr(v)))
+
+# A has m rows and n columns; b and x have m entries, c and y have n.  The adjoint is `A'`, built once per matrix and cached in
+# `A.adj`.  `ldiv` has no meaning without preconditioners and is dropped.  A rectangular system runs the library's primitive
+# sequence (LAST_PATH[] == 0) whatever `fused` says.  After the solve only ws.x, ws.y and ws.stats are defined: the library rotates
+# the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and (wₖ₋₂, wₖ₋₁) among the adopted vectors.
+function Krylov.usymlqr!(ws::UsymlqrWs, A::HIPCsr, b::HIPVector, c::HIPVector; ls::Bool = true, ln::Bool = true, ldiv::Bool = false,
+                         atol::Float64 = √eps(Float64), rtol::Float64 = √eps(Float64), itmax::Int = 0, timemax::Float64 = Inf,
+                         verbose::Int = 0, history::Bool = false, callback = nothing, iostream::IO = Krylov.kstdout, fused::Int = 2)
+  if !native_log(verbose, iostream)
+    GENERIC_SOLVES[] += 1
+    return invoke(Krylov.usymlqr!, Tuple{UsymlqrWs,Any,AbstractVector{Float64},AbstractVector{Float64}}, ws, A, b, c; ls, ln, ldiv, atol,
+                  rtol, itmax, timemax, verbose, history, callback = callback === nothing ? (w -> false) : callback, iostream)
+  end
+  m, n = size(A)                                                                            # :141-145
+  (m == ws.m && n == ws.n) || error("(workspace.m, workspace.n) = ($(ws.m), $(ws.n)) is inconsistent with size(A) = ($m, $n)")
+  length(b) == m || error("Inconsistent problem size")
+  length(c) == n || error("Inconsistent problem size")
+  (ls || ln) || error("The keyword arguments `ls` and `ln` can't be both `false`.")
+  At = A'
+  h = usymlqr_handle(ws)
+  for (name, v) in (("dx", ws.Δx), ("dy", ws.Δy))
+    usymlqr_adopt(h, name, v)
+  end
+  ws.warm_start && ck(ccall((:khip_usymlqr_warm_start, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), h, ws.Δx.ptr, ws.Δy.ptr))
+  stp = ccall((:khip_usymlqr_stats, lib), Ptr{Stats}, (Ptr{Cvoid},), h)
+  cbf, cbd, box = callback_args(user_callback(callback), ws, stp, history)
+  opts = Ref(Options(; atol, rtol, itmax, timemax, history, fused, verbose, log_fd = logfd(iostream), callback = cbf, callback_data = cbd))
+  prm = Ref(UsymlqrParams(Cint(ls), Cint(ln)))
+  opA = Ref(Operator(A));  opAt = Ref(Operator(At))
+  rc = GC.@preserve ws A At b c opts prm opA opAt box ccall((:khip_usymlqr_solve, lib), Cint,
+         (Ptr{Cvoid}, Ref{Operator}, Ref{Operator}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Options}, Ptr{Cvoid}),
+         h, opA, opAt, b.ptr, c.ptr, opts, prm)
+  st = fill_stats!(ws.stats, stp, history)
+  if history                                                                                # stats.Aresiduals
+    ar, nar = Ref{Ptr{Cvoid}}(), Ref{Cint}(0)
+    ck(ccall((:khip_usymlqr_aresiduals, lib), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Cint}), h, ar, nar))
+    nar[] > 0 && append!(ws.stats.Aresiduals, unsafe_wrap(Array, Ptr{Float64}(ar[]), Int(nar[])))
+  end
+  NATIVE_SOLVES[] += 1;  LAST_PATH[] = ccall((:khip_usymlqr_last_path, lib), Cint, (Ptr{Cvoid},), h)
+  ws.warm_start = false
+  finish_callback(box)
+  rc == 0 || failed(st)
+  return ws
+end
+
 # ------------------------------------------------------------------------------------------------ cgs!  (src/cgs.jl:126-281)
 const CgsWs = CgsWorkspace{Float64,Float64,HIPVector}
 function cgs_handle(ws::CgsWs)

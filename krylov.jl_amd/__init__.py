@@ -99,6 +99,10 @@ class CTrimrParams(C.Structure):
     _fields_ = [("tau", C.c_double), ("nu", C.c_double), ("spd", C.c_int), ("snd", C.c_int), ("flip", C.c_int), ("sp", C.c_int)]
 
 
+class CUsymlqrParams(C.Structure):
+    _fields_ = [("ls", C.c_int), ("ln", C.c_int)]
+
+
 class CStats(C.Structure):
     _fields_ = [("niter", C.c_int), ("solved", C.c_int), ("inconsistent", C.c_int), ("indefinite", C.c_int),
                 ("npcCount", C.c_int), ("timer", C.c_double), ("status", C.c_char * 96),
@@ -377,6 +381,22 @@ SIGNATURES = {
     "khip_trimr_workspace_bytes": (_sz, [_vp]),
     "khip_test_trimr_p3": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "khip_test_trimr_g": (_int, [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, C.c_double]),
+    "khip_usymlqr_default_params": (CUsymlqrParams, []),
+    "khip_usymlqr_workspace_create": (_int, [_vp, _i64, _i64, c_void_pp]),
+    "khip_usymlqr_workspace_adopt": (_int, [_vp, _i64, _i64] + [_vp] * 13 + [c_void_pp]),
+    "khip_usymlqr_workspace_adopt_vector": (_int, [_vp, C.c_char_p, _vp]),
+    "khip_usymlqr_workspace_destroy": (_int, [_vp]),
+    "khip_usymlqr_warm_start": (_int, [_vp, _vp, _vp]),
+    "khip_usymlqr_solve": (_int, [_vp, C.POINTER(COperator), C.POINTER(COperator), _vp, _vp, C.POINTER(COptions),
+                                  C.POINTER(CUsymlqrParams)]),
+    "khip_usymlqr_solution_x": (_vp, [_vp]),
+    "khip_usymlqr_solution_y": (_vp, [_vp]),
+    "khip_usymlqr_stats": (C.POINTER(CStats), [_vp]),
+    "khip_usymlqr_aresiduals": (_int, [_vp, C.POINTER(c_double_p), C.POINTER(_int)]),
+    "khip_usymlqr_last_path": (_int, [_vp]),
+    "khip_usymlqr_vector": (_vp, [_vp, C.c_char_p]),
+    "khip_usymlqr_workspace_bytes": (_sz, [_vp]),
+    "khip_test_usymlqr_p3": (_int, [_vp, _i64, _int, _int, _int] + [_vp] * 14),
     "khip_cgs_workspace_create": (_int, [_vp, _i64, _i64, c_void_pp]),
     "khip_cgs_workspace_adopt": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, c_void_pp]),
     "khip_cgs_workspace_adopt_vector": (_int, [_vp, C.c_char_p, _vp]),
@@ -604,11 +624,11 @@ class Context:
                     "usymlq_p3")
     # the families added since: PROFILE_TAGS keeps the length its tests pin (tests/test_usymlq_host.py), profile_kernels reports
     # PROFILE_FAMILIES
-    PROFILE_FAMILIES = PROFILE_TAGS + ("trilqr_p3", "tricg_p3", "trimr_p3")
+    PROFILE_FAMILIES = PROFILE_TAGS + ("trilqr_p3", "tricg_p3", "trimr_p3", "usymlqr_p3")
 
     def profile_kernels(self):
         """{family: (launches, total_ms)} of the HIP-event brackets recorded since the last call (option profile_spmv = 1):
-        khip_profile_kernels -- SpMV, SpMM, the panel kernels of block_gmres! and the fused passes of usymqr!, usymlq!, trilqr!, tricg! and trimr!."""
+        khip_profile_kernels -- SpMV, SpMM, the panel kernels of block_gmres! and the fused passes of usymqr!, usymlq!, trilqr!, tricg!, trimr! and usymlqr!."""
         k = len(self.PROFILE_FAMILIES)
         n, ms = (C.c_int64 * k)(), (C.c_double * k)()
         _ck(lib().khip_profile_kernels(self._h, k, n, ms))
@@ -2064,6 +2084,79 @@ class TrimrWorkspace(_Workspace):
         return self
 
 
+class UsymlqrWorkspace(_Workspace):
+    """UsymlqrWorkspace(m, n, Sm, Sn) (src/krylov_workspaces.jl): r, x of m entries, y, z of n, vₖ₋₁, vₖ of m, uₖ₋₁, uₖ, p of n, q, d̅ of m
+    and wₖ₋₂, wₖ₋₁ of n; Δx ("dx", m) and Δy ("dy", n) stay empty until a warm start.  x is on the ROW side (m entries), as in tricg!.
+    stats carries Aresiduals.  The fused loops rotate the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and (wₖ₋₂, wₖ₋₁), and `vector(name)` follows the role
+    (khip_usymlqr_vector): after k iterations a name holds what the reference's variable of that name holds.  A rectangular system
+    (m ≠ n) runs the primitive sequence whatever `fused` says: `last_path` reports 0."""
+    _prefix = "usymlqr"
+    VECTORS = ("r", "x", "y", "z", "v_prev", "v", "u_prev", "u", "p", "q", "dbar", "w_m2", "w_m1")
+    ROW_SIDE = ("r", "x", "v_prev", "v", "q", "dbar", "dx")                             # m entries; every other vector has n
+    SOLUTIONS = ("x", "y")
+
+    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
+        self.ctx, self.m, self.n = ctx, m, n
+        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
+        self._h = C.c_void_p()
+        if self.adopted:
+            t0 = time.perf_counter()
+            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(self._len(k)) for k in self.VECTORS}   # dx, dy stay empty
+            self._alloc_s = time.perf_counter() - t0
+            _ck(lib().khip_usymlqr_workspace_adopt(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
+        else:
+            _ck(lib().khip_usymlqr_workspace_create(ctx._h, m, n, C.byref(self._h)))
+
+    def _len(self, name: str) -> int:
+        return self.m if name in self.ROW_SIDE else self.n
+
+    @property
+    def x(self) -> DeviceVector:
+        if self.adopted:
+            return self._vec["x"]
+        return DeviceVector(self.ctx, self.m, ptr=lib().khip_usymlqr_solution_x(self._h), owner=self)
+
+    @property
+    def y(self) -> DeviceVector:
+        if self.adopted:
+            return self._vec["y"]
+        return DeviceVector(self.ctx, self.n, ptr=lib().khip_usymlqr_solution_y(self._h), owner=self)
+
+    @property
+    def stats(self) -> SimpleStats:
+        st = super().stats
+        ar, nar = c_double_p(), _int()
+        _ck(lib().khip_usymlqr_aresiduals(self._h, C.byref(ar), C.byref(nar)))
+        st.Aresiduals = np.array(ar[:nar.value]) if nar.value else np.zeros(0)
+        return st
+
+    def vector(self, name: str):
+        if name in self.SOLUTIONS:
+            return getattr(self, name)
+        p = lib().khip_usymlqr_vector(self._h, name.encode())
+        return DeviceVector(self.ctx, self._len(name), ptr=p, owner=self) if p else None
+
+    def warm_start_(self, x0: DeviceVector, y0: DeviceVector | None = None):
+        """warm_start!(workspace, x0, y0) (src/workspace_accessors.jl): Δx (m) and Δy (n) are allocated on first need; both are
+        required."""
+        if y0 is None or x0 is None:
+            raise KhipError(-1, "usymlqr: warm_start needs x0 and y0")
+        if len(x0) != self.m or len(y0) != self.n:
+            raise KhipError(-1, "Inconsistent problem size")
+        if self.adopted:
+            for name, src in (("dx", x0), ("dy", y0)):
+                if name not in self._vec:
+                    t0 = time.perf_counter()
+                    v = self.ctx.empty(self._len(name))
+                    self._alloc_s += time.perf_counter() - t0
+                    self._adopt_vector(name, v)
+                kcopy_(self._len(name), self._vec[name], src)
+            _ck(lib().khip_usymlqr_warm_start(self._h, self._vec["dx"].ptr, self._vec["dy"].ptr))    # same pointers: only the flag
+        else:
+            _ck(lib().khip_usymlqr_warm_start(self._h, _p(x0), _p(y0)))
+        return self
+
+
 class CgsWorkspace(_BiLanczosWorkspace):
     """CgsWorkspace(m, n, S) (src/krylov_workspaces.jl): x, r, u, p, q, ts; Δx, yz, vw stay empty until needed.  cgs! rotates no
     roles: every name keeps its buffer."""
@@ -2524,6 +2617,32 @@ def trimr_(ws: TrimrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None
     return _finish(ws, rc)
 
 
+def usymlqr_(ws: UsymlqrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, ls=True, ln=True, ldiv=False, **kw):
+    """usymlqr!(workspace, A, b, c; ls, ln, ldiv, atol, rtol, itmax, timemax, verbose, history, callback, iostream)
+    (src/usymlqr.jl:136-509): [I A; Aᴴ 0] [x; y] = [b; c] for A of m rows and n columns, b of m entries and c of n, as the sum of a
+    least-squares problem (ls) and a least-norm problem (ln).  `ldiv` is accepted and ignored (there are no preconditioners).
+    At: the adjoint of A (default: A.transpose(), built once and kept on A); a matrix-free A is callable(x[n], y[m]) and brings
+    At = callable(x[m], y[n]).  Returns the workspace."""
+    keep = []
+    if c is None:
+        raise KhipError(-1, "usymlqr: c (the second right-hand side) is required")
+    if len(b) != ws.m or len(c) != ws.n:
+        raise KhipError(-1, "Inconsistent problem size")
+    if At is None:
+        At = _adjoint_of(A, solver="usymlqr")
+    opts = _make_options(keep=keep, ws=ws, **kw)
+    prm = lib().khip_usymlqr_default_params()
+    prm.ls, prm.ln = int(bool(ls)), int(bool(ln))
+
+    def operator(op, nin, nout):
+        if op is None or isinstance(op, CsrMatrix):
+            return _make_operator(ws.ctx, op, nin, keep)
+        return _make_operator_mn(ws.ctx, op, nin, nout, keep)
+    rc = lib().khip_usymlqr_solve(ws._h, operator(A, ws.n, ws.m), operator(At, ws.m, ws.n), _p(b), _p(c), C.byref(opts),
+                                  C.byref(prm))
+    return _finish(ws, rc)
+
+
 def bilqr_(ws: BilqrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, transfer_to_bicg=True, **kw):
     """bilqr!(workspace, A, b, c; transfer_to_bicg, atol, rtol, itmax, timemax, verbose, history, callback, iostream)
     (src/bilqr.jl:116-484): x of A x = b by BiLQ and y of A' y = c by QMR from one two-sided Lanczos process.  At: the adjoint of A
@@ -2591,6 +2710,8 @@ FORWARDED_DEFAULTS = {
                   timemax=math.inf, verbose=0, history=False, callback=default_callback, iostream=None),
     "trimr": dict(M=None, N=None, ldiv=False, spd=False, snd=False, flip=False, sp=False, τ=1.0, ν=-1.0, atol=_SQRT_EPS, rtol=_SQRT_EPS,
                   itmax=0, timemax=math.inf, verbose=0, history=False, callback=default_callback, iostream=None),
+    "usymlqr": dict(ls=True, ln=True, ldiv=False, atol=_SQRT_EPS, rtol=_SQRT_EPS, itmax=0, timemax=math.inf, verbose=0, history=False,
+                    callback=default_callback, iostream=None),
 }
 WORKSPACE_KWARGS = {"gmres": dict(memory=20), "block_gmres": dict(memory=5)}      # kwargs_workspace_gmres, _block_gmres
 # kwargs_workspace_minres (src/minres.jl:159): kept apart from WORKSPACE_KWARGS, whose contents tests/test_abi.py pins
@@ -2619,8 +2740,8 @@ def krylov_workspace(method: str, *args, ctx: Context | None = None, **kw):
            "qmr": QmrWorkspace, "bilqr": BilqrWorkspace, "cgs": CgsWorkspace,
            "symmlq": SymmlqWorkspace, "minres_qlp": MinresQlpWorkspace, "usymqr": UsymqrWorkspace,
            "usymlq": UsymlqWorkspace, "trilqr": TrilqrWorkspace, "tricg": TricgWorkspace,
-           "trimr": TrimrWorkspace}[method]
-    if method in ("usymqr", "usymlq", "trilqr", "tricg", "trimr") and len(args) == 3:                                   # (A, b, c): m = length(b), n = length(c)
+           "trimr": TrimrWorkspace, "usymlqr": UsymlqrWorkspace}[method]
+    if method in ("usymqr", "usymlq", "trilqr", "tricg", "trimr", "usymlqr") and len(args) == 3:                                   # (A, b, c): m = length(b), n = length(c)
         A, b, c = args
         return cls(b.ctx, len(b), len(c), **kw)
     if method == "cg_lanczos_shift":                                            # (A, b, nshifts) / (m, n, nshifts)
@@ -2658,7 +2779,7 @@ def krylov_solve_(ws, A, b, x0=None, **kw):
     elapsed = 0.0
     if x0 is not None:
         t0 = time.perf_counter()
-        if method in ("tricg", "trimr"):                                                   # krylov_solve!(ws, A, b, c, x0, y0; kwargs...)
+        if method in ("tricg", "trimr", "usymlqr"):                                        # krylov_solve!(ws, A, b, c, x0, y0; kwargs...)
             ws.warm_start_(x0, full.pop("y0", None))
         else:
             ws.warm_start_(x0)
@@ -2688,14 +2809,14 @@ def krylov_solve(method: str, A, b, x0=None, ctx: Context | None = None, **kw):
         ctx = ctx or A.ctx
         ws = krylov_workspace(method, A, B, ctx=ctx, **wkw)
         b = ctx.array(np.asfortranarray(B).ravel(order="F"))
-    elif method in ("usymqr", "usymlq", "tricg", "trimr"):         # krylov_solve(Val(:usymqr), A, b, c[, x0]; kwargs...): c travels as a keyword here
+    elif method in ("usymqr", "usymlq", "tricg", "trimr", "usymlqr"):         # krylov_solve(Val(:usymqr), A, b, c[, x0]; kwargs...): c travels as a keyword here
         if kw.get("c") is None:
             raise KhipError(-1, f"{method}: c (the starting vector of the second Krylov space) is required")
         ws = krylov_workspace(method, A, b, kw["c"], **wkw)
     else:
         ws = krylov_workspace(method, A, b, **wkw)
     if x0 is not None:
-        if method in ("tricg", "trimr"):
+        if method in ("tricg", "trimr", "usymlqr"):
             ws.warm_start_(x0, kw.pop("y0", None))
         else:
             ws.warm_start_(x0)
@@ -2704,7 +2825,7 @@ def krylov_solve(method: str, A, b, x0=None, ctx: Context | None = None, **kw):
     full["timemax"] = full["timemax"] - elapsed
     _INPLACE[type(ws)][1](ws, A, b, **full)
     ws._timer_extra = elapsed
-    if method in ("tricg", "trimr"):
+    if method in ("tricg", "trimr", "usymlqr"):
         return ws.x, ws.y, ws.stats, ws
     return (ws.X if method == "block_gmres" else ws.x), ws.stats, ws
 
@@ -2822,6 +2943,22 @@ def trimr(A, b: DeviceVector, c: DeviceVector, x0=None, y0=None, **kw):
     full = _forward("trimr", kw)
     full["timemax"] = full["timemax"] - elapsed
     trimr_(ws, A, b, c, **full)
+    ws._timer_extra = elapsed
+    return ws.x, ws.y, ws.stats, ws
+
+
+def usymlqr(A, b: DeviceVector, c: DeviceVector, x0=None, y0=None, **kw):
+    """Out-of-place usymlqr(A, b, c[, x0, y0]; kwargs...) -> (x, y, stats, workspace) (src/usymlqr.jl:20-32); A' is taken once and kept
+    on A.  The workspace's creation and the warm start are charged to `timemax` and `stats.timer`, as krylov_solve does."""
+    wkw = {k: kw.pop(k) for k in list(kw) if k in ("adopt", "vectors")}
+    t0 = time.perf_counter()
+    ws = UsymlqrWorkspace(b.ctx, len(b), len(c), **wkw)
+    if x0 is not None or y0 is not None:
+        ws.warm_start_(x0, y0)
+    elapsed = time.perf_counter() - t0
+    full = _forward("usymlqr", kw)
+    full["timemax"] = full["timemax"] - elapsed
+    usymlqr_(ws, A, b, c, **full)
     ws._timer_extra = elapsed
     return ws.x, ws.y, ws.stats, ws
 
@@ -3283,6 +3420,7 @@ _INPLACE.update({CgWorkspace: ("cg", cg_), GmresWorkspace: ("gmres", gmres_), Bi
                  TrilqrWorkspace: ("trilqr", trilqr_),
                  TricgWorkspace: ("tricg", tricg_),
                  TrimrWorkspace: ("trimr", trimr_),
+                 UsymlqrWorkspace: ("usymlqr", usymlqr_),
                  SymmlqWorkspace: ("symmlq", symmlq_),
                  MinresQlpWorkspace: ("minres_qlp", minres_qlp_),
                  BilqrWorkspace: ("bilqr", bilqr_),

@@ -11,7 +11,7 @@ BUILD="${KHIP_BUILD_DIR:-$HERE/build}"
 mkdir -p "$BUILD"
 objs=""
 pids=""
-for f in blas1.hip spmv.hip csr_aux.hip spmm_tile.hip panel.hip ilu.hip template.hip colcode.hip coldelta.hip comm.cpp gen_irregular.cpp api.cpp solvers.cpp minres.cpp lanczos_shift.cpp bilq.cpp qmr.cpp bilqr.cpp usymqr.cpp usymlq.cpp trilqr.cpp tricg.cpp trimr.cpp cgs.cpp symmlq.cpp minres_qlp.cpp block.cpp processes.cpp; do
+for f in blas1.hip spmv.hip csr_aux.hip spmm_tile.hip panel.hip ilu.hip template.hip colcode.hip coldelta.hip comm.cpp gen_irregular.cpp api.cpp solvers.cpp minres.cpp lanczos_shift.cpp bilq.cpp qmr.cpp bilqr.cpp usymqr.cpp usymlq.cpp trilqr.cpp tricg.cpp trimr.cpp usymlqr.cpp cgs.cpp symmlq.cpp minres_qlp.cpp block.cpp processes.cpp; do
   [ -f "$SRC/$f" ] || continue
   o="$BUILD/${f%.*}.o"
   # spmm_tile.hip: the device assembly is kept beside the object (-save-temps=obj, a by-product of the same compile) --

@@ -511,7 +511,8 @@ enum ProfTag { kProfSpmv = 0, kProfSpmm = 1, kProfPanelTn = 2, kProfPanelNnTn = 
                kProfTrilqrP3 = 15,      // P3 of trilqr! (trilqr.cpp); its P1 and P2 are the two Ssy brackets
                kProfTricgP3 = 16,       // P3 of tricg! (tricg.cpp); its P1 and P2 are the two Ssy brackets
                kProfTrimrP3 = 17,       // P3 of trimr! (trimr.cpp); its P1 and P2 are the two Ssy brackets
-               kProfTags = 18 };
+               kProfUsymlqrP3 = 18,     // P3 of usymlqr! (usymlqr.cpp); its P1 and P2 are the two Ssy brackets
+               kProfTags = 19 };
 struct ProfScope {
   khip_ctx *ctx;
   hipEvent_t stop = nullptr;

@@ -21,7 +21,7 @@ enum Epilogue { EPI_NONE = 0, EPI_CG_STEP1 = 1, EPI_CG_STEP2 = 2, EPI_BICG_A = 3
                EPI_SYMMLQ_A = 23, EPI_SYMMLQ_B = 24, EPI_MINRES_QLP_X = 25, EPI_MINRES_QLP_A = 26, EPI_MINRES_QLP_B = 27,
                EPI_USYMQR_A = 28, EPI_USYMQR_B = 29, EPI_USYMLQ_A = 30, EPI_USYMLQ_B = 31,
                EPI_TRILQR_A = 32, EPI_TRILQR_B = 33, EPI_TRICG_A = 34, EPI_TRICG_B = 35,
-               EPI_TRIMR_A = 36, EPI_TRIMR_B = 37 };
+               EPI_TRIMR_A = 36, EPI_TRIMR_B = 37, EPI_USYMLQR_A = 38, EPI_USYMLQR_B = 39 };
 
 struct CgDevState {
   double gamma;        // r.z of the current iterate              (src/cg.jl:162, 257)
@@ -1488,6 +1488,134 @@ __host__ __device__ inline bool trimr_step_b(TrimrDevState &s, double qq, double
   return s.solved || s.breakdown;
 }
 
+// usymlqr! (src/usymlqr.jl:136-509), real Float64: [I A; Aᴴ 0] [x; y] = [b; c] as the sum of the least-squares problem [b; 0]
+// (USYMQR: y and the residual r) and the least-norm problem [0; c] (USYMLQ: x and z), both on ONE orthogonal tridiagonalisation and
+// ONE QR factorisation of Tₖ₊₁.ₖ.  As for its siblings, the same two steps run on the host (loops 0 and 1) and as the epilogues of
+// the two reductions of an iteration.  Each side is frozen once it is solved; the factorisation, wₖ and the shifts go on.  Both
+// tests belong to P2's epilogue, which runs BEFORE P3: do_ls / do_ln keep for P3 which sides were active when the iteration began.
+struct UsymlqrDevState : SsyCoef {
+  // coefficients the vector kernels read (γₖ, βₖ, αₖ: SsyCoef)
+  double beta_next, gamma_next;  // βₖ₊₁, γₖ₊₁: the divisors of P3               (src/usymlqr.jl:270-271, :441-455)
+  double neg_eps, neg_lambda;    // -ϵₖ₋₂, -λₖ₋₁: kscal! and the first kaxpy! of wₖ (:321, :327, :329)
+  double delta, inv_delta;       // δₖ: kdivcopy!(w₁, u₁, δ₁) (:316); one(T) / δₖ: kdiv!(wₖ, δₖ) = kscal!(one(T) / δₖ) (:323, :331)
+  double phi;                    // ϕₖ: y = y + ϕₖ wₖ                             (:345)
+  double r_coef, s2;             // -cₖ ϕbarₖ₊₁ / βₖ₊₁ and |sₖ|²: the kaxpby! of r   (:350)
+  double zc, zs, neg_zeta;       // ζₖ₋₁cₖ₋₁, ζₖ₋₁sₖ₋₁, -ζₖ₋₁: the x and z updates   (:410-415)
+  double neg_c, sn;              // -cₖ₋₁, sₖ₋₁: the kaxpby! of d̅                 (:419)
+  // constants of the solve
+  double eps_ls, eps_ln;         // ε_ls = atol + rtol β₁, ε_ln = atol + rtol γ₁ (:227-228)
+  double kappa, atol, rtol;      // κ = atol + rtol ‖Aᴴr₀‖, known after iteration 1 of an active least-squares side (:365)
+  double cNorm;                  // γ₁: rNorm_ln of iteration 1                  (:425)
+  // recurrences
+  double c_km2, c_km1, s_km2, s_km1;   // cₖ₋₂, cₖ₋₁, sₖ₋₂, sₖ₋₁
+  double epsilon, lambda;        // ϵₖ₋₂, λₖ₋₁
+  double dbar;                   // δbarₖ
+  double delta_km1;              // δₖ₋₁
+  double phibar;                 // ϕbarₖ
+  double zeta_m2, zeta_m1;       // ζₖ₋₂, ζₖ₋₁
+  double eta_prev;               // ηₖ₋₁
+  double rNorm_ls, rNorm_ln, ArNorm;
+  long long stop_seq, iter, hist_base, hist_cap;
+  long long nhist_ls, nhist_ln;  // the last iteration that pushed to a side's history: each side stops when it is solved
+  double *hist_ls, *hist_ln, *hist_ar;   // device history windows (null: no history); ‖Aᴴrₖ₋₁‖ follows the least-squares side
+  int ls, ln;                    // the keyword arguments
+  int do_ls, do_ln;              // the sides that were active when this iteration began: what P3 updates
+  int solved_ls, solved_ln, inconsistent;
+};
+
+// after αₖ = ⟨vₖ, q⟩ (:260)
+__host__ __device__ inline void usymlqr_step_a(UsymlqrDevState &s, double vq) { s.alpha = vq; }
+
+// after ‖q‖² and ‖p‖²: βₖ₊₁, γₖ₊₁, the two previous reflections and the new one (:270-310) and the coefficients of wₖ always; ϕ, the
+// r coefficient, the two norms, κ at k = 1 and the tests of an active least-squares side (:334-367); ζ, η, the residual norm and the
+// test of an active least-norm side (:369-438); the shifts always (:462-471); k = iter.  True when the loop stops (tired /
+// overtimed / the callback are the driver's).  P3 of this iteration still runs: the reference updates wₖ, y, r, x, z, d̅, vₖ₊₁ and
+// uₖ₊₁ before it tests.  The r coefficient is formed as the reference writes it, (-cₖ ϕbarₖ₊₁) / βₖ₊₁: 0 / 0 when βₖ₊₁ = 0.
+__host__ __device__ inline bool usymlqr_step_b(UsymlqrDevState &s, double qq, double pp, long long k) {
+  s.beta_next = sqrt(qq);
+  s.gamma_next = sqrt(pp);
+  double lbar = 0.0;             // λbarₖ₋₁
+  if (k >= 3) {
+    s.epsilon = s.s_km2 * s.gamma;
+    lbar = -s.c_km2 * s.gamma;
+  }
+  if (k >= 2) {
+    if (k == 2) lbar = s.gamma;
+    s.lambda = s.c_km1 * lbar + s.s_km1 * s.alpha;
+    s.dbar = s.s_km1 * lbar - s.c_km1 * s.alpha;
+  } else {
+    s.dbar = s.alpha;
+  }
+  double c, sn;
+  sym_givens(s.dbar, s.beta_next, c, sn, s.delta);
+  s.neg_eps = -s.epsilon;
+  s.neg_lambda = -s.lambda;
+  s.inv_delta = 1.0 / s.delta;
+  s.do_ls = (s.ls && !s.solved_ls) ? 1 : 0;
+  s.do_ln = (s.ln && !s.solved_ln) ? 1 : 0;
+  if (s.do_ls) {
+    s.phi = c * s.phibar;
+    const double phibar_next = sn * s.phibar;
+    s.r_coef = -c * phibar_next / s.beta_next;
+    s.s2 = sn * sn;
+    s.rNorm_ls = fabs(phibar_next);
+    const double cg = s.c_km1 * s.gamma_next;                  // cₖ₋₁ of before the shift, γₖ₊₁ of this iteration (:357)
+    s.ArNorm = fabs(s.phibar) * sqrt(s.dbar * s.dbar + cg * cg);
+    if (s.hist_ls) {
+      const long long idx = k - 1 - s.hist_base;
+      if (idx >= 0 && idx < s.hist_cap) { s.hist_ls[idx] = s.rNorm_ls; s.hist_ar[idx] = s.ArNorm; }
+    }
+    s.nhist_ls = k;
+    s.phibar = phibar_next;
+    s.solved_ls = (s.rNorm_ls <= s.eps_ls) ? 1 : 0;
+    if (k == 1) s.kappa = s.atol + s.rtol * s.ArNorm;
+    s.inconsistent = (!s.solved_ls && s.ArNorm <= s.kappa) ? 1 : 0;
+  }
+  if (s.do_ln) {
+    double eta = 0.0;            // ηₖ
+    if (k == 1) eta = s.gamma;
+    if (k == 2) {
+      s.zeta_m1 = s.eta_prev / s.delta_km1;
+      eta = -s.lambda * s.zeta_m1;
+    }
+    if (k >= 3) {
+      s.zeta_m2 = s.zeta_m1;
+      s.zeta_m1 = s.eta_prev / s.delta_km1;
+      eta = -s.epsilon * s.zeta_m2 - s.lambda * s.zeta_m1;
+    }
+    s.zc = s.zeta_m1 * s.c_km1;
+    s.zs = s.zeta_m1 * s.s_km1;
+    s.neg_zeta = -s.zeta_m1;
+    s.neg_c = -s.c_km1;
+    s.sn = s.s_km1;
+    if (k == 1) {
+      s.rNorm_ln = s.cNorm;
+    } else {
+      const double mu = s.gamma * (s.s_km2 * s.zeta_m2 - s.c_km2 * s.c_km1 * s.zeta_m1) + s.alpha * s.s_km1 * s.zeta_m1;
+      const double omega = s.gamma_next * s.s_km1 * s.zeta_m1;
+      s.rNorm_ln = sqrt(mu * mu + omega * omega);
+    }
+    if (s.hist_ln) {
+      const long long idx = k - 1 - s.hist_base;
+      if (idx >= 0 && idx < s.hist_cap) s.hist_ln[idx] = s.rNorm_ln;
+    }
+    s.nhist_ln = k;
+    s.eta_prev = eta;
+    s.solved_ln = (s.rNorm_ln <= s.eps_ln) ? 1 : 0;
+  }
+  if (k >= 2) {
+    s.s_km2 = s.s_km1;
+    s.c_km2 = s.c_km1;
+  }
+  s.s_km1 = sn;
+  s.c_km1 = c;
+  s.delta_km1 = s.delta;
+  s.gamma = s.gamma_next;        // P3 divides by gamma_next and beta_next; the next P1 reads gamma and beta
+  s.beta = s.beta_next;
+  s.iter = k;
+  return (s.solved_ls && s.solved_ln) || s.inconsistent;
+}
+
 __device__ __forceinline__ bool seq_skip(const long long *stop_seq, long long seq) {
   return stop_seq != nullptr && seq >= *stop_seq;
 }
@@ -1665,6 +1793,11 @@ __device__ inline void solver_epilogue(int epi, void *state, const double *v, lo
   } else if (epi == EPI_TRIMR_B) {                 // v = (q.q, p.p)             :321-551
     TrimrDevState *st = static_cast<TrimrDevState *>(state);
     if (trimr_step_b(*st, v[0], v[1], st->iter + 1)) st->stop_seq = seq + 2;    // P3 of this iteration (seq + 1) still runs (:446-516)
+  } else if (epi == EPI_USYMLQR_A) {               // v[0] = v.q                 src/usymlqr.jl:260
+    usymlqr_step_a(*static_cast<UsymlqrDevState *>(state), v[0]);
+  } else if (epi == EPI_USYMLQR_B) {               // v = (q.q, p.p)             :270-471
+    UsymlqrDevState *st = static_cast<UsymlqrDevState *>(state);
+    if (usymlqr_step_b(*st, v[0], v[1], st->iter + 1)) st->stop_seq = seq + 2;  // P3 of this iteration (seq + 1) still runs (:312-455)
   }
 }
 

@@ -257,6 +257,11 @@ void set_history(TrilqrDevState &s, double *w) {
   s.hist_p = w;
   s.hist_d = w ? w + kHistWindowMax : nullptr;
 }
+void set_history(UsymlqrDevState &s, double *w) {
+  s.hist_ls = w;
+  s.hist_ln = w ? w + kHistWindowMax : nullptr;
+  s.hist_ar = w ? w + 2 * kHistWindowMax : nullptr;
+}
 
 // entries of column c of a history row (cg_lanczos_shift!: each shift's history is a prefix) or of stream c (bilqr!, trilqr!: each side's
 // history ends with the iteration that solved it) that belong to a state's history
@@ -264,6 +269,7 @@ template <class S> long long hist_rows(const S &, int) { return std::numeric_lim
 long long hist_rows(const LanczosShiftDevState &s, int c) { return s.nhist[c]; }
 long long hist_rows(const BilqrDevState &s, int c) { return c == 0 ? s.nhist_p : s.nhist_d; }
 long long hist_rows(const TrilqrDevState &s, int c) { return c == 0 ? s.nhist_p : s.nhist_d; }
+long long hist_rows(const UsymlqrDevState &s, int c) { return c == 1 ? s.nhist_ln : s.nhist_ls; }   // ‖Aᴴrₖ₋₁‖ (2) ends with ‖rₖ‖_LS (0)
 
 struct DeviceLoopArgs {
   int64_t itmax;
@@ -285,6 +291,7 @@ struct DeviceLoop {
   S *dev = nullptr;
   S *pinned = nullptr;
   double *hist = nullptr;                // history windows, kHistWindowMax entries per stream (allocated with history only)
+  std::vector<double> *third_stream = nullptr;   // a third history stream of a solver whose driver names two (usymlqr! on Ssy<P>)
   hipEvent_t snap_ev[2] = {nullptr, nullptr};
 
   void release() {                       // khip_*_workspace_destroy
@@ -313,8 +320,10 @@ struct DeviceLoop {
   // (*overtimed) is reached.  step(dev, j) enqueues iteration j (0-based); before_snapshot() runs after the last step of each
   // chunk.  On return the final state is in *out and its history in the caller's vectors.
   template <class Step, class Hook>
-  int run(khip_ctx *ctx, S h, const DeviceLoopArgs &a, Step &&step, Hook &&before_snapshot, S *out, bool *overtimed) {
+  int run(khip_ctx *ctx, S h, const DeviceLoopArgs &args, Step &&step, Hook &&before_snapshot, S *out, bool *overtimed) {
     KHIP_TRY(alloc());
+    DeviceLoopArgs a = args;
+    if (third_stream && !a.columns && a.drain_to[1] && !a.drain_to[2]) a.drain_to[2] = third_stream;
     int streams = 0;
     while (streams < 3 && a.drain_to[streams]) ++streams;
     if (a.columns) streams = 1;
