@@ -1495,11 +1495,15 @@ class _Workspace:
         _ck(self._fn("workspace_adopt_vector")(self._h, name.encode(), v.ptr))
         return v
 
+    def _len(self, name: str) -> int:
+        """Entries of the vector `name`: n, but for the row side of a _TwoSidedWorkspace."""
+        return self.n
+
     def _allocate_if(self, cond: bool, name: str):
         """src/krylov_utils.jl:281-288: allocate the lazily-held vector `name` on first need."""
         if cond and self.adopted and name not in self._vec:
             t0 = time.perf_counter()
-            v = self.ctx.empty(self.n)
+            v = self.ctx.empty(self._len(name))
             self._alloc_s += time.perf_counter() - t0            # stats.allocation_timer counts the lazy allocations too
             self._adopt_vector(name, v)
 
@@ -1804,7 +1808,85 @@ class QmrWorkspace(_BiLanczosWorkspace):
     VECTORS = ("u_prev", "u", "q", "v_prev", "v", "p", "x", "w_prev2", "w_prev")
 
 
-class UsymqrWorkspace(_Workspace):
+class _TwoSidedWorkspace(_Workspace):
+    """What the workspaces of the solvers on the Saunders-Simon-Yip process share (usymqr!, usymlq!, trilqr!, tricg!, trimr!, usymlqr!):
+    A has m rows and n columns, so a vector has m entries where its name is in ROW_SIDE and n otherwise (`_len`).  VECTORS come with
+    the workspace (caller-owned: `vectors=` or fresh ones, handed to khip_*_workspace_adopt in that order; library-owned with
+    adopt=False); Δx ("dx") and, with SOLUTIONS == ("x", "y"), Δy ("dy") stay empty until a warm start.  `vector(name)` follows the
+    roles the fused loops rotate (khip_*_vector)."""
+    VECTORS = ()
+    ROW_SIDE = ()
+    SOLUTIONS = ("x",)
+    ARESIDUALS = False                                    # stats carries the Aresiduals history (khip_*_aresiduals)
+
+    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
+        self.ctx, self.m, self.n = ctx, m, n
+        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
+        self._h = C.c_void_p()
+        if self.adopted:
+            t0 = time.perf_counter()
+            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(self._len(k)) for k in self.VECTORS}
+            self._alloc_s = time.perf_counter() - t0
+            _ck(self._fn("workspace_adopt")(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
+        else:
+            _ck(self._fn("workspace_create")(ctx._h, m, n, C.byref(self._h)))
+
+    def _len(self, name: str) -> int:
+        return self.m if name in self.ROW_SIDE else self.n
+
+    def _solution(self, name: str) -> DeviceVector:
+        if self.adopted:
+            return self._vec[name]
+        fn = "solution" if self.SOLUTIONS == ("x",) else "solution_" + name
+        return DeviceVector(self.ctx, self._len(name), ptr=self._fn(fn)(self._h), owner=self)
+
+    @property
+    def x(self) -> DeviceVector:
+        return self._solution("x")
+
+    @property
+    def y(self) -> DeviceVector:
+        if "y" not in self.SOLUTIONS:
+            raise AttributeError("y")
+        return self._solution("y")
+
+    @property
+    def stats(self) -> SimpleStats:
+        st = super().stats
+        if self.ARESIDUALS:
+            ar, nar = c_double_p(), _int()
+            _ck(self._fn("aresiduals")(self._h, C.byref(ar), C.byref(nar)))
+            st.Aresiduals = np.array(ar[:nar.value]) if nar.value else np.zeros(0)
+        return st
+
+    def vector(self, name: str):
+        if name in self.SOLUTIONS:
+            return getattr(self, name)
+        p = self._fn("vector")(self._h, name.encode())
+        return DeviceVector(self.ctx, self._len(name), ptr=p, owner=self) if p else None
+
+    def warm_start_(self, x0: DeviceVector, y0: DeviceVector | None = None):
+        """warm_start!(workspace, x0[, y0]) (src/workspace_accessors.jl).  With SOLUTIONS == ("x", "y") both are required, each of
+        the length of its Δ: a wrong length is refused before anything is copied."""
+        if "y" not in self.SOLUTIONS:
+            if y0 is not None:
+                raise TypeError(f"{self._prefix}: warm_start_ takes x0 alone")
+            return super().warm_start_(x0)
+        if y0 is None or x0 is None:
+            raise KhipError(-1, f"{self._prefix}: warm_start needs x0 and y0")
+        if len(x0) != self._len("dx") or len(y0) != self._len("dy"):
+            raise KhipError(-1, "Inconsistent problem size")
+        if self.adopted:
+            for name, src in (("dx", x0), ("dy", y0)):
+                self._allocate_if(True, name)
+                kcopy_(self._len(name), self._vec[name], src)
+            _ck(self._fn("warm_start")(self._h, self._vec["dx"].ptr, self._vec["dy"].ptr))     # same pointers: only the flag
+        else:
+            _ck(self._fn("warm_start")(self._h, _p(x0), _p(y0)))
+        return self
+
+
+class UsymqrWorkspace(_TwoSidedWorkspace):
     """UsymqrWorkspace(m, n, Sm, Sn) (src/krylov_workspaces.jl): vₖ₋₁, vₖ, q of m entries and x, wₖ₋₂, wₖ₋₁, uₖ₋₁, uₖ, p of n; Δx ("dx")
     stays empty until a warm start.  stats carries Aresiduals.  The fused loops rotate the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and
     (wₖ₋₂, wₖ₋₁), and `vector(name)` follows the role (khip_usymqr_vector): after k iterations a name holds what the reference's
@@ -1813,38 +1895,10 @@ class UsymqrWorkspace(_Workspace):
     _prefix = "usymqr"
     VECTORS = ("v_prev", "v", "q", "x", "w_prev2", "w_prev", "u_prev", "u", "p")
     ROW_SIDE = ("v_prev", "v", "q")                                             # m entries; every other vector has n
-
-    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
-        self.ctx, self.m, self.n = ctx, m, n
-        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
-        self._h = C.c_void_p()
-        if self.adopted:
-            t0 = time.perf_counter()
-            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(self._len(k)) for k in self.VECTORS}   # dx stays empty
-            self._alloc_s = time.perf_counter() - t0
-            _ck(lib().khip_usymqr_workspace_adopt(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
-        else:
-            _ck(lib().khip_usymqr_workspace_create(ctx._h, m, n, C.byref(self._h)))
-
-    def _len(self, name: str) -> int:
-        return self.m if name in self.ROW_SIDE else self.n
-
-    @property
-    def stats(self) -> SimpleStats:
-        st = super().stats
-        ar, nar = c_double_p(), _int()
-        _ck(lib().khip_usymqr_aresiduals(self._h, C.byref(ar), C.byref(nar)))
-        st.Aresiduals = np.array(ar[:nar.value]) if nar.value else np.zeros(0)
-        return st
-
-    def vector(self, name: str):
-        if name == "x":
-            return self.x
-        p = lib().khip_usymqr_vector(self._h, name.encode())
-        return DeviceVector(self.ctx, self._len(name), ptr=p, owner=self) if p else None
+    ARESIDUALS = True
 
 
-class UsymlqWorkspace(_Workspace):
+class UsymlqWorkspace(_TwoSidedWorkspace):
     """UsymlqWorkspace(m, n, Sm, Sn) (src/krylov_workspaces.jl): uₖ₋₁, uₖ, p, x, d̅ of n entries and vₖ₋₁, vₖ, q of m; Δx ("dx") stays
     empty until a warm start.  The fused loops rotate the roles of (vₖ₋₁, vₖ) and (uₖ₋₁, uₖ), and `vector(name)` follows the role
     (khip_usymlq_vector): after k iterations a name holds what the reference's variable of that name holds ("dbar" = d̅ₖ).  A
@@ -1853,29 +1907,8 @@ class UsymlqWorkspace(_Workspace):
     VECTORS = ("u_prev", "u", "p", "x", "dbar", "v_prev", "v", "q")
     ROW_SIDE = ("v_prev", "v", "q")                                             # m entries; every other vector has n
 
-    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
-        self.ctx, self.m, self.n = ctx, m, n
-        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
-        self._h = C.c_void_p()
-        if self.adopted:
-            t0 = time.perf_counter()
-            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(self._len(k)) for k in self.VECTORS}   # dx stays empty
-            self._alloc_s = time.perf_counter() - t0
-            _ck(lib().khip_usymlq_workspace_adopt(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
-        else:
-            _ck(lib().khip_usymlq_workspace_create(ctx._h, m, n, C.byref(self._h)))
 
-    def _len(self, name: str) -> int:
-        return self.m if name in self.ROW_SIDE else self.n
-
-    def vector(self, name: str):
-        if name == "x":
-            return self.x
-        p = lib().khip_usymlq_vector(self._h, name.encode())
-        return DeviceVector(self.ctx, self._len(name), ptr=p, owner=self) if p else None
-
-
-class TrilqrWorkspace(_Workspace):
+class TrilqrWorkspace(_TwoSidedWorkspace):
     """TrilqrWorkspace(m, n, Sm, Sn) (src/krylov_workspaces.jl): uₖ₋₁, uₖ, p, d̅, x of n entries and vₖ₋₁, vₖ, q, t ("y"), wₖ₋₃, wₖ₋₂ of m;
     Δx ("dx", n) and Δy ("dy", m) stay empty until a warm start.  stats is an AdjointStats, with `inconsistent` (the dual side's flag)
     beside the reference's fields.  The fused loops rotate the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and (wₖ₋₃, wₖ₋₂), and `vector(name)`
@@ -1885,33 +1918,6 @@ class TrilqrWorkspace(_Workspace):
     VECTORS = ("u_prev", "u", "p", "dbar", "x", "v_prev", "v", "q", "y", "w_prev3", "w_prev2")
     ROW_SIDE = ("v_prev", "v", "q", "y", "w_prev3", "w_prev2", "dy")            # m entries; every other vector has n
     SOLUTIONS = ("x", "y")
-
-    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
-        self.ctx, self.m, self.n = ctx, m, n
-        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
-        self._h = C.c_void_p()
-        if self.adopted:
-            t0 = time.perf_counter()
-            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(self._len(k)) for k in self.VECTORS}   # dx, dy stay empty
-            self._alloc_s = time.perf_counter() - t0
-            _ck(lib().khip_trilqr_workspace_adopt(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
-        else:
-            _ck(lib().khip_trilqr_workspace_create(ctx._h, m, n, C.byref(self._h)))
-
-    def _len(self, name: str) -> int:
-        return self.m if name in self.ROW_SIDE else self.n
-
-    @property
-    def x(self) -> DeviceVector:
-        if self.adopted:
-            return self._vec["x"]
-        return DeviceVector(self.ctx, self.n, ptr=lib().khip_trilqr_solution_x(self._h), owner=self)
-
-    @property
-    def y(self) -> DeviceVector:
-        if self.adopted:
-            return self._vec["y"]
-        return DeviceVector(self.ctx, self.m, ptr=lib().khip_trilqr_solution_y(self._h), owner=self)
 
     @property
     def stats(self) -> AdjointStats:
@@ -1927,32 +1933,8 @@ class TrilqrWorkspace(_Workspace):
         st.timer += getattr(self, "_timer_extra", 0.0)
         return st
 
-    def vector(self, name: str):
-        if name in self.SOLUTIONS:
-            return getattr(self, name)
-        p = lib().khip_trilqr_vector(self._h, name.encode())
-        return DeviceVector(self.ctx, self._len(name), ptr=p, owner=self) if p else None
 
-    def warm_start_(self, x0: DeviceVector, y0: DeviceVector | None = None):
-        """warm_start!(workspace, x0, y0) (src/workspace_accessors.jl): Δx (n) and Δy (m) are allocated on first need; both are
-        required."""
-        if y0 is None or x0 is None:
-            raise KhipError(-1, "trilqr: warm_start needs x0 and y0")
-        if self.adopted:
-            for name, src in (("dx", x0), ("dy", y0)):
-                if name not in self._vec:
-                    t0 = time.perf_counter()
-                    v = self.ctx.empty(self._len(name))
-                    self._alloc_s += time.perf_counter() - t0
-                    self._adopt_vector(name, v)
-                kcopy_(self._len(name), self._vec[name], src)
-            _ck(lib().khip_trilqr_warm_start(self._h, self._vec["dx"].ptr, self._vec["dy"].ptr))     # same pointers: only the flag
-        else:
-            _ck(lib().khip_trilqr_warm_start(self._h, _p(x0), _p(y0)))
-        return self
-
-
-class TricgWorkspace(_Workspace):
+class TricgWorkspace(_TwoSidedWorkspace):
     """TricgWorkspace(m, n, Sm, Sn) (src/krylov_workspaces.jl), M = N = I: y, uₖ₋₁, uₖ, p, gy₂ₖ₋₁, gy₂ₖ of n entries and x, vₖ₋₁, vₖ, q,
     gx₂ₖ₋₁, gx₂ₖ of m; Δx ("dx", m) and Δy ("dy", n) stay empty until a warm start.  x is on the ROW side (m entries), unlike in
     usymqr!, usymlq! and trilqr!.  The fused loops rotate the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ), (gx₂ₖ₋₁, gx₂ₖ) and (gy₂ₖ₋₁, gy₂ₖ), and
@@ -1964,61 +1946,8 @@ class TricgWorkspace(_Workspace):
     ROW_SIDE = ("x", "v_prev", "v", "q", "gx_prev", "gx", "dx")                 # m entries; every other vector has n
     SOLUTIONS = ("x", "y")
 
-    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
-        self.ctx, self.m, self.n = ctx, m, n
-        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
-        self._h = C.c_void_p()
-        if self.adopted:
-            t0 = time.perf_counter()
-            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(self._len(k)) for k in self.VECTORS}   # dx, dy stay empty
-            self._alloc_s = time.perf_counter() - t0
-            _ck(lib().khip_tricg_workspace_adopt(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
-        else:
-            _ck(lib().khip_tricg_workspace_create(ctx._h, m, n, C.byref(self._h)))
 
-    def _len(self, name: str) -> int:
-        return self.m if name in self.ROW_SIDE else self.n
-
-    @property
-    def x(self) -> DeviceVector:
-        if self.adopted:
-            return self._vec["x"]
-        return DeviceVector(self.ctx, self.m, ptr=lib().khip_tricg_solution_x(self._h), owner=self)
-
-    @property
-    def y(self) -> DeviceVector:
-        if self.adopted:
-            return self._vec["y"]
-        return DeviceVector(self.ctx, self.n, ptr=lib().khip_tricg_solution_y(self._h), owner=self)
-
-    def vector(self, name: str):
-        if name in self.SOLUTIONS:
-            return getattr(self, name)
-        p = lib().khip_tricg_vector(self._h, name.encode())
-        return DeviceVector(self.ctx, self._len(name), ptr=p, owner=self) if p else None
-
-    def warm_start_(self, x0: DeviceVector, y0: DeviceVector | None = None):
-        """warm_start!(workspace, x0, y0) (src/workspace_accessors.jl): Δx (m) and Δy (n) are allocated on first need; both are
-        required."""
-        if y0 is None or x0 is None:
-            raise KhipError(-1, "tricg: warm_start needs x0 and y0")
-        if len(x0) != self.m or len(y0) != self.n:
-            raise KhipError(-1, "Inconsistent problem size")
-        if self.adopted:
-            for name, src in (("dx", x0), ("dy", y0)):
-                if name not in self._vec:
-                    t0 = time.perf_counter()
-                    v = self.ctx.empty(self._len(name))
-                    self._alloc_s += time.perf_counter() - t0
-                    self._adopt_vector(name, v)
-                kcopy_(self._len(name), self._vec[name], src)
-            _ck(lib().khip_tricg_warm_start(self._h, self._vec["dx"].ptr, self._vec["dy"].ptr))      # same pointers: only the flag
-        else:
-            _ck(lib().khip_tricg_warm_start(self._h, _p(x0), _p(y0)))
-        return self
-
-
-class TrimrWorkspace(_Workspace):
+class TrimrWorkspace(_TwoSidedWorkspace):
     """TrimrWorkspace(m, n, Sm, Sn) (src/krylov_workspaces.jl), M = N = I: y, uₖ₋₁, uₖ, p, gy₂ₖ₋₃, gy₂ₖ₋₂, gy₂ₖ₋₁, gy₂ₖ of n entries and x, vₖ₋₁,
     vₖ, q, gx₂ₖ₋₃, gx₂ₖ₋₂, gx₂ₖ₋₁, gx₂ₖ of m; Δx ("dx", m) and Δy ("dy", n) stay empty until a warm start.  x is on the ROW side (m
     entries), as in tricg!.  The fused loops rotate the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and of the older and the newer pair of g of each
@@ -2030,61 +1959,8 @@ class TrimrWorkspace(_Workspace):
     ROW_SIDE = ("x", "v_prev", "v", "q", "gx_m3", "gx_m2", "gx_m1", "gx", "dx")                 # m entries; every other vector has n
     SOLUTIONS = ("x", "y")
 
-    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
-        self.ctx, self.m, self.n = ctx, m, n
-        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
-        self._h = C.c_void_p()
-        if self.adopted:
-            t0 = time.perf_counter()
-            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(self._len(k)) for k in self.VECTORS}   # dx, dy stay empty
-            self._alloc_s = time.perf_counter() - t0
-            _ck(lib().khip_trimr_workspace_adopt(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
-        else:
-            _ck(lib().khip_trimr_workspace_create(ctx._h, m, n, C.byref(self._h)))
 
-    def _len(self, name: str) -> int:
-        return self.m if name in self.ROW_SIDE else self.n
-
-    @property
-    def x(self) -> DeviceVector:
-        if self.adopted:
-            return self._vec["x"]
-        return DeviceVector(self.ctx, self.m, ptr=lib().khip_trimr_solution_x(self._h), owner=self)
-
-    @property
-    def y(self) -> DeviceVector:
-        if self.adopted:
-            return self._vec["y"]
-        return DeviceVector(self.ctx, self.n, ptr=lib().khip_trimr_solution_y(self._h), owner=self)
-
-    def vector(self, name: str):
-        if name in self.SOLUTIONS:
-            return getattr(self, name)
-        p = lib().khip_trimr_vector(self._h, name.encode())
-        return DeviceVector(self.ctx, self._len(name), ptr=p, owner=self) if p else None
-
-    def warm_start_(self, x0: DeviceVector, y0: DeviceVector | None = None):
-        """warm_start!(workspace, x0, y0) (src/workspace_accessors.jl): Δx (m) and Δy (n) are allocated on first need; both are
-        required."""
-        if y0 is None or x0 is None:
-            raise KhipError(-1, "trimr: warm_start needs x0 and y0")
-        if len(x0) != self.m or len(y0) != self.n:
-            raise KhipError(-1, "Inconsistent problem size")
-        if self.adopted:
-            for name, src in (("dx", x0), ("dy", y0)):
-                if name not in self._vec:
-                    t0 = time.perf_counter()
-                    v = self.ctx.empty(self._len(name))
-                    self._alloc_s += time.perf_counter() - t0
-                    self._adopt_vector(name, v)
-                kcopy_(self._len(name), self._vec[name], src)
-            _ck(lib().khip_trimr_warm_start(self._h, self._vec["dx"].ptr, self._vec["dy"].ptr))      # same pointers: only the flag
-        else:
-            _ck(lib().khip_trimr_warm_start(self._h, _p(x0), _p(y0)))
-        return self
-
-
-class UsymlqrWorkspace(_Workspace):
+class UsymlqrWorkspace(_TwoSidedWorkspace):
     """UsymlqrWorkspace(m, n, Sm, Sn) (src/krylov_workspaces.jl): r, x of m entries, y, z of n, vₖ₋₁, vₖ of m, uₖ₋₁, uₖ, p of n, q, d̅ of m
     and wₖ₋₂, wₖ₋₁ of n; Δx ("dx", m) and Δy ("dy", n) stay empty until a warm start.  x is on the ROW side (m entries), as in tricg!.
     stats carries Aresiduals.  The fused loops rotate the roles of (vₖ₋₁, vₖ), (uₖ₋₁, uₖ) and (wₖ₋₂, wₖ₋₁), and `vector(name)` follows the role
@@ -2094,67 +1970,7 @@ class UsymlqrWorkspace(_Workspace):
     VECTORS = ("r", "x", "y", "z", "v_prev", "v", "u_prev", "u", "p", "q", "dbar", "w_m2", "w_m1")
     ROW_SIDE = ("r", "x", "v_prev", "v", "q", "dbar", "dx")                             # m entries; every other vector has n
     SOLUTIONS = ("x", "y")
-
-    def __init__(self, ctx: Context, m: int, n: int, adopt: bool | None = None, vectors=None):
-        self.ctx, self.m, self.n = ctx, m, n
-        self.adopted = vectors is not None or (_adopt_default() if adopt is None else bool(adopt))
-        self._h = C.c_void_p()
-        if self.adopted:
-            t0 = time.perf_counter()
-            self._vec = dict(vectors) if vectors is not None else {k: ctx.empty(self._len(k)) for k in self.VECTORS}   # dx, dy stay empty
-            self._alloc_s = time.perf_counter() - t0
-            _ck(lib().khip_usymlqr_workspace_adopt(ctx._h, m, n, *[self._vec[k].ptr for k in self.VECTORS], C.byref(self._h)))
-        else:
-            _ck(lib().khip_usymlqr_workspace_create(ctx._h, m, n, C.byref(self._h)))
-
-    def _len(self, name: str) -> int:
-        return self.m if name in self.ROW_SIDE else self.n
-
-    @property
-    def x(self) -> DeviceVector:
-        if self.adopted:
-            return self._vec["x"]
-        return DeviceVector(self.ctx, self.m, ptr=lib().khip_usymlqr_solution_x(self._h), owner=self)
-
-    @property
-    def y(self) -> DeviceVector:
-        if self.adopted:
-            return self._vec["y"]
-        return DeviceVector(self.ctx, self.n, ptr=lib().khip_usymlqr_solution_y(self._h), owner=self)
-
-    @property
-    def stats(self) -> SimpleStats:
-        st = super().stats
-        ar, nar = c_double_p(), _int()
-        _ck(lib().khip_usymlqr_aresiduals(self._h, C.byref(ar), C.byref(nar)))
-        st.Aresiduals = np.array(ar[:nar.value]) if nar.value else np.zeros(0)
-        return st
-
-    def vector(self, name: str):
-        if name in self.SOLUTIONS:
-            return getattr(self, name)
-        p = lib().khip_usymlqr_vector(self._h, name.encode())
-        return DeviceVector(self.ctx, self._len(name), ptr=p, owner=self) if p else None
-
-    def warm_start_(self, x0: DeviceVector, y0: DeviceVector | None = None):
-        """warm_start!(workspace, x0, y0) (src/workspace_accessors.jl): Δx (m) and Δy (n) are allocated on first need; both are
-        required."""
-        if y0 is None or x0 is None:
-            raise KhipError(-1, "usymlqr: warm_start needs x0 and y0")
-        if len(x0) != self.m or len(y0) != self.n:
-            raise KhipError(-1, "Inconsistent problem size")
-        if self.adopted:
-            for name, src in (("dx", x0), ("dy", y0)):
-                if name not in self._vec:
-                    t0 = time.perf_counter()
-                    v = self.ctx.empty(self._len(name))
-                    self._alloc_s += time.perf_counter() - t0
-                    self._adopt_vector(name, v)
-                kcopy_(self._len(name), self._vec[name], src)
-            _ck(lib().khip_usymlqr_warm_start(self._h, self._vec["dx"].ptr, self._vec["dy"].ptr))    # same pointers: only the flag
-        else:
-            _ck(lib().khip_usymlqr_warm_start(self._h, _p(x0), _p(y0)))
-        return self
+    ARESIDUALS = True
 
 
 class CgsWorkspace(_BiLanczosWorkspace):
@@ -2489,49 +2305,43 @@ def qmr_(ws: QmrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, M=
     return _bilq_qmr_solve(ws, lib().khip_qmr_default_params(), A, b, c, M, N, At, Mt, Nt, kw)
 
 
-def usymqr_(ws: UsymqrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, **kw):
-    """usymqr!(workspace, A, b, c; atol, rtol, itmax, timemax, verbose, history, callback, iostream) (src/usymqr.jl:130-365) for A of m
-    rows and n columns, b of m entries and c of n.  At: the adjoint of A (default: A.transpose(), built once and kept on A); a
-    matrix-free A is callable(x[n], y[m]) and brings At = callable(x[m], y[n]).  Returns the workspace."""
+def _ssy_solve(ws, A, b, c, At, opts_kw, prm=None, c_message="the starting vector of the second Krylov space"):
+    """What the six solvers on the Saunders-Simon-Yip process share: c is required (`c_message` says what it is), b has m entries
+    and c has n, At defaults to A.transpose(), a matrix-free operator is wrapped at its two lengths, and the call; `prm` is the
+    solver's params (usymqr! has none)."""
     keep = []
+    solver = ws._prefix
     if c is None:
-        raise KhipError(-1, "usymqr: c (the starting vector of the second Krylov space) is required")
+        raise KhipError(-1, f"{solver}: c ({c_message}) is required")
     if len(b) != ws.m or len(c) != ws.n:
         raise KhipError(-1, "Inconsistent problem size")
     if At is None:
-        At = _adjoint_of(A, solver="usymqr")
-    opts = _make_options(keep=keep, ws=ws, **kw)
+        At = _adjoint_of(A, solver=solver)
+    opts = _make_options(keep=keep, ws=ws, **opts_kw)
 
     def operator(op, nin, nout):
         if op is None or isinstance(op, CsrMatrix):
             return _make_operator(ws.ctx, op, nin, keep)
         return _make_operator_mn(ws.ctx, op, nin, nout, keep)
-    rc = lib().khip_usymqr_solve(ws._h, operator(A, ws.n, ws.m), operator(At, ws.m, ws.n), _p(b), _p(c), C.byref(opts))
+    params = () if prm is None else (C.byref(prm),)
+    rc = ws._fn("solve")(ws._h, operator(A, ws.n, ws.m), operator(At, ws.m, ws.n), _p(b), _p(c), C.byref(opts), *params)
     return _finish(ws, rc)
+
+
+def usymqr_(ws: UsymqrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, **kw):
+    """usymqr!(workspace, A, b, c; atol, rtol, itmax, timemax, verbose, history, callback, iostream) (src/usymqr.jl:130-365) for A of m
+    rows and n columns, b of m entries and c of n.  At: the adjoint of A (default: A.transpose(), built once and kept on A); a
+    matrix-free A is callable(x[n], y[m]) and brings At = callable(x[m], y[n]).  Returns the workspace."""
+    return _ssy_solve(ws, A, b, c, At, kw)
 
 
 def usymlq_(ws: UsymlqWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, transfer_to_usymcg=True, **kw):
     """usymlq!(workspace, A, b, c; transfer_to_usymcg, atol, rtol, itmax, timemax, verbose, history, callback, iostream)
     (src/usymlq.jl:124-366) for A of m rows and n columns, b of m entries and c of n.  At: the adjoint of A (default: A.transpose(),
     built once and kept on A); a matrix-free A is callable(x[n], y[m]) and brings At = callable(x[m], y[n]).  Returns the workspace."""
-    keep = []
-    if c is None:
-        raise KhipError(-1, "usymlq: c (the starting vector of the second Krylov space) is required")
-    if len(b) != ws.m or len(c) != ws.n:
-        raise KhipError(-1, "Inconsistent problem size")
-    if At is None:
-        At = _adjoint_of(A, solver="usymlq")
-    opts = _make_options(keep=keep, ws=ws, **kw)
     prm = lib().khip_usymlq_default_params()
     prm.transfer_to_usymcg = int(bool(transfer_to_usymcg))
-
-    def operator(op, nin, nout):
-        if op is None or isinstance(op, CsrMatrix):
-            return _make_operator(ws.ctx, op, nin, keep)
-        return _make_operator_mn(ws.ctx, op, nin, nout, keep)
-    rc = lib().khip_usymlq_solve(ws._h, operator(A, ws.n, ws.m), operator(At, ws.m, ws.n), _p(b), _p(c), C.byref(opts),
-                                 C.byref(prm))
-    return _finish(ws, rc)
+    return _ssy_solve(ws, A, b, c, At, kw, prm)
 
 
 def trilqr_(ws: TrilqrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, transfer_to_usymcg=True, **kw):
@@ -2539,24 +2349,9 @@ def trilqr_(ws: TrilqrWorkspace, A, b: DeviceVector, c: DeviceVector | None = No
     (src/trilqr.jl:115-460): x of A x = b by USYMLQ and t of Aᴴ t = c by USYMQR from one orthogonal tridiagonalisation, for A of m rows
     and n columns, b of m entries and c of n.  At: the adjoint of A (default: A.transpose(), built once and kept on A); a matrix-free
     A is callable(x[n], y[m]) and brings At = callable(x[m], y[n]).  Returns the workspace."""
-    keep = []
-    if c is None:
-        raise KhipError(-1, "trilqr: c (the right-hand side of the dual system) is required")
-    if len(b) != ws.m or len(c) != ws.n:
-        raise KhipError(-1, "Inconsistent problem size")
-    if At is None:
-        At = _adjoint_of(A, solver="trilqr")
-    opts = _make_options(keep=keep, ws=ws, **kw)
     prm = lib().khip_trilqr_default_params()
     prm.transfer_to_usymcg = int(bool(transfer_to_usymcg))
-
-    def operator(op, nin, nout):
-        if op is None or isinstance(op, CsrMatrix):
-            return _make_operator(ws.ctx, op, nin, keep)
-        return _make_operator_mn(ws.ctx, op, nin, nout, keep)
-    rc = lib().khip_trilqr_solve(ws._h, operator(A, ws.n, ws.m), operator(At, ws.m, ws.n), _p(b), _p(c), C.byref(opts),
-                                 C.byref(prm))
-    return _finish(ws, rc)
+    return _ssy_solve(ws, A, b, c, At, kw, prm, c_message="the right-hand side of the dual system")
 
 
 def tricg_(ws: TricgWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, τ=1.0, ν=-1.0, spd=False, snd=False,
@@ -2565,27 +2360,12 @@ def tricg_(ws: TricgWorkspace, A, b: DeviceVector, c: DeviceVector | None = None
     (src/tricg.jl:149-484): [τI A; Aᴴ νI] [x; y] = [b; c] for A of m rows and n columns, b of m entries and c of n; M = N = I only.
     At: the adjoint of A (default: A.transpose(), built once and kept on A); a matrix-free A is callable(x[n], y[m]) and brings
     At = callable(x[m], y[n]).  Returns the workspace."""
-    keep = []
-    if c is None:
-        raise KhipError(-1, "tricg: c (the second right-hand side) is required")
-    if M is not None or N is not None:
+    if c is not None and (M is not None or N is not None):                      # a missing c is reported first, by _ssy_solve
         raise KhipError(-5, "tricg: M and N other than I are not supported")
-    if len(b) != ws.m or len(c) != ws.n:
-        raise KhipError(-1, "Inconsistent problem size")
-    if At is None:
-        At = _adjoint_of(A, solver="tricg")
-    opts = _make_options(keep=keep, ws=ws, **kw)
     prm = lib().khip_tricg_default_params()
     prm.tau, prm.nu = float(τ), float(ν)
     prm.spd, prm.snd, prm.flip = int(bool(spd)), int(bool(snd)), int(bool(flip))
-
-    def operator(op, nin, nout):
-        if op is None or isinstance(op, CsrMatrix):
-            return _make_operator(ws.ctx, op, nin, keep)
-        return _make_operator_mn(ws.ctx, op, nin, nout, keep)
-    rc = lib().khip_tricg_solve(ws._h, operator(A, ws.n, ws.m), operator(At, ws.m, ws.n), _p(b), _p(c), C.byref(opts),
-                                C.byref(prm))
-    return _finish(ws, rc)
+    return _ssy_solve(ws, A, b, c, At, kw, prm, c_message="the second right-hand side")
 
 
 def trimr_(ws: TrimrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, τ=1.0, ν=-1.0, spd=False, snd=False,
@@ -2594,27 +2374,12 @@ def trimr_(ws: TrimrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None
     (src/trimr.jl:150-577): [τI A; Aᴴ νI] [x; y] = [b; c] for A of m rows and n columns, b of m entries and c of n; M = N = I only.
     At: the adjoint of A (default: A.transpose(), built once and kept on A); a matrix-free A is callable(x[n], y[m]) and brings
     At = callable(x[m], y[n]).  Returns the workspace."""
-    keep = []
-    if c is None:
-        raise KhipError(-1, "trimr: c (the second right-hand side) is required")
-    if M is not None or N is not None:
+    if c is not None and (M is not None or N is not None):                      # a missing c is reported first, by _ssy_solve
         raise KhipError(-5, "trimr: M and N other than I are not supported")
-    if len(b) != ws.m or len(c) != ws.n:
-        raise KhipError(-1, "Inconsistent problem size")
-    if At is None:
-        At = _adjoint_of(A, solver="trimr")
-    opts = _make_options(keep=keep, ws=ws, **kw)
     prm = lib().khip_trimr_default_params()
     prm.tau, prm.nu = float(τ), float(ν)
     prm.spd, prm.snd, prm.flip, prm.sp = int(bool(spd)), int(bool(snd)), int(bool(flip)), int(bool(sp))
-
-    def operator(op, nin, nout):
-        if op is None or isinstance(op, CsrMatrix):
-            return _make_operator(ws.ctx, op, nin, keep)
-        return _make_operator_mn(ws.ctx, op, nin, nout, keep)
-    rc = lib().khip_trimr_solve(ws._h, operator(A, ws.n, ws.m), operator(At, ws.m, ws.n), _p(b), _p(c), C.byref(opts),
-                                C.byref(prm))
-    return _finish(ws, rc)
+    return _ssy_solve(ws, A, b, c, At, kw, prm, c_message="the second right-hand side")
 
 
 def usymlqr_(ws: UsymlqrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, ls=True, ln=True, ldiv=False, **kw):
@@ -2623,24 +2388,9 @@ def usymlqr_(ws: UsymlqrWorkspace, A, b: DeviceVector, c: DeviceVector | None = 
     least-squares problem (ls) and a least-norm problem (ln).  `ldiv` is accepted and ignored (there are no preconditioners).
     At: the adjoint of A (default: A.transpose(), built once and kept on A); a matrix-free A is callable(x[n], y[m]) and brings
     At = callable(x[m], y[n]).  Returns the workspace."""
-    keep = []
-    if c is None:
-        raise KhipError(-1, "usymlqr: c (the second right-hand side) is required")
-    if len(b) != ws.m or len(c) != ws.n:
-        raise KhipError(-1, "Inconsistent problem size")
-    if At is None:
-        At = _adjoint_of(A, solver="usymlqr")
-    opts = _make_options(keep=keep, ws=ws, **kw)
     prm = lib().khip_usymlqr_default_params()
     prm.ls, prm.ln = int(bool(ls)), int(bool(ln))
-
-    def operator(op, nin, nout):
-        if op is None or isinstance(op, CsrMatrix):
-            return _make_operator(ws.ctx, op, nin, keep)
-        return _make_operator_mn(ws.ctx, op, nin, nout, keep)
-    rc = lib().khip_usymlqr_solve(ws._h, operator(A, ws.n, ws.m), operator(At, ws.m, ws.n), _p(b), _p(c), C.byref(opts),
-                                  C.byref(prm))
-    return _finish(ws, rc)
+    return _ssy_solve(ws, A, b, c, At, kw, prm, c_message="the second right-hand side")
 
 
 def bilqr_(ws: BilqrWorkspace, A, b: DeviceVector, c: DeviceVector | None = None, At=None, transfer_to_bicg=True, **kw):
@@ -2741,7 +2491,7 @@ def krylov_workspace(method: str, *args, ctx: Context | None = None, **kw):
            "symmlq": SymmlqWorkspace, "minres_qlp": MinresQlpWorkspace, "usymqr": UsymqrWorkspace,
            "usymlq": UsymlqWorkspace, "trilqr": TrilqrWorkspace, "tricg": TricgWorkspace,
            "trimr": TrimrWorkspace, "usymlqr": UsymlqrWorkspace}[method]
-    if method in ("usymqr", "usymlq", "trilqr", "tricg", "trimr", "usymlqr") and len(args) == 3:                                   # (A, b, c): m = length(b), n = length(c)
+    if method in _TAKES_C and len(args) == 3:                                    # (A, b, c): m = length(b), n = length(c)
         A, b, c = args
         return cls(b.ctx, len(b), len(c), **kw)
     if method == "cg_lanczos_shift":                                            # (A, b, nshifts) / (m, n, nshifts)
@@ -2764,6 +2514,8 @@ def krylov_workspace(method: str, *args, ctx: Context | None = None, **kw):
 
 
 _INPLACE = {}      # filled below: CgWorkspace -> ("cg", cg_), ...
+_TAKES_C = {"usymqr", "usymlq", "trilqr", "tricg", "trimr", "usymlqr"}          # krylov_solve(Val(method), A, b, c, ...): A is m x n
+_TAKES_X0_Y0 = {"tricg", "trimr", "usymlqr"}       # ... and krylov_solve takes (x0, y0) and returns (x, y, stats, workspace)
 
 
 def krylov_solve_(ws, A, b, x0=None, **kw):
@@ -2779,7 +2531,7 @@ def krylov_solve_(ws, A, b, x0=None, **kw):
     elapsed = 0.0
     if x0 is not None:
         t0 = time.perf_counter()
-        if method in ("tricg", "trimr", "usymlqr"):                                        # krylov_solve!(ws, A, b, c, x0, y0; kwargs...)
+        if method in _TAKES_X0_Y0:                                              # krylov_solve!(ws, A, b, c, x0, y0; kwargs...)
             ws.warm_start_(x0, full.pop("y0", None))
         else:
             ws.warm_start_(x0)
@@ -2809,14 +2561,14 @@ def krylov_solve(method: str, A, b, x0=None, ctx: Context | None = None, **kw):
         ctx = ctx or A.ctx
         ws = krylov_workspace(method, A, B, ctx=ctx, **wkw)
         b = ctx.array(np.asfortranarray(B).ravel(order="F"))
-    elif method in ("usymqr", "usymlq", "tricg", "trimr", "usymlqr"):         # krylov_solve(Val(:usymqr), A, b, c[, x0]; kwargs...): c travels as a keyword here
+    elif method in _TAKES_C:                           # krylov_solve(Val(:usymqr), A, b, c[, x0]; kwargs...): c travels as a keyword here
         if kw.get("c") is None:
             raise KhipError(-1, f"{method}: c (the starting vector of the second Krylov space) is required")
         ws = krylov_workspace(method, A, b, kw["c"], **wkw)
     else:
         ws = krylov_workspace(method, A, b, **wkw)
     if x0 is not None:
-        if method in ("tricg", "trimr", "usymlqr"):
+        if method in _TAKES_X0_Y0:
             ws.warm_start_(x0, kw.pop("y0", None))
         else:
             ws.warm_start_(x0)
@@ -2825,7 +2577,7 @@ def krylov_solve(method: str, A, b, x0=None, ctx: Context | None = None, **kw):
     full["timemax"] = full["timemax"] - elapsed
     _INPLACE[type(ws)][1](ws, A, b, **full)
     ws._timer_extra = elapsed
-    if method in ("tricg", "trimr", "usymlqr"):
+    if method in _TAKES_X0_Y0:
         return ws.x, ws.y, ws.stats, ws
     return (ws.X if method == "block_gmres" else ws.x), ws.stats, ws
 
@@ -2883,84 +2635,51 @@ def minres_qlp(A, b: DeviceVector, x0=None, **kw):
     return krylov_solve("minres_qlp", A, b, x0, **kw)
 
 
-def bilqr(A, b: DeviceVector, c: DeviceVector, x0=None, y0=None, **kw):
-    """Out-of-place bilqr(A, b, c[, x0, y0]; kwargs...) -> (x, y, stats, workspace) (src/bilqr.jl:16-26); A' is taken once and kept
-    on A.  The workspace's creation and the warm start are charged to `timemax` and `stats.timer`, as krylov_solve does."""
+def _solve_pair(method: str, WsClass, A, b, c, x0, y0, kw):
+    """Out-of-place method(A, b, c[, x0, y0]; kwargs...) -> (x, y, stats, workspace) of the solvers with two solutions.  The
+    workspace's creation and the warm start are charged to `timemax` and `stats.timer`, as krylov_solve does."""
     wkw = {k: kw.pop(k) for k in list(kw) if k in ("adopt", "vectors")}
     t0 = time.perf_counter()
-    ws = BilqrWorkspace(b.ctx, len(b), len(b), **wkw)
+    n = len(c) if issubclass(WsClass, _TwoSidedWorkspace) else len(b)           # bilqr! is square
+    ws = WsClass(b.ctx, len(b), n, **wkw)
     if x0 is not None or y0 is not None:
         ws.warm_start_(x0, y0)
     elapsed = time.perf_counter() - t0
-    full = _forward("bilqr", kw)
+    full = _forward(method, kw)
     full["timemax"] = full["timemax"] - elapsed
-    bilqr_(ws, A, b, c, **full)
+    _INPLACE[WsClass][1](ws, A, b, c, **full)
     ws._timer_extra = elapsed
     return ws.x, ws.y, ws.stats, ws
+
+
+def bilqr(A, b: DeviceVector, c: DeviceVector, x0=None, y0=None, **kw):
+    """Out-of-place bilqr(A, b, c[, x0, y0]; kwargs...) -> (x, y, stats, workspace) (src/bilqr.jl:16-26); A' is taken once and kept
+    on A.  The workspace's creation and the warm start are charged to `timemax` and `stats.timer`, as krylov_solve does."""
+    return _solve_pair("bilqr", BilqrWorkspace, A, b, c, x0, y0, kw)
 
 
 def trilqr(A, b: DeviceVector, c: DeviceVector, x0=None, y0=None, **kw):
     """Out-of-place trilqr(A, b, c[, x0, y0]; kwargs...) -> (x, t, stats, workspace) (src/trilqr.jl:16-26); A' is taken once and kept
     on A.  The workspace's creation and the warm start are charged to `timemax` and `stats.timer`, as krylov_solve does."""
-    wkw = {k: kw.pop(k) for k in list(kw) if k in ("adopt", "vectors")}
-    t0 = time.perf_counter()
-    ws = TrilqrWorkspace(b.ctx, len(b), len(c), **wkw)
-    if x0 is not None or y0 is not None:
-        ws.warm_start_(x0, y0)
-    elapsed = time.perf_counter() - t0
-    full = _forward("trilqr", kw)
-    full["timemax"] = full["timemax"] - elapsed
-    trilqr_(ws, A, b, c, **full)
-    ws._timer_extra = elapsed
-    return ws.x, ws.y, ws.stats, ws
+    return _solve_pair("trilqr", TrilqrWorkspace, A, b, c, x0, y0, kw)
 
 
 def tricg(A, b: DeviceVector, c: DeviceVector, x0=None, y0=None, **kw):
     """Out-of-place tricg(A, b, c[, x0, y0]; kwargs...) -> (x, y, stats, workspace) (src/tricg.jl:16-33); A' is taken once and kept on
     A.  The workspace's creation and the warm start are charged to `timemax` and `stats.timer`, as krylov_solve does."""
-    wkw = {k: kw.pop(k) for k in list(kw) if k in ("adopt", "vectors")}
-    t0 = time.perf_counter()
-    ws = TricgWorkspace(b.ctx, len(b), len(c), **wkw)
-    if x0 is not None or y0 is not None:
-        ws.warm_start_(x0, y0)
-    elapsed = time.perf_counter() - t0
-    full = _forward("tricg", kw)
-    full["timemax"] = full["timemax"] - elapsed
-    tricg_(ws, A, b, c, **full)
-    ws._timer_extra = elapsed
-    return ws.x, ws.y, ws.stats, ws
+    return _solve_pair("tricg", TricgWorkspace, A, b, c, x0, y0, kw)
 
 
 def trimr(A, b: DeviceVector, c: DeviceVector, x0=None, y0=None, **kw):
     """Out-of-place trimr(A, b, c[, x0, y0]; kwargs...) -> (x, y, stats, workspace) (src/trimr.jl:16-34); A' is taken once and kept on
     A.  The workspace's creation and the warm start are charged to `timemax` and `stats.timer`, as krylov_solve does."""
-    wkw = {k: kw.pop(k) for k in list(kw) if k in ("adopt", "vectors")}
-    t0 = time.perf_counter()
-    ws = TrimrWorkspace(b.ctx, len(b), len(c), **wkw)
-    if x0 is not None or y0 is not None:
-        ws.warm_start_(x0, y0)
-    elapsed = time.perf_counter() - t0
-    full = _forward("trimr", kw)
-    full["timemax"] = full["timemax"] - elapsed
-    trimr_(ws, A, b, c, **full)
-    ws._timer_extra = elapsed
-    return ws.x, ws.y, ws.stats, ws
+    return _solve_pair("trimr", TrimrWorkspace, A, b, c, x0, y0, kw)
 
 
 def usymlqr(A, b: DeviceVector, c: DeviceVector, x0=None, y0=None, **kw):
     """Out-of-place usymlqr(A, b, c[, x0, y0]; kwargs...) -> (x, y, stats, workspace) (src/usymlqr.jl:20-32); A' is taken once and kept
     on A.  The workspace's creation and the warm start are charged to `timemax` and `stats.timer`, as krylov_solve does."""
-    wkw = {k: kw.pop(k) for k in list(kw) if k in ("adopt", "vectors")}
-    t0 = time.perf_counter()
-    ws = UsymlqrWorkspace(b.ctx, len(b), len(c), **wkw)
-    if x0 is not None or y0 is not None:
-        ws.warm_start_(x0, y0)
-    elapsed = time.perf_counter() - t0
-    full = _forward("usymlqr", kw)
-    full["timemax"] = full["timemax"] - elapsed
-    usymlqr_(ws, A, b, c, **full)
-    ws._timer_extra = elapsed
-    return ws.x, ws.y, ws.stats, ws
+    return _solve_pair("usymlqr", UsymlqrWorkspace, A, b, c, x0, y0, kw)
 
 
 def cg_lanczos_shift(A, b: DeviceVector, shifts, **kw):

@@ -224,7 +224,7 @@ int khip_bilq_workspace_destroy(khip_bilq_workspace *ws) {
   return KHIP_OK;
 }
 
-int khip_bilq_warm_start(khip_bilq_workspace *ws, const double *x0) { return ws_warm_start(ws, x0, "bilq_warm_start"); }
+int khip_bilq_warm_start(khip_bilq_workspace *ws, const double *x0) { return ws_warm_start(ws, kVectors, x0, "bilq_warm_start"); }
 double *khip_bilq_solution(khip_bilq_workspace *ws) { return ws ? ws->x : nullptr; }
 const khip_stats *khip_bilq_stats(khip_bilq_workspace *ws) { return ws ? &ws->box.st : nullptr; }
 int khip_bilq_last_path(khip_bilq_workspace *ws) { return ws ? ws->box.path : -1; }

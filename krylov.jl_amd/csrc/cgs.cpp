@@ -262,7 +262,7 @@ int khip_cgs_workspace_destroy(khip_cgs_workspace *ws) {
   return KHIP_OK;
 }
 
-int khip_cgs_warm_start(khip_cgs_workspace *ws, const double *x0) { return ws_warm_start(ws, x0, "cgs_warm_start"); }
+int khip_cgs_warm_start(khip_cgs_workspace *ws, const double *x0) { return ws_warm_start(ws, kVectors, x0, "cgs_warm_start"); }
 double *khip_cgs_solution(khip_cgs_workspace *ws) { return ws ? ws->x : nullptr; }
 const khip_stats *khip_cgs_stats(khip_cgs_workspace *ws) { return ws ? &ws->box.st : nullptr; }
 int khip_cgs_last_path(khip_cgs_workspace *ws) { return ws ? ws->box.path : -1; }

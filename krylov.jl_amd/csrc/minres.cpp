@@ -294,7 +294,7 @@ int khip_minres_workspace_destroy(khip_minres_workspace *ws) {
   return KHIP_OK;
 }
 
-int khip_minres_warm_start(khip_minres_workspace *ws, const double *x0) { return ws_warm_start(ws, x0, "minres_warm_start"); }
+int khip_minres_warm_start(khip_minres_workspace *ws, const double *x0) { return ws_warm_start(ws, kVectors, x0, "minres_warm_start"); }
 
 double *khip_minres_solution(khip_minres_workspace *ws) { return ws ? ws->x : nullptr; }
 const khip_stats *khip_minres_stats(khip_minres_workspace *ws) { return ws ? &ws->box.st : nullptr; }

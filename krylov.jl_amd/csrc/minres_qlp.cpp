@@ -331,7 +331,7 @@ int khip_minres_qlp_workspace_destroy(khip_minres_qlp_workspace *ws) {
   return KHIP_OK;
 }
 
-int khip_minres_qlp_warm_start(khip_minres_qlp_workspace *ws, const double *x0) { return ws_warm_start(ws, x0, "minres_qlp_warm_start"); }
+int khip_minres_qlp_warm_start(khip_minres_qlp_workspace *ws, const double *x0) { return ws_warm_start(ws, kVectors, x0, "minres_qlp_warm_start"); }
 double *khip_minres_qlp_solution(khip_minres_qlp_workspace *ws) { return ws ? ws->x : nullptr; }
 const khip_stats *khip_minres_qlp_stats(khip_minres_qlp_workspace *ws) { return ws ? &ws->box.st : nullptr; }
 int khip_minres_qlp_last_path(khip_minres_qlp_workspace *ws) { return ws ? ws->box.path : -1; }

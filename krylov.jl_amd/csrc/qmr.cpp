@@ -237,7 +237,7 @@ int khip_qmr_workspace_destroy(khip_qmr_workspace *ws) {
   return KHIP_OK;
 }
 
-int khip_qmr_warm_start(khip_qmr_workspace *ws, const double *x0) { return ws_warm_start(ws, x0, "qmr_warm_start"); }
+int khip_qmr_warm_start(khip_qmr_workspace *ws, const double *x0) { return ws_warm_start(ws, kVectors, x0, "qmr_warm_start"); }
 double *khip_qmr_solution(khip_qmr_workspace *ws) { return ws ? ws->x : nullptr; }
 const khip_stats *khip_qmr_stats(khip_qmr_workspace *ws) { return ws ? &ws->box.st : nullptr; }
 int khip_qmr_last_path(khip_qmr_workspace *ws) { return ws ? ws->box.path : -1; }

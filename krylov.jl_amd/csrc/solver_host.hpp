@@ -143,33 +143,44 @@ int adopt_named(khip_ctx *ctx, Borrowed &b, NamedSlots tab, const char *fn, cons
   return KHIP_ERR_INVALID;
 }
 
-// ---- one vector table per workspace type (minres!, bilq!, qmr!, bilqr!): the only place a workspace lists its vectors ----------
+// ---- one vector table per workspace type: the only place a workspace lists its vectors and says how long each one is -----------
 // Core vectors are allocated by khip_*_workspace_create, handed over in the table's order by khip_*_workspace_adopt and fixed
 // for khip_*_workspace_adopt_vector; they come first.  Lazy vectors stay empty until a solve, a warm start or adopt_vector
-// fills them.  A workspace W has ctx, n, borrowed and box beside its vectors; `fn` is the entry point, for the messages.
+// fills them.  A vector has n entries unless its entry says RowSide (m entries: the solvers on an m x n operator).  A workspace W
+// has ctx, m, n, borrowed and box beside its vectors; `fn` is the entry point, for the messages.
 enum WsVecKind { Core, Lazy };
+enum WsVecSide { ColSide, RowSide };   // n entries (what an entry without a fourth member means) / m entries
 template <class W>
 struct WsVec {
   const char *k;
   double *W::*slot;
   WsVecKind kind;
+  WsVecSide side;
 };
+template <class W> int64_t ws_len(const W *ws, const WsVec<W> &e) { return e.side == RowSide ? ws->m : ws->n; }
+template <class W, size_t N> const WsVec<W> *ws_entry(const WsVec<W> (&tab)[N], double *W::*slot) {
+  for (const WsVec<W> &e : tab) if (e.slot == slot) return &e;
+  return nullptr;
+}
 template <class W, size_t N> std::string ws_core_names(const WsVec<W> (&tab)[N]) {
   std::string names;
   for (const WsVec<W> &e : tab) if (e.kind == Core) names += (names.empty() ? "" : ", ") + std::string(e.k);
   return names;
 }
+// stops at the first allocation that fails; what was allocated before it stays in its slot for khip_*_workspace_destroy
 template <class W, size_t N> int ws_create_core(W *ws, const WsVec<W> (&tab)[N]) {
   (void)take_alloc_seconds();
-  for (const WsVec<W> &e : tab) if (e.kind == Core) KHIP_TRY(alloc_vec(ws->ctx, ws->n, &(ws->*e.slot)));
+  int rc = KHIP_OK;
+  for (const WsVec<W> &e : tab) if (e.kind == Core && rc == KHIP_OK) rc = alloc_vec(ws->ctx, ws_len(ws, e), &(ws->*e.slot));
   ws->box.st.allocation_timer = take_alloc_seconds();
-  return KHIP_OK;
+  return rc;
 }
 template <class W, size_t N>
 int ws_adopt_core(W *ws, const WsVec<W> (&tab)[N], const char *fn, std::initializer_list<double *> ptrs) {
   const std::string names = ws_core_names(tab);
   bool all = true;
   for (const double *p : ptrs) all = all && p;
+  // the message says "n entries" for every table (its wording since the square solvers); a RowSide vector has m
   KHIP_REQUIRE(ws->n == 0 || all, "%s: %s must be device vectors of n entries", fn, names.c_str());
   for (const double *const *i = ptrs.begin(); i != ptrs.end(); ++i)
     for (const double *const *j = i + 1; j != ptrs.end(); ++j)
@@ -181,6 +192,29 @@ int ws_adopt_core(W *ws, const WsVec<W> (&tab)[N], const char *fn, std::initiali
     ws->*e.slot = *next;
     ws->borrowed.add(*next++);
   }
+  return KHIP_OK;
+}
+// khip_*_workspace_create / _adopt of the solvers on an m x n operator: a fresh workspace with its core vectors allocated
+// here / taken from the caller in the table's order.  `destroy` is the solver's khip_*_workspace_destroy.
+template <class W, size_t N>
+int ws_create(khip_ctx *ctx, int64_t m, int64_t n, const WsVec<W> (&tab)[N], const char *fn, int (*destroy)(W *), W **out) {
+  KHIP_REQUIRE(ctx && out && m >= 0 && n >= 0, "%s: bad argument", fn);
+  W *ws = new W();
+  ws->ctx = ctx; ws->m = m; ws->n = n;
+  const int rc = ws_create_core(ws, tab);
+  if (rc) { (void)destroy(ws); return rc; }
+  *out = ws;
+  return KHIP_OK;
+}
+template <class W, size_t N>
+int ws_adopt(khip_ctx *ctx, int64_t m, int64_t n, const WsVec<W> (&tab)[N], const char *fn, std::initializer_list<double *> ptrs,
+             W **out) {
+  KHIP_REQUIRE(ctx && out && m >= 0 && n >= 0, "%s: bad argument", fn);
+  W *ws = new W();
+  ws->ctx = ctx; ws->m = m; ws->n = n;
+  const int rc = ws_adopt_core(ws, tab, fn, ptrs);
+  if (rc) { delete ws; return rc; }
+  *out = ws;
   return KHIP_OK;
 }
 template <class W, size_t N>
@@ -202,14 +236,26 @@ template <class W, size_t N> double *ws_vector(W *ws, const WsVec<W> (&tab)[N], 
 template <class W, size_t N> size_t ws_bytes(W *ws, const WsVec<W> (&tab)[N]) {
   if (!ws) return 0;
   size_t cnt = 0;
-  for (const WsVec<W> &e : tab) cnt += ws->*e.slot ? 1 : 0;
-  return cnt * sizeof(double) * (size_t)ws->n;
+  for (const WsVec<W> &e : tab) if (ws->*e.slot) cnt += (size_t)ws_len(ws, e);
+  return cnt * sizeof(double);
 }
-// khip_*_warm_start of the workspaces with one Δx (minres!, bilq!, qmr!): x0 == ws->dx only sets the flag
-template <class W> int ws_warm_start(W *ws, const double *x0, const char *fn) {
+// khip_*_warm_start of the workspaces with one Δx: x0 == ws->dx only sets the flag
+template <class W, size_t N> int ws_warm_start(W *ws, const WsVec<W> (&tab)[N], const double *x0, const char *fn) {
   KHIP_REQUIRE(ws && x0, "%s: null argument", fn);
-  if (!ws->dx) KHIP_TRY(alloc_vec(ws->ctx, ws->n, &ws->dx));
-  if (x0 != ws->dx) KHIP_TRY(khip_copy(ws->ctx, ws->n, ws->dx, x0));
+  const int64_t len = ws_len(ws, *ws_entry(tab, &W::dx));
+  if (!ws->dx) KHIP_TRY(alloc_vec(ws->ctx, len, &ws->dx));
+  if (x0 != ws->dx) KHIP_TRY(khip_copy(ws->ctx, len, ws->dx, x0));
+  ws->warm_start = true;
+  return KHIP_OK;
+}
+// khip_*_warm_start of the workspaces with Δx and Δy, each at its own length: x0 == ws->dx / y0 == ws->dy only sets the flag
+template <class W, size_t N> int ws_warm_start2(W *ws, const WsVec<W> (&tab)[N], const double *x0, const double *y0, const char *fn) {
+  KHIP_REQUIRE(ws && x0 && y0, "%s: x0 and y0 are both required", fn);
+  const int64_t nx = ws_len(ws, *ws_entry(tab, &W::dx)), ny = ws_len(ws, *ws_entry(tab, &W::dy));
+  if (!ws->dx) KHIP_TRY(alloc_vec(ws->ctx, nx, &ws->dx));
+  if (!ws->dy) KHIP_TRY(alloc_vec(ws->ctx, ny, &ws->dy));
+  if (x0 != ws->dx) KHIP_TRY(khip_copy(ws->ctx, nx, ws->dx, x0));
+  if (y0 != ws->dy) KHIP_TRY(khip_copy(ws->ctx, ny, ws->dy, y0));
   ws->warm_start = true;
   return KHIP_OK;
 }

@@ -233,7 +233,7 @@ int khip_symmlq_workspace_destroy(khip_symmlq_workspace *ws) {
   return KHIP_OK;
 }
 
-int khip_symmlq_warm_start(khip_symmlq_workspace *ws, const double *x0) { return ws_warm_start(ws, x0, "symmlq_warm_start"); }
+int khip_symmlq_warm_start(khip_symmlq_workspace *ws, const double *x0) { return ws_warm_start(ws, kVectors, x0, "symmlq_warm_start"); }
 double *khip_symmlq_solution(khip_symmlq_workspace *ws) { return ws ? ws->x : nullptr; }
 const khip_stats *khip_symmlq_stats(khip_symmlq_workspace *ws) { return ws ? &ws->box.st : nullptr; }
 int khip_symmlq_last_path(khip_symmlq_workspace *ws) { return ws ? ws->box.path : -1; }

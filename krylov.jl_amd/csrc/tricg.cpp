@@ -213,14 +213,11 @@ namespace {
 // y, N⁻¹uₖ₋₁, N⁻¹uₖ, p, gy₂ₖ₋₁, gy₂ₖ, x, M⁻¹vₖ₋₁, M⁻¹vₖ, q, gx₂ₖ₋₁, gx₂ₖ come with the workspace; Δx, Δy stay empty until a warm start
 // (src/krylov_workspaces.jl, TricgWorkspace: the table keeps its order; with M = N = I its uₖ and vₖ never exist)
 using W = khip_tricg_workspace;
-constexpr WsVec<W> kVectors[] = {{"y", &W::y, Core},           {"u_prev", &W::u_prev, Core}, {"u", &W::u, Core},
-                                 {"p", &W::p, Core},           {"gy_prev", &W::gy_prev, Core}, {"gy", &W::gy, Core},
-                                 {"x", &W::x, Core},           {"v_prev", &W::v_prev, Core}, {"v", &W::v, Core},
-                                 {"q", &W::q, Core},           {"gx_prev", &W::gx_prev, Core}, {"gx", &W::gx, Core},
-                                 {"dx", &W::dx, Lazy},         {"dy", &W::dy, Lazy}};
-constexpr size_t kVectorCount = sizeof(kVectors) / sizeof(kVectors[0]);
-constexpr size_t kColSide = 6;              // the first six vectors of the table and Δy have n entries, the others m
-int64_t side(const W *ws, size_t i) { return (i < kColSide || kVectors[i].slot == &W::dy) ? ws->n : ws->m; }
+constexpr WsVec<W> kVectors[] = {{"y", &W::y, Core},             {"u_prev", &W::u_prev, Core},            {"u", &W::u, Core},
+                                 {"p", &W::p, Core},             {"gy_prev", &W::gy_prev, Core},          {"gy", &W::gy, Core},
+                                 {"x", &W::x, Core, RowSide},    {"v_prev", &W::v_prev, Core, RowSide},   {"v", &W::v, Core, RowSide},
+                                 {"q", &W::q, Core, RowSide},    {"gx_prev", &W::gx_prev, Core, RowSide}, {"gx", &W::gx, Core, RowSide},
+                                 {"dx", &W::dx, Lazy, RowSide},  {"dy", &W::dy, Lazy}};
 
 // what tricg! adds to the driver of the process (ssy.hpp)
 struct Tricg : SsyPolicy<TricgDevState, W> {
@@ -289,29 +286,13 @@ khip_tricg_params khip_tricg_default_params(void) {
 }
 
 int khip_tricg_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_tricg_workspace **out) {
-  KHIP_REQUIRE(ctx && out && m >= 0 && n >= 0, "tricg_workspace_create: bad argument");
-  khip_tricg_workspace *ws = new khip_tricg_workspace();
-  ws->ctx = ctx; ws->m = m; ws->n = n;
-  (void)take_alloc_seconds();
-  int rc = KHIP_OK;
-  for (size_t i = 0; i < kVectorCount && rc == KHIP_OK; ++i)
-    if (kVectors[i].kind == Core) rc = alloc_vec(ctx, side(ws, i), &(ws->*kVectors[i].slot));
-  ws->box.st.allocation_timer = take_alloc_seconds();
-  if (rc) { khip_tricg_workspace_destroy(ws); return rc; }
-  *out = ws;
-  return KHIP_OK;
+  return ws_create(ctx, m, n, kVectors, "tricg_workspace_create", khip_tricg_workspace_destroy, out);
 }
 
 int khip_tricg_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *y, double *u_prev, double *u, double *p, double *gy_prev,
                                double *gy, double *x, double *v_prev, double *v, double *q, double *gx_prev, double *gx,
                                khip_tricg_workspace **out) {
-  KHIP_REQUIRE(ctx && out && m >= 0 && n >= 0, "tricg_workspace_adopt: bad argument");
-  khip_tricg_workspace *ws = new khip_tricg_workspace();
-  ws->ctx = ctx; ws->m = m; ws->n = n;
-  const int rc = ws_adopt_core(ws, kVectors, "tricg_workspace_adopt", {y, u_prev, u, p, gy_prev, gy, x, v_prev, v, q, gx_prev, gx});
-  if (rc) { delete ws; return rc; }
-  *out = ws;
-  return KHIP_OK;
+  return ws_adopt(ctx, m, n, kVectors, "tricg_workspace_adopt", {y, u_prev, u, p, gy_prev, gy, x, v_prev, v, q, gx_prev, gx}, out);
 }
 
 int khip_tricg_workspace_adopt_vector(khip_tricg_workspace *ws, const char *name, double *ptr) {
@@ -326,14 +307,8 @@ int khip_tricg_workspace_destroy(khip_tricg_workspace *ws) {
   return KHIP_OK;
 }
 
-int khip_tricg_warm_start(khip_tricg_workspace *ws, const double *x0, const double *y0) {
-  KHIP_REQUIRE(ws && x0 && y0, "tricg_warm_start: x0 and y0 are both required");
-  if (!ws->dx) KHIP_TRY(alloc_vec(ws->ctx, ws->m, &ws->dx));
-  if (!ws->dy) KHIP_TRY(alloc_vec(ws->ctx, ws->n, &ws->dy));
-  if (x0 != ws->dx) KHIP_TRY(khip_copy(ws->ctx, ws->m, ws->dx, x0));
-  if (y0 != ws->dy) KHIP_TRY(khip_copy(ws->ctx, ws->n, ws->dy, y0));
-  ws->warm_start = true;
-  return KHIP_OK;
+int khip_tricg_warm_start(khip_tricg_workspace *ws, const double *x0, const double *y0) {   // Δx of m entries, Δy of n
+  return ws_warm_start2(ws, kVectors, x0, y0, "tricg_warm_start");
 }
 
 double *khip_tricg_solution_x(khip_tricg_workspace *ws) { return ws ? ws->x : nullptr; }
@@ -341,14 +316,7 @@ double *khip_tricg_solution_y(khip_tricg_workspace *ws) { return ws ? ws->y : nu
 const khip_stats *khip_tricg_stats(khip_tricg_workspace *ws) { return ws ? &ws->box.st : nullptr; }
 int khip_tricg_last_path(khip_tricg_workspace *ws) { return ws ? ws->box.path : -1; }
 double *khip_tricg_vector(khip_tricg_workspace *ws, const char *name) { return ws_vector(ws, kVectors, name); }
-
-size_t khip_tricg_workspace_bytes(khip_tricg_workspace *ws) {
-  if (!ws) return 0;
-  size_t cnt = 0;
-  for (size_t i = 0; i < kVectorCount; ++i)
-    if (ws->*kVectors[i].slot) cnt += (size_t)side(ws, i);
-  return cnt * sizeof(double);
-}
+size_t khip_tricg_workspace_bytes(khip_tricg_workspace *ws) { return ws_bytes(ws, kVectors); }
 
 int khip_tricg_solve(khip_tricg_workspace *ws, const khip_operator *A, const khip_operator *At, const double *b, const double *c,
                      const khip_options *opts_in, const khip_tricg_params *params_in) {

@@ -191,13 +191,11 @@ namespace {
 // uₖ₋₁, uₖ, p, d̅, x, vₖ₋₁, vₖ, q, t ("y"), wₖ₋₃, wₖ₋₂ come with the workspace; Δx, Δy stay empty until a warm start
 // (src/krylov_workspaces.jl, TrilqrWorkspace: the table keeps its order)
 using W = khip_trilqr_workspace;
-constexpr WsVec<W> kVectors[] = {{"u_prev", &W::u_prev, Core},   {"u", &W::u, Core},   {"p", &W::p, Core}, {"dbar", &W::dbar, Core},
-                                 {"x", &W::x, Core},             {"v_prev", &W::v_prev, Core},             {"v", &W::v, Core},
-                                 {"q", &W::q, Core},             {"y", &W::y, Core},   {"w_prev3", &W::w_prev3, Core},
-                                 {"w_prev2", &W::w_prev2, Core}, {"dx", &W::dx, Lazy}, {"dy", &W::dy, Lazy}};
-constexpr size_t kVectorCount = sizeof(kVectors) / sizeof(kVectors[0]);
-constexpr size_t kColSide = 5;              // the first five vectors of the table and Δx have n entries, the others m
-int64_t side(const W *ws, size_t i) { return (i < kColSide || kVectors[i].slot == &W::dx) ? ws->n : ws->m; }
+constexpr WsVec<W> kVectors[] = {{"u_prev", &W::u_prev, Core},            {"u", &W::u, Core},          {"p", &W::p, Core},
+                                 {"dbar", &W::dbar, Core},                {"x", &W::x, Core},          {"v_prev", &W::v_prev, Core, RowSide},
+                                 {"v", &W::v, Core, RowSide},             {"q", &W::q, Core, RowSide}, {"y", &W::y, Core, RowSide},
+                                 {"w_prev3", &W::w_prev3, Core, RowSide}, {"w_prev2", &W::w_prev2, Core, RowSide},
+                                 {"dx", &W::dx, Lazy},                    {"dy", &W::dy, Lazy, RowSide}};
 
 // "%7s" of the reference pads characters; ✗ ✗ ✗ ✗ is seven of them                                      (src/trilqr.jl:417-418)
 const char *const kCrosses = "\xe2\x9c\x97 \xe2\x9c\x97 \xe2\x9c\x97 \xe2\x9c\x97";
@@ -320,29 +318,13 @@ khip_trilqr_params khip_trilqr_default_params(void) {
 }
 
 int khip_trilqr_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_trilqr_workspace **out) {
-  KHIP_REQUIRE(ctx && out && m >= 0 && n >= 0, "trilqr_workspace_create: bad argument");
-  khip_trilqr_workspace *ws = new khip_trilqr_workspace();
-  ws->ctx = ctx; ws->m = m; ws->n = n;
-  (void)take_alloc_seconds();
-  int rc = KHIP_OK;
-  for (size_t i = 0; i < kVectorCount && rc == KHIP_OK; ++i)
-    if (kVectors[i].kind == Core) rc = alloc_vec(ctx, side(ws, i), &(ws->*kVectors[i].slot));
-  ws->box.st.allocation_timer = take_alloc_seconds();
-  if (rc) { khip_trilqr_workspace_destroy(ws); return rc; }
-  *out = ws;
-  return KHIP_OK;
+  return ws_create(ctx, m, n, kVectors, "trilqr_workspace_create", khip_trilqr_workspace_destroy, out);
 }
 
 int khip_trilqr_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *u_prev, double *u, double *p, double *dbar, double *x,
                                 double *v_prev, double *v, double *q, double *y, double *w_prev3, double *w_prev2,
                                 khip_trilqr_workspace **out) {
-  KHIP_REQUIRE(ctx && out && m >= 0 && n >= 0, "trilqr_workspace_adopt: bad argument");
-  khip_trilqr_workspace *ws = new khip_trilqr_workspace();
-  ws->ctx = ctx; ws->m = m; ws->n = n;
-  const int rc = ws_adopt_core(ws, kVectors, "trilqr_workspace_adopt", {u_prev, u, p, dbar, x, v_prev, v, q, y, w_prev3, w_prev2});
-  if (rc) { delete ws; return rc; }
-  *out = ws;
-  return KHIP_OK;
+  return ws_adopt(ctx, m, n, kVectors, "trilqr_workspace_adopt", {u_prev, u, p, dbar, x, v_prev, v, q, y, w_prev3, w_prev2}, out);
 }
 
 int khip_trilqr_workspace_adopt_vector(khip_trilqr_workspace *ws, const char *name, double *ptr) {
@@ -357,14 +339,8 @@ int khip_trilqr_workspace_destroy(khip_trilqr_workspace *ws) {
   return KHIP_OK;
 }
 
-int khip_trilqr_warm_start(khip_trilqr_workspace *ws, const double *x0, const double *y0) {
-  KHIP_REQUIRE(ws && x0 && y0, "trilqr_warm_start: x0 and y0 are both required");
-  if (!ws->dx) KHIP_TRY(alloc_vec(ws->ctx, ws->n, &ws->dx));
-  if (!ws->dy) KHIP_TRY(alloc_vec(ws->ctx, ws->m, &ws->dy));
-  if (x0 != ws->dx) KHIP_TRY(khip_copy(ws->ctx, ws->n, ws->dx, x0));
-  if (y0 != ws->dy) KHIP_TRY(khip_copy(ws->ctx, ws->m, ws->dy, y0));
-  ws->warm_start = true;
-  return KHIP_OK;
+int khip_trilqr_warm_start(khip_trilqr_workspace *ws, const double *x0, const double *y0) {   // Δx of n entries, Δy of m
+  return ws_warm_start2(ws, kVectors, x0, y0, "trilqr_warm_start");
 }
 
 double *khip_trilqr_solution_x(khip_trilqr_workspace *ws) { return ws ? ws->x : nullptr; }
@@ -384,14 +360,7 @@ int khip_trilqr_adjoint_stats(khip_trilqr_workspace *ws, int *solved_primal, int
 }
 int khip_trilqr_last_path(khip_trilqr_workspace *ws) { return ws ? ws->box.path : -1; }
 double *khip_trilqr_vector(khip_trilqr_workspace *ws, const char *name) { return ws_vector(ws, kVectors, name); }
-
-size_t khip_trilqr_workspace_bytes(khip_trilqr_workspace *ws) {
-  if (!ws) return 0;
-  size_t cnt = 0;
-  for (size_t i = 0; i < kVectorCount; ++i)
-    if (ws->*kVectors[i].slot) cnt += (size_t)side(ws, i);
-  return cnt * sizeof(double);
-}
+size_t khip_trilqr_workspace_bytes(khip_trilqr_workspace *ws) { return ws_bytes(ws, kVectors); }
 
 int khip_trilqr_solve(khip_trilqr_workspace *ws, const khip_operator *A, const khip_operator *At, const double *b, const double *c,
                       const khip_options *opts_in, const khip_trilqr_params *params_in) {

@@ -329,12 +329,10 @@ namespace {
 using W = khip_trimr_workspace;
 constexpr WsVec<W> kVectors[] = {{"y", &W::y, Core},         {"u_prev", &W::u_prev, Core}, {"u", &W::u, Core},         {"p", &W::p, Core},
                                  {"gy_m3", &W::gy_m3, Core}, {"gy_m2", &W::gy_m2, Core},   {"gy_m1", &W::gy_m1, Core}, {"gy", &W::gy, Core},
-                                 {"x", &W::x, Core},         {"v_prev", &W::v_prev, Core}, {"v", &W::v, Core},         {"q", &W::q, Core},
-                                 {"gx_m3", &W::gx_m3, Core}, {"gx_m2", &W::gx_m2, Core},   {"gx_m1", &W::gx_m1, Core}, {"gx", &W::gx, Core},
-                                 {"dx", &W::dx, Lazy},       {"dy", &W::dy, Lazy}};
-constexpr size_t kVectorCount = sizeof(kVectors) / sizeof(kVectors[0]);
-constexpr size_t kColSide = 8;              // the first eight vectors of the table and Δy have n entries, the others m
-int64_t side(const W *ws, size_t i) { return (i < kColSide || kVectors[i].slot == &W::dy) ? ws->n : ws->m; }
+                                 {"x", &W::x, Core, RowSide},         {"v_prev", &W::v_prev, Core, RowSide}, {"v", &W::v, Core, RowSide},
+                                 {"q", &W::q, Core, RowSide},         {"gx_m3", &W::gx_m3, Core, RowSide},   {"gx_m2", &W::gx_m2, Core, RowSide},
+                                 {"gx_m1", &W::gx_m1, Core, RowSide}, {"gx", &W::gx, Core, RowSide},
+                                 {"dx", &W::dx, Lazy, RowSide},       {"dy", &W::dy, Lazy}};
 
 // what trimr! adds to the driver of the process (ssy.hpp)
 struct Trimr : SsyPolicy<TrimrDevState, W> {
@@ -404,30 +402,14 @@ khip_trimr_params khip_trimr_default_params(void) {
 }
 
 int khip_trimr_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_trimr_workspace **out) {
-  KHIP_REQUIRE(ctx && out && m >= 0 && n >= 0, "trimr_workspace_create: bad argument");
-  khip_trimr_workspace *ws = new khip_trimr_workspace();
-  ws->ctx = ctx; ws->m = m; ws->n = n;
-  (void)take_alloc_seconds();
-  int rc = KHIP_OK;
-  for (size_t i = 0; i < kVectorCount && rc == KHIP_OK; ++i)
-    if (kVectors[i].kind == Core) rc = alloc_vec(ctx, side(ws, i), &(ws->*kVectors[i].slot));
-  ws->box.st.allocation_timer = take_alloc_seconds();
-  if (rc) { khip_trimr_workspace_destroy(ws); return rc; }
-  *out = ws;
-  return KHIP_OK;
+  return ws_create(ctx, m, n, kVectors, "trimr_workspace_create", khip_trimr_workspace_destroy, out);
 }
 
 int khip_trimr_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *y, double *u_prev, double *u, double *p, double *gy_m3,
                                double *gy_m2, double *gy_m1, double *gy, double *x, double *v_prev, double *v, double *q, double *gx_m3,
                                double *gx_m2, double *gx_m1, double *gx, khip_trimr_workspace **out) {
-  KHIP_REQUIRE(ctx && out && m >= 0 && n >= 0, "trimr_workspace_adopt: bad argument");
-  khip_trimr_workspace *ws = new khip_trimr_workspace();
-  ws->ctx = ctx; ws->m = m; ws->n = n;
-  const int rc = ws_adopt_core(ws, kVectors, "trimr_workspace_adopt",
-                               {y, u_prev, u, p, gy_m3, gy_m2, gy_m1, gy, x, v_prev, v, q, gx_m3, gx_m2, gx_m1, gx});
-  if (rc) { delete ws; return rc; }
-  *out = ws;
-  return KHIP_OK;
+  return ws_adopt(ctx, m, n, kVectors, "trimr_workspace_adopt",
+                  {y, u_prev, u, p, gy_m3, gy_m2, gy_m1, gy, x, v_prev, v, q, gx_m3, gx_m2, gx_m1, gx}, out);
 }
 
 int khip_trimr_workspace_adopt_vector(khip_trimr_workspace *ws, const char *name, double *ptr) {
@@ -442,14 +424,8 @@ int khip_trimr_workspace_destroy(khip_trimr_workspace *ws) {
   return KHIP_OK;
 }
 
-int khip_trimr_warm_start(khip_trimr_workspace *ws, const double *x0, const double *y0) {
-  KHIP_REQUIRE(ws && x0 && y0, "trimr_warm_start: x0 and y0 are both required");
-  if (!ws->dx) KHIP_TRY(alloc_vec(ws->ctx, ws->m, &ws->dx));
-  if (!ws->dy) KHIP_TRY(alloc_vec(ws->ctx, ws->n, &ws->dy));
-  if (x0 != ws->dx) KHIP_TRY(khip_copy(ws->ctx, ws->m, ws->dx, x0));
-  if (y0 != ws->dy) KHIP_TRY(khip_copy(ws->ctx, ws->n, ws->dy, y0));
-  ws->warm_start = true;
-  return KHIP_OK;
+int khip_trimr_warm_start(khip_trimr_workspace *ws, const double *x0, const double *y0) {   // Δx of m entries, Δy of n
+  return ws_warm_start2(ws, kVectors, x0, y0, "trimr_warm_start");
 }
 
 double *khip_trimr_solution_x(khip_trimr_workspace *ws) { return ws ? ws->x : nullptr; }
@@ -457,14 +433,7 @@ double *khip_trimr_solution_y(khip_trimr_workspace *ws) { return ws ? ws->y : nu
 const khip_stats *khip_trimr_stats(khip_trimr_workspace *ws) { return ws ? &ws->box.st : nullptr; }
 int khip_trimr_last_path(khip_trimr_workspace *ws) { return ws ? ws->box.path : -1; }
 double *khip_trimr_vector(khip_trimr_workspace *ws, const char *name) { return ws_vector(ws, kVectors, name); }
-
-size_t khip_trimr_workspace_bytes(khip_trimr_workspace *ws) {
-  if (!ws) return 0;
-  size_t cnt = 0;
-  for (size_t i = 0; i < kVectorCount; ++i)
-    if (ws->*kVectors[i].slot) cnt += (size_t)side(ws, i);
-  return cnt * sizeof(double);
-}
+size_t khip_trimr_workspace_bytes(khip_trimr_workspace *ws) { return ws_bytes(ws, kVectors); }
 
 int khip_trimr_solve(khip_trimr_workspace *ws, const khip_operator *A, const khip_operator *At, const double *b, const double *c,
                      const khip_options *opts_in, const khip_trimr_params *params_in) {

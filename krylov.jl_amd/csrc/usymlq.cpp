@@ -133,9 +133,8 @@ namespace {
 // UsymlqWorkspace: the table keeps its order)
 using W = khip_usymlq_workspace;
 constexpr WsVec<W> kVectors[] = {{"u_prev", &W::u_prev, Core}, {"u", &W::u, Core},       {"p", &W::p, Core},
-                                 {"x", &W::x, Core},           {"dbar", &W::dbar, Core}, {"v_prev", &W::v_prev, Core},
-                                 {"v", &W::v, Core},           {"q", &W::q, Core},       {"dx", &W::dx, Lazy}};
-constexpr int kColSide = 5;                 // the first five vectors of the table and Δx have n entries, v_prev, v, q have m
+                                 {"x", &W::x, Core},           {"dbar", &W::dbar, Core}, {"v_prev", &W::v_prev, Core, RowSide},
+                                 {"v", &W::v, Core, RowSide},  {"q", &W::q, Core, RowSide}, {"dx", &W::dx, Lazy}};
 
 // what usymlq! adds to the driver of the process (ssy.hpp)
 struct Usymlq : SsyPolicy<UsymlqDevState, W> {
@@ -169,8 +168,6 @@ struct Usymlq : SsyPolicy<UsymlqDevState, W> {
   }
 };
 
-int64_t side(const W *ws, size_t i) { return (i < (size_t)kColSide || kVectors[i].kind == Lazy) ? ws->n : ws->m; }
-
 }  // namespace
 
 extern "C" {
@@ -182,28 +179,12 @@ khip_usymlq_params khip_usymlq_default_params(void) {
 }
 
 int khip_usymlq_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_usymlq_workspace **out) {
-  KHIP_REQUIRE(ctx && out && m >= 0 && n >= 0, "usymlq_workspace_create: bad argument");
-  khip_usymlq_workspace *ws = new khip_usymlq_workspace();
-  ws->ctx = ctx; ws->m = m; ws->n = n;
-  (void)take_alloc_seconds();
-  int rc = KHIP_OK;
-  for (size_t i = 0; i < sizeof(kVectors) / sizeof(kVectors[0]) && rc == KHIP_OK; ++i)
-    if (kVectors[i].kind == Core) rc = alloc_vec(ctx, side(ws, i), &(ws->*kVectors[i].slot));
-  ws->box.st.allocation_timer = take_alloc_seconds();
-  if (rc) { khip_usymlq_workspace_destroy(ws); return rc; }
-  *out = ws;
-  return KHIP_OK;
+  return ws_create(ctx, m, n, kVectors, "usymlq_workspace_create", khip_usymlq_workspace_destroy, out);
 }
 
 int khip_usymlq_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *u_prev, double *u, double *p, double *x, double *dbar,
                                 double *v_prev, double *v, double *q, khip_usymlq_workspace **out) {
-  KHIP_REQUIRE(ctx && out && m >= 0 && n >= 0, "usymlq_workspace_adopt: bad argument");
-  khip_usymlq_workspace *ws = new khip_usymlq_workspace();
-  ws->ctx = ctx; ws->m = m; ws->n = n;
-  const int rc = ws_adopt_core(ws, kVectors, "usymlq_workspace_adopt", {u_prev, u, p, x, dbar, v_prev, v, q});
-  if (rc) { delete ws; return rc; }
-  *out = ws;
-  return KHIP_OK;
+  return ws_adopt(ctx, m, n, kVectors, "usymlq_workspace_adopt", {u_prev, u, p, x, dbar, v_prev, v, q}, out);
 }
 
 int khip_usymlq_workspace_adopt_vector(khip_usymlq_workspace *ws, const char *name, double *ptr) {
@@ -218,19 +199,12 @@ int khip_usymlq_workspace_destroy(khip_usymlq_workspace *ws) {
   return KHIP_OK;
 }
 
-int khip_usymlq_warm_start(khip_usymlq_workspace *ws, const double *x0) { return ws_warm_start(ws, x0, "usymlq_warm_start"); }
+int khip_usymlq_warm_start(khip_usymlq_workspace *ws, const double *x0) { return ws_warm_start(ws, kVectors, x0, "usymlq_warm_start"); }
 double *khip_usymlq_solution(khip_usymlq_workspace *ws) { return ws ? ws->x : nullptr; }
 const khip_stats *khip_usymlq_stats(khip_usymlq_workspace *ws) { return ws ? &ws->box.st : nullptr; }
 int khip_usymlq_last_path(khip_usymlq_workspace *ws) { return ws ? ws->box.path : -1; }
 double *khip_usymlq_vector(khip_usymlq_workspace *ws, const char *name) { return ws_vector(ws, kVectors, name); }
-
-size_t khip_usymlq_workspace_bytes(khip_usymlq_workspace *ws) {
-  if (!ws) return 0;
-  size_t cnt = 0;
-  for (size_t i = 0; i < sizeof(kVectors) / sizeof(kVectors[0]); ++i)
-    if (ws->*kVectors[i].slot) cnt += (size_t)side(ws, i);
-  return cnt * sizeof(double);
-}
+size_t khip_usymlq_workspace_bytes(khip_usymlq_workspace *ws) { return ws_bytes(ws, kVectors); }
 
 int khip_usymlq_solve(khip_usymlq_workspace *ws, const khip_operator *A, const khip_operator *At, const double *b, const double *c,
                       const khip_options *opts_in, const khip_usymlq_params *params_in) {

@@ -211,17 +211,12 @@ namespace {
 // r, x, y, z, vₖ₋₁, vₖ, uₖ₋₁, uₖ, p, q, d̅, wₖ₋₂, wₖ₋₁ come with the workspace; Δx, Δy stay empty until a warm start
 // (src/krylov_workspaces.jl, UsymlqrWorkspace: the table keeps its order)
 using W = khip_usymlqr_workspace;
-constexpr WsVec<W> kVectors[] = {{"r", &W::r, Core},           {"x", &W::x, Core},       {"y", &W::y, Core},       {"z", &W::z, Core},
-                                 {"v_prev", &W::v_prev, Core}, {"v", &W::v, Core},       {"u_prev", &W::u_prev, Core},
-                                 {"u", &W::u, Core},           {"p", &W::p, Core},       {"q", &W::q, Core},
-                                 {"dbar", &W::dbar, Core},     {"w_m2", &W::w_m2, Core}, {"w_m1", &W::w_m1, Core},
-                                 {"dx", &W::dx, Lazy},         {"dy", &W::dy, Lazy}};
-constexpr size_t kVectorCount = sizeof(kVectors) / sizeof(kVectors[0]);
-int64_t side(const W *ws, size_t i) {       // r, x, vₖ₋₁, vₖ, q, d̅ and Δx have m entries, the others n
-  double *W::*const s = kVectors[i].slot;
-  const bool row = s == &W::r || s == &W::x || s == &W::v_prev || s == &W::v || s == &W::q || s == &W::dbar || s == &W::dx;
-  return row ? ws->m : ws->n;
-}
+constexpr WsVec<W> kVectors[] = {{"r", &W::r, Core, RowSide},           {"x", &W::x, Core, RowSide}, {"y", &W::y, Core},
+                                 {"z", &W::z, Core},                    {"v_prev", &W::v_prev, Core, RowSide},
+                                 {"v", &W::v, Core, RowSide},           {"u_prev", &W::u_prev, Core}, {"u", &W::u, Core},
+                                 {"p", &W::p, Core},                    {"q", &W::q, Core, RowSide},
+                                 {"dbar", &W::dbar, Core, RowSide},     {"w_m2", &W::w_m2, Core},    {"w_m1", &W::w_m1, Core},
+                                 {"dx", &W::dx, Lazy, RowSide},         {"dy", &W::dy, Lazy}};
 
 // "%7s" of the reference pads characters; ✗ ✗ ✗ ✗ is seven of them                                      (src/usymlqr.jl:240-241)
 const char *const kCrosses = "\xe2\x9c\x97 \xe2\x9c\x97 \xe2\x9c\x97 \xe2\x9c\x97";
@@ -307,29 +302,13 @@ khip_usymlqr_params khip_usymlqr_default_params(void) {
 }
 
 int khip_usymlqr_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_usymlqr_workspace **out) {
-  KHIP_REQUIRE(ctx && out && m >= 0 && n >= 0, "usymlqr_workspace_create: bad argument");
-  khip_usymlqr_workspace *ws = new khip_usymlqr_workspace();
-  ws->ctx = ctx; ws->m = m; ws->n = n;
-  (void)take_alloc_seconds();
-  int rc = KHIP_OK;
-  for (size_t i = 0; i < kVectorCount && rc == KHIP_OK; ++i)
-    if (kVectors[i].kind == Core) rc = alloc_vec(ctx, side(ws, i), &(ws->*kVectors[i].slot));
-  ws->box.st.allocation_timer = take_alloc_seconds();
-  if (rc) { khip_usymlqr_workspace_destroy(ws); return rc; }
-  *out = ws;
-  return KHIP_OK;
+  return ws_create(ctx, m, n, kVectors, "usymlqr_workspace_create", khip_usymlqr_workspace_destroy, out);
 }
 
 int khip_usymlqr_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *r, double *x, double *y, double *z, double *v_prev, double *v,
                                  double *u_prev, double *u, double *p, double *q, double *dbar, double *w_m2, double *w_m1,
                                  khip_usymlqr_workspace **out) {
-  KHIP_REQUIRE(ctx && out && m >= 0 && n >= 0, "usymlqr_workspace_adopt: bad argument");
-  khip_usymlqr_workspace *ws = new khip_usymlqr_workspace();
-  ws->ctx = ctx; ws->m = m; ws->n = n;
-  const int rc = ws_adopt_core(ws, kVectors, "usymlqr_workspace_adopt", {r, x, y, z, v_prev, v, u_prev, u, p, q, dbar, w_m2, w_m1});
-  if (rc) { delete ws; return rc; }
-  *out = ws;
-  return KHIP_OK;
+  return ws_adopt(ctx, m, n, kVectors, "usymlqr_workspace_adopt", {r, x, y, z, v_prev, v, u_prev, u, p, q, dbar, w_m2, w_m1}, out);
 }
 
 int khip_usymlqr_workspace_adopt_vector(khip_usymlqr_workspace *ws, const char *name, double *ptr) {
@@ -344,14 +323,8 @@ int khip_usymlqr_workspace_destroy(khip_usymlqr_workspace *ws) {
   return KHIP_OK;
 }
 
-int khip_usymlqr_warm_start(khip_usymlqr_workspace *ws, const double *x0, const double *y0) {
-  KHIP_REQUIRE(ws && x0 && y0, "usymlqr_warm_start: x0 and y0 are both required");
-  if (!ws->dx) KHIP_TRY(alloc_vec(ws->ctx, ws->m, &ws->dx));
-  if (!ws->dy) KHIP_TRY(alloc_vec(ws->ctx, ws->n, &ws->dy));
-  if (x0 != ws->dx) KHIP_TRY(khip_copy(ws->ctx, ws->m, ws->dx, x0));
-  if (y0 != ws->dy) KHIP_TRY(khip_copy(ws->ctx, ws->n, ws->dy, y0));
-  ws->warm_start = true;
-  return KHIP_OK;
+int khip_usymlqr_warm_start(khip_usymlqr_workspace *ws, const double *x0, const double *y0) {   // Δx of m entries, Δy of n
+  return ws_warm_start2(ws, kVectors, x0, y0, "usymlqr_warm_start");
 }
 
 double *khip_usymlqr_solution_x(khip_usymlqr_workspace *ws) { return ws ? ws->x : nullptr; }
@@ -359,14 +332,7 @@ double *khip_usymlqr_solution_y(khip_usymlqr_workspace *ws) { return ws ? ws->y 
 const khip_stats *khip_usymlqr_stats(khip_usymlqr_workspace *ws) { return ws ? &ws->box.st : nullptr; }
 int khip_usymlqr_last_path(khip_usymlqr_workspace *ws) { return ws ? ws->box.path : -1; }
 double *khip_usymlqr_vector(khip_usymlqr_workspace *ws, const char *name) { return ws_vector(ws, kVectors, name); }
-
-size_t khip_usymlqr_workspace_bytes(khip_usymlqr_workspace *ws) {
-  if (!ws) return 0;
-  size_t cnt = 0;
-  for (size_t i = 0; i < kVectorCount; ++i)
-    if (ws->*kVectors[i].slot) cnt += (size_t)side(ws, i);
-  return cnt * sizeof(double);
-}
+size_t khip_usymlqr_workspace_bytes(khip_usymlqr_workspace *ws) { return ws_bytes(ws, kVectors); }
 
 int khip_usymlqr_aresiduals(khip_usymlqr_workspace *ws, const double **aresiduals, int *naresiduals) {
   KHIP_REQUIRE(ws && aresiduals && naresiduals, "usymlqr_aresiduals: null argument");

@@ -130,11 +130,10 @@ namespace {
 // vₖ₋₁, vₖ, q, x, wₖ₋₂, wₖ₋₁, uₖ₋₁, uₖ, p come with the workspace; Δx stays empty until a warm start (src/krylov_workspaces.jl,
 // UsymqrWorkspace: the table keeps its order)
 using W = khip_usymqr_workspace;
-constexpr WsVec<W> kVectors[] = {{"v_prev", &W::v_prev, Core}, {"v", &W::v, Core},           {"q", &W::q, Core},
-                                 {"x", &W::x, Core},           {"w_prev2", &W::w_prev2, Core}, {"w_prev", &W::w_prev, Core},
-                                 {"u_prev", &W::u_prev, Core}, {"u", &W::u, Core},           {"p", &W::p, Core},
+constexpr WsVec<W> kVectors[] = {{"v_prev", &W::v_prev, Core, RowSide}, {"v", &W::v, Core, RowSide},   {"q", &W::q, Core, RowSide},
+                                 {"x", &W::x, Core},                    {"w_prev2", &W::w_prev2, Core}, {"w_prev", &W::w_prev, Core},
+                                 {"u_prev", &W::u_prev, Core},          {"u", &W::u, Core},             {"p", &W::p, Core},
                                  {"dx", &W::dx, Lazy}};
-constexpr int kRowSide = 3;                 // the first three vectors of the table have m entries
 
 // what usymqr! adds to the driver of the process (ssy.hpp)
 struct Usymqr : SsyPolicy<UsymqrDevState, W> {
@@ -177,35 +176,17 @@ struct Usymqr : SsyPolicy<UsymqrDevState, W> {
   }
 };
 
-int64_t side(const W *ws, size_t i) { return i < (size_t)kRowSide ? ws->m : ws->n; }
-
 }  // namespace
 
 extern "C" {
 
 int khip_usymqr_workspace_create(khip_ctx *ctx, int64_t m, int64_t n, khip_usymqr_workspace **out) {
-  KHIP_REQUIRE(ctx && out && m >= 0 && n >= 0, "usymqr_workspace_create: bad argument");
-  khip_usymqr_workspace *ws = new khip_usymqr_workspace();
-  ws->ctx = ctx; ws->m = m; ws->n = n;
-  (void)take_alloc_seconds();
-  int rc = KHIP_OK;
-  for (size_t i = 0; i < sizeof(kVectors) / sizeof(kVectors[0]) && rc == KHIP_OK; ++i)
-    if (kVectors[i].kind == Core) rc = alloc_vec(ctx, side(ws, i), &(ws->*kVectors[i].slot));
-  ws->box.st.allocation_timer = take_alloc_seconds();
-  if (rc) { khip_usymqr_workspace_destroy(ws); return rc; }
-  *out = ws;
-  return KHIP_OK;
+  return ws_create(ctx, m, n, kVectors, "usymqr_workspace_create", khip_usymqr_workspace_destroy, out);
 }
 
 int khip_usymqr_workspace_adopt(khip_ctx *ctx, int64_t m, int64_t n, double *v_prev, double *v, double *q, double *x, double *w_prev2,
                                 double *w_prev, double *u_prev, double *u, double *p, khip_usymqr_workspace **out) {
-  KHIP_REQUIRE(ctx && out && m >= 0 && n >= 0, "usymqr_workspace_adopt: bad argument");
-  khip_usymqr_workspace *ws = new khip_usymqr_workspace();
-  ws->ctx = ctx; ws->m = m; ws->n = n;
-  const int rc = ws_adopt_core(ws, kVectors, "usymqr_workspace_adopt", {v_prev, v, q, x, w_prev2, w_prev, u_prev, u, p});
-  if (rc) { delete ws; return rc; }
-  *out = ws;
-  return KHIP_OK;
+  return ws_adopt(ctx, m, n, kVectors, "usymqr_workspace_adopt", {v_prev, v, q, x, w_prev2, w_prev, u_prev, u, p}, out);
 }
 
 int khip_usymqr_workspace_adopt_vector(khip_usymqr_workspace *ws, const char *name, double *ptr) {
@@ -220,19 +201,12 @@ int khip_usymqr_workspace_destroy(khip_usymqr_workspace *ws) {
   return KHIP_OK;
 }
 
-int khip_usymqr_warm_start(khip_usymqr_workspace *ws, const double *x0) { return ws_warm_start(ws, x0, "usymqr_warm_start"); }
+int khip_usymqr_warm_start(khip_usymqr_workspace *ws, const double *x0) { return ws_warm_start(ws, kVectors, x0, "usymqr_warm_start"); }
 double *khip_usymqr_solution(khip_usymqr_workspace *ws) { return ws ? ws->x : nullptr; }
 const khip_stats *khip_usymqr_stats(khip_usymqr_workspace *ws) { return ws ? &ws->box.st : nullptr; }
 int khip_usymqr_last_path(khip_usymqr_workspace *ws) { return ws ? ws->box.path : -1; }
 double *khip_usymqr_vector(khip_usymqr_workspace *ws, const char *name) { return ws_vector(ws, kVectors, name); }
-
-size_t khip_usymqr_workspace_bytes(khip_usymqr_workspace *ws) {
-  if (!ws) return 0;
-  size_t cnt = 0;
-  for (size_t i = 0; i < sizeof(kVectors) / sizeof(kVectors[0]); ++i)
-    if (ws->*kVectors[i].slot) cnt += (size_t)side(ws, i);
-  return cnt * sizeof(double);
-}
+size_t khip_usymqr_workspace_bytes(khip_usymqr_workspace *ws) { return ws_bytes(ws, kVectors); }
 
 int khip_usymqr_aresiduals(khip_usymqr_workspace *ws, const double **aresiduals, int *naresiduals) {
   KHIP_REQUIRE(ws && aresiduals && naresiduals, "usymqr_aresiduals: null argument");
