@@ -446,50 +446,42 @@ __global__ __launch_bounds__(kBlock) void spmv_code_kernel(SpmvArgs a, RedArgs r
 // ENT: entry-coded slices (colcode.hip csr_build_sell_entries) -- code words only, a byte is the rank of the pair (column - row, value)
 //      in the handle's dictionary; offset and value come out of LDS.  One word per lane (rows of at most 8 entries), else 16-byte pairs
 
-// eight entries of an entry-coded row: eight lookups, the eight gathers issued together, then the products in stored order
+// Eight entries of an entry-coded row, one wait per phase: the eight offsets out of LDS (one wait), the gathers, the eight values out of
+// LDS behind the gathers' issue, where the address registers are dead (one wait each for LDS and for memory), then the products in stored
+// order.  No lookup, no product and no wait sits in an exec-masked block, only the gathers do: no memory instruction is issued for
+// an absent entry.  Code 0xFF reads slot 255, which exists and is zero, and an absent entry is skipped by a select, never by a
+// multiply with that zero: -0.0, Inf and NaN in acc and in x pass an absent entry untouched.  One rounded multiply and one rounded
+// add per stored entry: the bits of the serial loop.  A lane without a row passes cw = ~0.
 template <bool DIST>
 __device__ __forceinline__ double ent_step(const SpmvArgs &a, int32_t row, unsigned long long cw, const int32_t *s_off, const double *s_val, double acc) {
   double vv[8], xx[8];
   int32_t cc[8];
-  bool on[8];
+  uint32_t c[8];                                // the codes as 32-bit values: their tests and lookups take no 64-bit operation
+  const uint32_t lo = (uint32_t)cw, hi = (uint32_t)(cw >> 32);
 #pragma unroll
-  for (int u = 0; u < 8; ++u) { const int c = (int)((cw >> (8 * u)) & 0xFFull); on[u] = c != 0xFF; cc[u] = row + s_off[c]; vv[u] = s_val[c]; }
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    xx[u] = 0.0;
-    if (on[u]) xx[u] = gather_x<DIST>(a, cc[u]);
-  }
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    if (on[u]) {
-      const double prod = vv[u] * xx[u];
-      acc = acc + prod;
-    }
-  }
-  return acc;
-}
-
-// ent_step with the value lookups behind the gathers: the values are not live while the gathers are issued (the same lookups, the
-// same products in the same order -- the same bits); LDS answers long before the gathers do
-template <bool DIST>
-__device__ __forceinline__ double ent_step_late(const SpmvArgs &a, int32_t row, unsigned long long cw, const int32_t *s_off, const double *s_val, double acc) {
-  double xx[8];
-  int32_t cc[8];
-#pragma unroll
-  for (int u = 0; u < 8; ++u) cc[u] = row + s_off[(int)((cw >> (8 * u)) & 0xFFull)];
+  for (int u = 0; u < 8; ++u) { c[u] = ((u < 4 ? lo : hi) >> (8 * (u & 3))) & 0xFFu; cc[u] = s_off[c[u]]; }
+  // The empty statements emit nothing.  They make their operands opaque where they stand, so the compiler can neither sink a lookup
+  // into the exec-masked block of its one user nor the products under the caller's `row >= 0`: each phase's wait stays one wait on
+  // the path every wave takes, and the compiler can see at the top of the next trip that the queue is empty.
+  // No test reads the assembly; to re-check after a compiler change, compile this file with the flags of build.sh plus
+  // --cuda-device-only -S and compare the loop of spmv_sell_persist_kernel<true, true, false, true, true> with profiles/ent_onewait_loop.md.
+  asm volatile("" : "+v"(cc[0]), "+v"(cc[1]), "+v"(cc[2]), "+v"(cc[3]), "+v"(cc[4]), "+v"(cc[5]), "+v"(cc[6]), "+v"(cc[7]));
 #pragma unroll
   for (int u = 0; u < 8; ++u) {
     xx[u] = 0.0;
-    if (((cw >> (8 * u)) & 0xFFull) != 0xFFull) xx[u] = gather_x<DIST>(a, cc[u]);
+    if (c[u] != 0xFFu) xx[u] = gather_x<DIST>(a, row + cc[u]);
   }
 #pragma unroll
+  for (int u = 0; u < 8; ++u) vv[u] = s_val[c[u]];
+  asm volatile("" : "+v"(vv[0]), "+v"(vv[1]), "+v"(vv[2]), "+v"(vv[3]), "+v"(vv[4]), "+v"(vv[5]), "+v"(vv[6]), "+v"(vv[7]));
+  asm volatile("" : "+v"(xx[0]), "+v"(xx[1]), "+v"(xx[2]), "+v"(xx[3]), "+v"(xx[4]), "+v"(xx[5]), "+v"(xx[6]), "+v"(xx[7]));
+#pragma unroll
   for (int u = 0; u < 8; ++u) {
-    const int c = (int)((cw >> (8 * u)) & 0xFFull);
-    if (c != 0xFF) {
-      const double prod = s_val[c] * xx[u];
-      acc = acc + prod;
-    }
+    const double prod = vv[u] * xx[u];
+    const double s = acc + prod;
+    acc = c[u] != 0xFFu ? s : acc;
   }
+  asm volatile("" : "+v"(acc));
   return acc;
 }
 
@@ -567,7 +559,11 @@ __global__ __launch_bounds__(kBlock) void spmv_sell_kernel(SpmvArgs a, RedArgs r
       const int L = T - W;
       const unsigned long long *base = a.sell + (size_t)o0 * 64 + (rowl & 63);
       double acc = 0.0, wv = 0.0;
-      if (DOT) wv = a.dotw[rowl];                 // in flight beside the row's entries (2.06 -> 1.97 ms fused at 512^3, profiles/r06ap/aq)
+      // in flight beside the row's entries where the entries are loaded here (2.06 -> 1.97 ms fused at 512^3, profiles/r06ap/aq).
+      // Not in the ENT arm: its code words were loaded a block ahead inside an exec-masked block, the compiler drains the queue at
+      // the first use of them, and this load, issued in front of that use, is drained with them before any gather is issued.
+      // spmv_sell_persist_kernel<..., ONE> has no such drain in its trip: there the weight is in flight beside the gathers.
+      if (DOT) wv = a.dotw[rowl];
       if (ENT) {                                 // T words of eight entry codes and nothing else
         dbl2 ce = ent_next;                      // loaded one row block ahead
         ent_prefetch(rb + 1);                    // ... and the next block's, beside this block's gathers
@@ -710,7 +706,8 @@ __global__ __launch_bounds__(kBlock) void spmv_sell_kernel(SpmvArgs a, RedArgs r
 // workgroup waits for: the table fetch and its barrier once per launched workgroup, and the code words of the next row block loaded
 // beside the gathers of this one ACROSS the boundary between virtual workgroups.
 // ONE: every slice holds one code word per row (a.sell_units == 1, the 7-point operators): a lane carries that word instead of a
-// 16-byte pair, 60 VGPRs and 8 waves per SIMD with the compensated dot where the general walk takes 73 and 6.
+// 16-byte pair, 62 VGPRs and 8 waves per SIMD with the compensated dot where the general walk takes 73 and 6; its trip has one
+// memory wait, in front of the products.
 // Not kept: issuing the NEXT block's gathers before this block's products (124-127 VGPRs, 4 waves per SIMD, slower).
 struct SellPos { int v, rb, rb_end; };            // a row block of virtual workgroup v; behind the end: v >= nvirt, rb = rb_end = nrb
 
@@ -767,7 +764,7 @@ __global__ __launch_bounds__(kBlock) void spmv_sell_persist_kernel(SpmvArgs a, R
     double acc = 0.0;
     for (int w = 0; w < T; ++w) {
       if (w >= 2 && (w & 1) == 0) ce = ld<NTM>(pb + (size_t)(w >> 1) * 64);
-      acc = ent_step_late<DIST>(a, (int32_t)rowl, (unsigned long long)__double_as_longlong((w & 1) ? ce.y : ce.x), s_off, s_val, acc);
+      acc = ent_step<DIST>(a, (int32_t)rowl, (unsigned long long)__double_as_longlong((w & 1) ? ce.y : ce.x), s_off, s_val, acc);
     }
     return acc;
   };
@@ -807,14 +804,31 @@ __global__ __launch_bounds__(kBlock) void spmv_sell_persist_kernel(SpmvArgs a, R
     for (int i = tid; i < 256; i += kBlock) { s_off[i] = eo[i]; s_val[i] = ev[i]; }
     __syncthreads();
   }
+  // ONE: the first block's code word is waited for here, once, on the path every wave takes.  Left to its first use the wait
+  // would stand in the loop, and from the second trip on it would wait for the y store of the trip before.
+  if (ONE) asm volatile("" : "+v"(ent_next.x));
   while (cur.v < nvirt) {                      // depends on blockIdx only: every barrier below is reached by all four waves
     const SellPos nxt = next_of(cur);
     const int64_t rowl = lane_row(cur);
-    double wv = 0.0;
-    if (DOT && rowl >= 0) wv = a.dotw[rowl];
-    const dbl2 ce = ent_next;                  // loaded one row block ahead
-    load_codes(nxt, ent_next);                 // ... and the next block's, beside this block's gathers
-    if (rowl >= 0) finish_row(rowl, walk_row(rowl, ce), wv);
+    if (ONE) {
+      // One wait per phase.  The code word of this block was loaded one block ahead, and the wait in front of the previous
+      // block's products retired it: nothing stands between the top of a trip and the issue of its gathers but the offsets' LDS
+      // lookup.  The row walk is not under `rowl >= 0` (a lane without a row walks eight absent entries), so that wait is on every
+      // path and the compiler need not drain the queue up here -- which also puts the dot's weight, loaded here, in flight beside
+      // the gathers (carrying it a block ahead like the code word measured no gain on top of that and cost two VGPRs: not kept).
+      const unsigned long long cw = rowl >= 0 ? (unsigned long long)__double_as_longlong(ent_next.x) : ~0ull;
+      double wv = 0.0;
+      if (DOT && rowl >= 0) wv = a.dotw[rowl];
+      load_codes(nxt, ent_next);               // the next block's, beside this block's gathers
+      const double acc = ent_step<DIST>(a, (int32_t)rowl, cw, s_off, s_val, 0.0);
+      if (rowl >= 0) finish_row(rowl, acc, wv);
+    } else {
+      double wv = 0.0;
+      if (DOT && rowl >= 0) wv = a.dotw[rowl];   // behind the queue's drain at the top of the trip (the code words of the block before)
+      const dbl2 ce = ent_next;                // loaded one row block ahead
+      load_codes(nxt, ent_next);               // ... and the next block's, beside this block's gathers
+      if (rowl >= 0) finish_row(rowl, walk_row(rowl, ce), wv);
+    }
     if (nxt.v != cur.v) publish(cur.v);
     cur = nxt;
   }
